@@ -21,8 +21,16 @@ Either way each rank holds band-sized buffers only and receives its feature rows
 point-to-point from rank 0 over RCCL/xGMI; with one rank the same code path runs with an empty
 exchange.  Outputs stay sharded; --gather additionally times assembling the image on rank 0.
 
-After the timed loop the output that was timed is compared with the CPU oracle on a few HR row
-bands ("checked"); the run fails if that is out of tolerance.
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write the
+timed output if --dump-outputs DIR is given, print the line.  --full adds everything else the
+benchmark measures or checks: the timed output against the CPU oracle on a few HR row bands
+("checked"; the run fails if that is out of tolerance), the split-bf16, target-shape, side,
+whole-model and strong-scaling legs, the in-run HBM traffic passes and the CPU baseline.
+
+--dump-outputs DIR: after the timed steps each rank writes the HR output of the last timed step
+(what a caller of the path receives; its own band when N > 1) as DIR/output.npy (float32; N > 1:
+DIR/output_rank<r>.npy).  An output above the 64 MB budget is cut to a fixed, seeded sample of
+whole HR rows.  Inputs and weights are seeded, so the same arguments give the same inputs.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -145,7 +153,7 @@ def parse():
                     help="arithmetic of the per-pixel layers; f32 is the reference's precision and the only "
                          "valid headline (bf16 is BASELINE config 5's optional path, 2e-3 relative; bf16x3 = split "
                          "bf16, three bf16 MFMA products per term, held to f32's 1e-4)")
-    ap.add_argument("--no-split", action="store_true", help="skip the split-bf16 side leg of the default run")
+    ap.add_argument("--no-split", action="store_true", help="skip the split-bf16 side leg of a --full run")
     ap.add_argument("--dist-mode", choices=["halo", "bcast"], default="halo")
     ap.add_argument("--gather", action="store_true", help="also time assembling the image on rank 0 (reported "
                                                            "as gather_ms, never part of value)")
@@ -170,7 +178,37 @@ def parse():
                                                               "roofline.traffic (the committed measurement is reported, labelled)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the oracle check, the extra legs, the traffic passes, "
+                         "the CPU baseline (each --no-* option above then turns one of them off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/output.npy (N > 1: output_rank<r>.npy per rank)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64_000_000          # all dumped arrays together, .npy headers included
+
+
+def dump_rows(hu_rows, row_bytes, budget):
+    """HR rows (band-relative indices) to dump: all of them if they fit ``budget`` bytes, else a fixed, seeded, sorted
+    sample of whole rows that does."""
+    import numpy as np
+    keep = max(1, (budget - 4096) // row_bytes)
+    if hu_rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(2024).choice(hu_rows, size=keep, replace=False))
+
+
+def dump_outputs(directory, out_band, rank, world):
+    """The timed path's output (this rank's band, (B, 3, rows, WU) float32) -> directory/<name>.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = out_band.float().cpu().numpy()
+    rows = dump_rows(out.shape[2], out.shape[0] * out.shape[1] * out.shape[3] * out.itemsize, DUMP_BUDGET_BYTES // world)
+    if rows is not None:
+        out = np.ascontiguousarray(out[:, :, rows])
+    name = "output.npy" if world == 1 else f"output_rank{rank}.npy"
+    np.save(os.path.join(directory, name), out)
 
 
 def effective_cores() -> int:
@@ -780,16 +818,19 @@ def main():
     world, rank = job.world, job.rank
     N = job.N
     census = job.census()
+    full = args.full                                       # everything beyond the headline runs only with --full
 
-    r = run_workload(job, args.workload, args.scaling, args.steps, args.warmup, check=not args.no_check,
+    r = run_workload(job, args.workload, args.scaling, args.steps, args.warmup, check=full and not args.no_check,
                      gather=args.gather)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["dec"].out_band, rank, world)
     elapsed, bd = r["elapsed"], r["bd"]
     H, W, HU, WU, wl_label = r["H"], r["W"], r["HU"], r["WU"], r["label"]
     (h1, w1), (hu1, wu1), _ = WORKLOADS[args.workload]
     step_ms, hand_ms, p_ms, k_ms_all = r["step_ms"], r["hand_ms"], r["p_ms"], r["k_ms_all"]
     event_steps = r["event_steps"]
     checked, gather_ms, gather_ok = r.get("checked"), r.get("gather_ms"), r.get("gather_ok")
-    feat_cpu = r["feat"].cpu() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    feat_cpu = r["feat"].cpu() if (full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     hand_max = job.reduce_max([statistics.median(hand_ms)])[0]
     # which form of the hoisted conv the library ran for this launch (diinn_p_launch_info: env overrides included)
     p_algo = C.c_int(0)
@@ -800,7 +841,7 @@ def main():
     torch.cuda.empty_cache()
 
     split = None
-    if world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_split:
+    if full and world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_split:
         # the same workload in the optional split-bf16 mode (DIINN_COMPUTE_BF16X3: bf16 MFMAs, three products per term,
         # held to the fp32 bound by the same post-run check): reported beside the fp32 line, never as `value`
         t = run_workload(job, "c2", "weak", args.steps, args.warmup, compute="bf16x3")
@@ -815,10 +856,10 @@ def main():
         del t
         torch.cuda.empty_cache()
     strong = None
-    if world > 1 and not args.no_strong:
+    if full and world > 1 and not args.no_strong:
         strong = strong_legs(job)
     target = None
-    if world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_target:
+    if full and world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_target:
         # the north_star's target shape (1024^2 -> 4096^2 on one GPU) timed by the same run: 1 warm-up + 2 steps
         t = run_workload(job, "tgt", "strong", 2, 1, check=False)
         t_k = sum(t["k_ms_all"]) / len(t["k_ms_all"])
@@ -833,7 +874,7 @@ def main():
         torch.cuda.empty_cache()
 
     side = whole = None
-    if world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_side_legs:
+    if full and world == 1 and args.workload == "c2" and args.compute == "f32" and not args.no_side_legs:
         side = [side_leg(job, n, c, st, wu_, check=not args.no_check) for (n, c, st, wu_) in SIDE_LEGS]
         try:
             whole = whole_model_leg(job.dev)
@@ -863,7 +904,9 @@ def main():
         traffic, traffic_source = None, None
         if not bf and args.workload == "c2" and world == 1:
             why = "--no-traffic"
-            if "rocprofiler" in os.environ.get("LD_PRELOAD", ""):
+            if not full:
+                why = "measured only with --full"
+            elif "rocprofiler" in os.environ.get("LD_PRELOAD", ""):
                 why = "this run is itself being profiled"
             elif not args.no_traffic:
                 traffic, traffic_source = measure_traffic(args)

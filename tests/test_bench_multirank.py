@@ -30,7 +30,7 @@ def _run_bench(nproc, *extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--backend", "gloo", "--steps", "3", "--warmup", "1",
-           *extra]
+           "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -40,15 +40,15 @@ def _run_bench(nproc, *extra):
 
 def _run_driver_command(nproc, steps=3, warmup=1, backend="gloo", timeout=1500):
     """The driver's LITERAL command (task contract): ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W`` -- no other flag; the one-device test
-    transport is selected through the environment only."""
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W`` plus ``--full`` (the checks and legs
+    asserted on) -- no other flag; the one-device test transport is selected through the environment only."""
     import time
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     if backend == "gloo":
         env.update(DIINN_BENCH_ONE_DEVICE="1", DIINN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", str(steps), "--warmup", str(warmup)]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", str(steps), "--warmup", str(warmup), "--full"]
     t0 = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     wall = time.time() - t0
@@ -59,13 +59,13 @@ def _run_driver_command(nproc, steps=3, warmup=1, backend="gloo", timeout=1500):
 
 
 def _run_bare_command(nproc, steps=3, warmup=1, timeout=1500, extra=()):
-    """The BARE form ``python3 bench.py --gpus N --steps K --warmup W`` -- no launcher around it, WORLD_SIZE unset: bench.py
+    """The BARE form ``python3 bench.py --gpus N --steps K --warmup W --full`` -- no launcher around it, WORLD_SIZE unset: bench.py
     starts its own N ranks as a child ``torch.distributed.run`` before anything touches the GPU, relays rank 0's line and
     exits with the child's code (the first 8-GPU lease must not depend on the launch form)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", DIINN_BENCH_ONE_DEVICE="1", DIINN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", str(steps), "--warmup", str(warmup),
-           *extra]
+           "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "starting the ranks as a child" in r.stderr
@@ -127,7 +127,7 @@ def test_bare_command_two_ranks_starts_its_own_ranks():
 
 
 def test_bare_command_eight_ranks_starts_its_own_ranks():
-    """``python3 bench.py --gpus 8 --steps 3 --warmup 1`` as typed: eight ranks, one JSON line.  (The default strong legs ran
+    """``python3 bench.py --gpus 8 --steps 3 --warmup 1 --full`` as typed: eight ranks, one JSON line.  (The default strong legs ran
     in the torchrun form above; here they are replaced by a small one to keep eight processes on one GPU short.)"""
     res = _run_bare_command(8, extra=("--strong-legs", "c1", "--strong-steps", "2"))
     _check_census(res, 8, "gloo", 1)
