@@ -602,7 +602,7 @@ int diinn_conv3x3_x3(void* stream, const float* in_dev, long long in_bs, int Cin
     return launch_conv_x3(stream, p);
 }
 
-// the same layer inside the trunk (diinn_rdn_forward_x3): inputs from the planes `in_dev`, or -- in_dev null -- all Cin channels
+// the same layer inside the trunk (DIINN_RDN_ALGO_X3): inputs from the planes `in_dev`, or -- in_dev null -- all Cin channels
 // from the split-format buffer xs; outputs to the planes `out_dev` (may be null) and, when xs_out_g8 >= 0, to channel groups
 // xs_out_g8 .. + 7 of xs
 __attribute__((visibility("hidden")))

@@ -338,7 +338,7 @@ int launch_P_wino(void* stream, const float* feat_dev, const float* packed_dev, 
 __attribute__((visibility("hidden")))
 int launch_decode_bf16(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
 // diinn_conv_x3.hip: a split-bf16 3x3 layer reading planes or the trunk's split-format buffer (and optionally extending it);
-// a block's 1x1 fusion layer from that buffer (diinn_rdn_forward_x3)
+// a block's 1x1 fusion layer from that buffer (diinn_rdn_forward_ex, DIINN_RDN_ALGO_X3)
 extern "C" __attribute__((visibility("hidden")))
 int diinn_conv3x3_x3_split(void* stream, const float* in_dev, long long in_bs, float* xs_dev, long long xs_bs16, int xs_out_g8,
                            int Cin, const float* wx_dev, const float* bias_dev, float* out_dev, long long out_bs, int relu,

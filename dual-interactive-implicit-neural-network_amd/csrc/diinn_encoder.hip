@@ -17,7 +17,7 @@
 // on the 3x3 layers run as Winograd F(2x2,3x3) in csrc/diinn_winograd.hip.
 // Measured against MIOpen (PyTorch-ROCm), whole encoder: 2.0 vs 7.4 ms at 48x48, 3.8 vs 7.9 at 128x128, 11.7 vs 28.1
 // at 256x256, 46.0 vs 108.1 at 512x512 (tools/enc_trunk_time.py; round 1, this kernel alone: 2.1 / 6.5 / 23.9 / 96.9).
-// diinn_rdn_forward[_wino] runs the whole trunk (everything after SFENet1) as 147 launches from C++.
+// diinn_rdn_forward_ex runs the whole trunk (everything after SFENet1) as 147 launches from C++.
 #include "diinn_device.h"
 
 constexpr int CS_WAVES = 8;                       // K-split: waves per workgroup, each 1/8 of the input channels
@@ -569,6 +569,50 @@ static int launch_conv_ksplit(void* stream, const ConvKsplitParams& p_in, int ta
     return hip_status(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The 147 layers of the trunk after SFENet1 in execution order (rdn.py:97-103; RDN._trunk_layers on the module side):
+// SFENet2, 16 blocks x (8 dense 3x3 convs over 64 (c + 1) inputs, LFF 1x1 576), GFF.0 1x1 1024, GFF.1 3x3 64.  Every layer
+// has 64 outputs; each weight image holds its layers back to back in this order.
+struct RdnLayer { int cin, taps; };
+constexpr int RDN_LAYERS = 1 + 16 * 9 + 2;
+constexpr RdnLayer rdn_layer(int l) {
+    return l == 0 || l == RDN_LAYERS - 1 ? RdnLayer{64, 9}
+         : l == RDN_LAYERS - 2           ? RdnLayer{1024, 1}
+         : (l - 1) % 9 < 8               ? RdnLayer{64 * ((l - 1) % 9 + 1), 9}
+                                         : RdnLayer{576, 1};
+}
+constexpr size_t rdn_cin_sum(int taps, int end = RDN_LAYERS) {   // sum of Cin over the layers [0, end) with `taps` taps
+    size_t n = 0;
+    for (int l = 0; l < end; ++l) n += rdn_layer(l).taps == taps ? rdn_layer(l).cin : 0;
+    return n;
+}
+constexpr size_t RDN_CIN_3X3 = rdn_cin_sum(9), RDN_CIN_1X1 = rdn_cin_sum(1);
+constexpr size_t RDN_CIN_LFF = rdn_cin_sum(1, RDN_LAYERS - 2);     // the 16 local fusions: the 1x1 layers before GFF.0
+static_assert(RDN_CIN_3X3 == 36992 && RDN_CIN_1X1 == 10240 && RDN_CIN_LFF == 16 * 576, "the trunk's layer list");
+
+// One cursor over the weight images: every layer takes its slices with exactly one next(cin, taps), in execution order.  It
+// counts input channels rather than moving pointers, so an absent image stays NULL and no pointer leaves its image.
+struct RdnWeights {
+    struct Slices { const float *w, *wu, *wu4, *wx, *bias; };
+    const float *w, *wu, *wu4, *wx, *bias;   // direct, F(2x2), F(4x4), split-bf16 images (the last three may be NULL); biases
+    size_t c3 = 0, c1 = 0;                   // input channels of the 3x3 / 1x1 layers walked so far
+    int layers = 0;
+    Slices next(int cin, int taps) {
+        auto at = [](const float* img, size_t off) { return img ? img + off : nullptr; };
+        Slices s{w + 64 * (9 * c3 + c1), nullptr, nullptr, nullptr, bias + 64 * layers};
+        if (taps == 9) {
+            s.wu = at(wu, 64 * 16 * c3); s.wu4 = at(wu4, 64 * 36 * c3); s.wx = at(wx, 64 * 9 * c3);
+            c3 += cin;
+        } else {
+            // the split-bf16 image holds the local fusions after its 3x3 layers (none for GFF.0)
+            if (c1 < RDN_CIN_LFF) s.wx = at(wx, 64 * (9 * RDN_CIN_3X3 + c1));
+            c1 += cin;
+        }
+        ++layers;
+        return s;
+    }
+};
+
 extern "C" {
 
 int diinn_conv_ksplit(void* stream, const float* in_dev, long long in_batch_stride, int Cin, int taps,
@@ -609,51 +653,28 @@ int diinn_sfe1_forward(void* stream, const float* x_dev, int Cin, const float* w
 }
 
 size_t diinn_rdn_packed_floats(void) {
-    // SFENet2 64*64*9; 16 x [8 dense convs 64*(64..512)*9 + LFF 64*576]; GFF 64*1024 + 64*64*9
-    size_t n = (size_t)64 * 64 * 9;
-    for (int c = 0; c < 8; ++c) n += (size_t)16 * 64 * (64 + 64 * c) * 9;
-    n += (size_t)16 * 64 * 576 + (size_t)64 * 1024 + (size_t)64 * 64 * 9;
-    return n;
-}
-
-size_t diinn_rdn_workspace_floats(int B, int H, int W) {
-    // the four one-algorithm entry points (kept for one ABI version): [the F(4x4,3x3) kernel's split area (counters first: they
-    // are zeroed at the start of every forward)][two dense buffers 576][global fusion input 1024][64]
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return diinn_conv_wino4_workspace_floats() + (size_t)B * H * W * (2 * 576 + 1024 + 64);
+    return 64 * (9 * RDN_CIN_3X3 + RDN_CIN_1X1);                 // every layer, 64 x Cin x taps
 }
 
 size_t diinn_rdn_planes_floats(int algo, int B, int H, int W) {
     // diinn_rdn_forward_ex's planes: [two dense buffers 576][global fusion input 1024][64] (+ for DIINN_RDN_ALGO_X3 the
-    // split-format copy of one dense buffer: [B][72 groups][hi, lo][H][W] x 16 bytes); the F(4x4) split area is a buffer of its own there
+    // split-format copy of one dense buffer: [B][72 groups][hi, lo][H][W] x 16 bytes); the F(4x4) split area is a buffer of its own
     if (B <= 0 || H <= 0 || W <= 0 || algo < DIINN_RDN_ALGO_AUTO || algo > DIINN_RDN_ALGO_X3) return 0;
     return (size_t)B * H * W * (2 * 576 + 1024 + 64 + (algo == DIINN_RDN_ALGO_X3 ? 576 : 0));
 }
 
 size_t diinn_rdn_wino_packed_floats(void) {
-    // the 3x3 layers only, 16 floats per (output, input) pair: SFENet2, 16 x 8 dense convs, GFF.1
-    size_t n = (size_t)2 * 64 * 64 * 16;
-    for (int c = 0; c < 8; ++c) n += (size_t)16 * 64 * (64 + 64 * c) * 16;
-    return n;
+    return 64 * 16 * RDN_CIN_3X3;                                // the 3x3 layers only, 16 floats per (output, input) pair
 }
 
 size_t diinn_rdn_wino4_packed_floats(void) {
     // the 3x3 layers only, 36 floats per (output, input) pair (F(4x4, 3x3): csrc/diinn_winograd4.hip)
-    return diinn_rdn_wino_packed_floats() / 16 * 36;
-}
-
-size_t diinn_rdn_x3_workspace_floats(int B, int H, int W) {
-    // diinn_rdn_workspace_floats + the split-format copy of one dense buffer ([B][72 groups][hi, lo][H][W] x 16 bytes)
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return diinn_rdn_workspace_floats(B, H, W) + (size_t)B * 576 * H * W;
+    return 64 * 36 * RDN_CIN_3X3;
 }
 
 size_t diinn_rdn_x3_packed_floats(void) {
-    // the 3x3 layers, 9 taps x (hi + lo) bf16 = 9 floats per (output, input) pair: SFENet2, 16 x 8 dense convs, GFF.1 in
-    // execution order; then the 16 local-fusion 1x1 layers, 1 float per pair
-    size_t n = (size_t)2 * 64 * 64 * 9;
-    for (int c = 0; c < 8; ++c) n += (size_t)16 * 64 * (64 + 64 * c) * 9;
-    return n + (size_t)16 * 64 * 576;
+    // the 3x3 layers, 9 taps x (hi + lo) bf16 = 9 floats per (output, input) pair; then the 16 local fusions, 1 float per pair
+    return 64 * (9 * RDN_CIN_3X3 + RDN_CIN_LFF);
 }
 
 int diinn_rdn_wino4_applies(int B, int H, int W) {
@@ -670,131 +691,13 @@ int diinn_rdn_wino4_applies(int B, int H, int W) {
     return r4 < 0.97 * (r2w < r2h ? r2w : r2h);
 }
 
+// ---- the trunk's ONE entry point: which kernel family the 3x3 layers may take is an argument, the images it may read are the
+// ones given.  AUTO = the fastest fp32 form the given images allow (the rules below); DIRECT / WINO / WINO4 cap the family;
+// X3 = split bf16 on large maps, asked for explicitly (optional arithmetic).
 // planes: diinn_rdn_planes_floats; w4ws: the F(4x4) kernel's split area (diinn_conv_wino4_workspace_floats; NULL: no layer is split)
-static int rdn_forward_impl(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                            const float* packed_wino4_dev, const float* packed_x3_dev,
-                            const float* biases_dev, float* planes, float* w4ws, float* out_dev, int B, int H, int W,
-                            bool zero_status = false) {
-    if (!sfe1_dev || !packed_dev || !biases_dev || !planes || !out_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    const long long hw = (long long)H * W;
-    // Winograd blocks are 16 x 8 pixels and a workgroup walks all input channels: faster than the split-K kernel from
-    // about 90 x 90 pixels up (tools/r02_ab_env.sh: 96x96 3.6 vs 4.5 ms, 64x64 3.4 vs 2.1 ms per trunk)
-    const long long wino_min = knob(diinn_knobs().enc_wino_min);
-    const bool wino = (packed_wino_dev || packed_wino4_dev) && (long long)B * hw >= wino_min;
-    // F(4x4, 3x3) (csrc/diinn_winograd4.hip): 1.78x fewer MFMAs again, in work items of 128 x 4 pixels x one output half.
-    // Both kernels run in rounds of one workgroup per CU, and measured over 192 .. 512-pixel maps one F(4x4) round
-    // costs 1.40 F(2x2) rounds of whole blocks (16 x 8 pixels x both halves; a round of halves 0.57; r04 measured 1.44, r05 1.40): the cheaper one
-    // by that count runs.  DIINN_ENC_WINO4_MIN = n >= 0 replaces the rule by "from n pixels on".
-    const bool wino4 = packed_wino4_dev && wino && diinn_rdn_wino4_applies(B, H, W);
-    if (wino && !wino4 && !packed_wino_dev) return DIINN_ERR_INVALID_ARG;   // this map runs F(2x2): its image is needed
-    // the F(4x4) kernel's split area leads the workspace; its arrival counters (the first 2 KiB) are zeroed here, once per
-    // forward, whatever a caller or an aborted launch left there (a memset node: capture-safe).  NOT the sticky status
-    // word behind them (word 1023 of the first 4 KiB, which the workspace's owner zeroes once when it allocates): a
-    // hand-off that gave up stays visible -- NaN features from then on -- until diinn_conv_wino4_ws_status has cleared it
-    const size_t w4ws_floats = w4ws ? diinn_conv_wino4_workspace_floats() : 0;
-    if (wino4 && w4ws) {
-        st = hip_status(hipMemsetAsync(w4ws, 0, zero_status ? 4096 : DIINN_WINO4_COUNTER_BYTES, (hipStream_t)stream));
-        if (st) return st;
-    }
-    float* buf[2] = {planes, planes + (size_t)B * 576 * hw};                   // dense buffers [B,576,H,W]
-    float* gff_in = planes + (size_t)2 * B * 576 * hw;                           // [B,1024,H,W]
-    float* tmp = gff_in + (size_t)B * 1024 * hw;                                 // [B,64,H,W]
-    // split-bf16 3x3 layers (csrc/diinn_conv_x3.hip; optional): blocks of 32 x 8 pixels; they pay from about 0.8 blocks
-    // per CU on (measured per trunk, x3 vs Winograd: 160x160 7.8 vs 6.2 ms, 192x192 7.2 vs 9.3, 224x224 7.5 vs 11.4, 256x256 8.6 vs 11.8,
-    // 384x384 20.8 vs 28.0, 512x512 32.9 vs 46.5)
-    const bool x3 = packed_x3_dev && (long long)B * hw >= knob(diinn_knobs().enc_x3_min);
-    // small maps (csrc/diinn_conv_t16.hip): the direct sum in units of (1 .. 3 rows x 16 pixels, 16 outputs) where the split-K
-    // kernel's units leave compute units idle; the same weight image (per trunk: 48x48 1.95 -> 1.85 ms, 40x40 1.92 -> 1.44, 32x32 1.87 -> 1.05)
-    const bool t16 = !wino && !x3 && diinn_conv_t16_applies(B, H, W) != 0 &&
-                     ((((size_t)sfe1_dev) | ((size_t)planes) | ((size_t)packed_dev)) & 15) == 0;   // (its 16-byte LDS-DMA pieces; else the split-K kernel, as before)
-    const float* w = packed_dev;
-    const float* wu = packed_wino_dev;
-    const float* wu4 = packed_wino4_dev;
-    const float* wx = packed_x3_dev;
-    const float* bias = biases_dev;
-    auto conv = [&](const float* in, long long in_bs, int cin, int taps, const float* res, long long res_bs,
-                    float* o0, long long o0_bs, float* o1, long long o1_bs, int relu) {
-        const int s = (x3 && taps == 9 && !o1)
-            ? diinn_conv3x3_x3(stream, in, in_bs, cin, wx, bias, res, res_bs, o0, o0_bs, relu, B, H, W)
-            : (wino4 && taps == 9 && !o1)
-            ? diinn_conv_wino4_ws(stream, in, in_bs, cin, wu4, bias, res, res_bs, o0, o0_bs, relu, B, H, W, w4ws, w4ws_floats)
-            : (wino && taps == 9 && !o1)
-            ? diinn_conv_wino(stream, in, in_bs, cin, wu, bias, res, res_bs, o0, o0_bs, relu, B, H, W)
-            : (t16 && taps == 9 && !o1)
-            ? diinn_conv_t16(stream, in, in_bs, cin, w, bias, res, res_bs, o0, o0_bs, relu, B, H, W)
-            : (t16 && taps == 1 && cin <= 640)
-            ? diinn_conv1x1_t16(stream, in, in_bs, cin, w, bias, res, res_bs, o0, o0_bs, o1, o1_bs, relu, B, H, W)
-            : diinn_conv_ksplit(stream, in, in_bs, cin, taps, w, bias, res, res_bs, o0, o0_bs, o1, o1_bs, relu, B, H, W);
-        w += (size_t)64 * cin * taps;
-        if (taps == 9 && wu) wu += (size_t)64 * cin * 16;
-        if (taps == 9 && wu4) wu4 += (size_t)64 * cin * 36;
-        if (taps == 9 && wx) wx += (size_t)64 * cin * 9;
-        bias += 64;
-        return s;
-    };
-    float* xs = tmp + (size_t)B * 64 * hw;                                       // x3 only: the block's channels in split format
-    const long long xs_bs16 = 144 * hw;                                          // 72 groups x (hi, lo) planes of 16-byte pixels
-    size_t n3 = (size_t)2 * 64 * 64 * 9;
-    for (int c = 0; c < 8; ++c) n3 += (size_t)16 * 64 * (64 + 64 * c) * 9;
-    const float* wx1 = packed_x3_dev ? packed_x3_dev + n3 : nullptr;             // the fusion layers' split-bf16 weights
-    // SFENet2: 64 -> 64 into channels [0,64) of the first dense buffer (rdn.py:97); x3: also groups 0..7 of the split buffer
-    if (x3) {
-        st = diinn_conv3x3_x3_split(stream, sfe1_dev, 64 * hw, xs, xs_bs16, 0, 64, wx, bias, buf[0], 576 * hw, 0, B, H, W);
-        w += (size_t)64 * 64 * 9; wu += (size_t)64 * 64 * 16; wx += (size_t)64 * 64 * 9; bias += 64;
-        if (wu4) wu4 += (size_t)64 * 64 * 36;
-    } else {
-        st = conv(sfe1_dev, 64 * hw, 64, 9, nullptr, 0, buf[0], 576 * hw, nullptr, 0, 0);
-    }
-    if (st) return st;
-    for (int d = 0; d < 16; ++d) {
-        float* cur = buf[d & 1];
-        float* nxt = buf[(d + 1) & 1];
-        if (x3) {
-            // inside the trunk the layers exchange their activations already split (csrc/diinn_conv_x3.hip): every dense conv
-            // reads ALL its inputs from the split buffer (two 16-byte copies per staged pixel instead of eight loads and a
-            // conversion, redone by each of the up to eight layers that read a channel) and appends its outputs to it --
-            // ONLY to it: the fp32 planes of the dense channels have no reader left, which halves the store burst at the end
-            // of every layer (at 256x256 the epilogue's 33 MB were 10 of a layer's 23-92 us); the fusion layer reads the
-            // split buffer whole and writes the next block's first 64 channels back in place, next to the planes
-            for (int c = 0; c < 8; ++c) {
-                st = diinn_conv3x3_x3_split(stream, nullptr, 0, xs, xs_bs16, 8 * (c + 1), 64 * (c + 1), wx, bias,
-                                            nullptr, 0, 1, B, H, W);
-                if (st) return st;
-                w += (size_t)64 * 64 * (c + 1) * 9;
-                wu += (size_t)64 * 64 * (c + 1) * 16;
-                if (wu4) wu4 += (size_t)64 * 64 * (c + 1) * 36;
-                wx += (size_t)64 * 64 * (c + 1) * 9;
-                bias += 64;
-            }
-            st = diinn_conv1x1_x3_split(stream, xs, xs_bs16, 576, wx1 + (size_t)d * 64 * 576, bias, cur, 576 * hw, nxt, 576 * hw,
-                                        gff_in + (size_t)64 * d * hw, 1024 * hw, B, H, W);
-            if (st) return st;
-            w += (size_t)64 * 576;
-            bias += 64;
-            continue;
-        } else
-        for (int c = 0; c < 8; ++c) {                            // dense 3x3 convs: read channels [0, 64(c+1)), append 64 (rdn.py:15-17)
-            st = conv(cur, 576 * hw, 64 * (c + 1), 9, nullptr, 0, cur + (size_t)64 * (c + 1) * hw, 576 * hw, nullptr, 0, 1);
-            if (st) return st;
-        }
-        // LFF 1x1 576 -> 64 plus the block input (rdn.py:34): next block's input and the d-th slice of the global fusion input
-        st = conv(cur, 576 * hw, 576, 1, cur, 576 * hw, nxt, 576 * hw, gff_in + (size_t)64 * d * hw, 1024 * hw, 0);
-        if (st) return st;
-    }
-    // GFF: 1x1 1024 -> 64, then 3x3 64 -> 64, plus the shallow features (rdn.py:100-103)
-    st = conv(gff_in, 1024 * hw, 1024, 1, nullptr, 0, tmp, 64 * hw, nullptr, 0, 0);
-    if (st) return st;
-    return conv(tmp, 64 * hw, 64, 9, sfe1_dev, 64 * hw, out_dev, 64 * hw, nullptr, 0, 0);
-}
-
-// ---- ONE trunk entry point (ABI v9): which kernel family the 3x3 layers may take is an argument, the images it may read are
-// the ones given.  AUTO = the fastest fp32 form the given images allow (the rules above); DIRECT / WINO / WINO4 cap the family
-// (the result of the four former entry points); X3 = split bf16 on large maps, asked for explicitly (optional arithmetic).
-static int rdn_forward_algo(void* stream, int algo, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                            const float* packed_wino4_dev, const float* packed_x3_dev, const float* biases_dev,
-                            float* planes_dev, float* w4ws_dev, float* out_dev, int B, int H, int W, bool zero_status) {
+int diinn_rdn_forward_ex(void* stream, int algo, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
+                         const float* packed_wino4_dev, const float* packed_x3_dev, const float* biases_dev,
+                         float* planes, float* w4ws, float* out_dev, int B, int H, int W) {
     switch (algo) {
         case DIINN_RDN_ALGO_AUTO: packed_x3_dev = nullptr; break;
         case DIINN_RDN_ALGO_DIRECT: packed_wino_dev = packed_wino4_dev = packed_x3_dev = nullptr; break;
@@ -814,51 +717,101 @@ static int rdn_forward_algo(void* stream, int algo, const float* sfe1_dev, const
             break;
         default: return DIINN_ERR_INVALID_ARG;
     }
-    if ((((size_t)planes_dev) & 15) || (((size_t)w4ws_dev) & 15)) return DIINN_ERR_INVALID_ARG;
-    return rdn_forward_impl(stream, sfe1_dev, packed_dev, packed_wino_dev, packed_wino4_dev, packed_x3_dev, biases_dev, planes_dev,
-                            w4ws_dev, out_dev, B, H, W, zero_status);
-}
-
-int diinn_rdn_forward_ex(void* stream, int algo, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                         const float* packed_wino4_dev, const float* packed_x3_dev, const float* biases_dev,
-                         float* planes_dev, float* w4ws_dev, float* out_dev, int B, int H, int W) {
-    return rdn_forward_algo(stream, algo, sfe1_dev, packed_dev, packed_wino_dev, packed_wino4_dev, packed_x3_dev, biases_dev, planes_dev,
-                            w4ws_dev, out_dev, B, H, W, false);
-}
-
-// ---- the four one-algorithm entry points of ABI <= 8: thin wrappers, to be dropped with the next ABI number.  Their single
-// workspace is [F(4x4) split area][planes] (diinn_rdn_workspace_floats / diinn_rdn_x3_workspace_floats).
-static int rdn_forward_v8(void* stream, int algo, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                          const float* packed_wino4_dev, const float* packed_x3_dev, const float* biases_dev,
-                          float* workspace_dev, float* out_dev, int B, int H, int W) {
-    if (!workspace_dev) return DIINN_ERR_INVALID_ARG;
-    // ABI <= 8 promised "the first 4 KiB are zeroed by the forward itself" (callers hand in uninitialised workspaces): all control
-    // words, the status word included -- so these entry points have no sticky status (a give-up is still NaN in that forward's output)
-    return rdn_forward_algo(stream, algo, sfe1_dev, packed_dev, packed_wino_dev, packed_wino4_dev, packed_x3_dev, biases_dev,
-                            workspace_dev + diinn_conv_wino4_workspace_floats(), workspace_dev, out_dev, B, H, W, true);
-}
-
-int diinn_rdn_forward(void* stream, const float* sfe1_dev, const float* packed_dev, const float* biases_dev,
-                      float* workspace_dev, float* out_dev, int B, int H, int W) {
-    return rdn_forward_v8(stream, DIINN_RDN_ALGO_DIRECT, sfe1_dev, packed_dev, nullptr, nullptr, nullptr, biases_dev, workspace_dev, out_dev, B, H, W);
-}
-
-int diinn_rdn_forward_wino(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                           const float* biases_dev, float* workspace_dev, float* out_dev, int B, int H, int W) {
-    return rdn_forward_v8(stream, DIINN_RDN_ALGO_WINO, sfe1_dev, packed_dev, packed_wino_dev, nullptr, nullptr, biases_dev, workspace_dev, out_dev, B, H, W);
-}
-
-int diinn_rdn_forward_wino4(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                            const float* packed_wino4_dev, const float* biases_dev, float* workspace_dev, float* out_dev,
-                            int B, int H, int W) {
-    return rdn_forward_v8(stream, DIINN_RDN_ALGO_WINO4, sfe1_dev, packed_dev, packed_wino_dev, packed_wino4_dev, nullptr, biases_dev, workspace_dev,
-                          out_dev, B, H, W);
-}
-
-int diinn_rdn_forward_x3(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                         const float* packed_x3_dev, const float* biases_dev, float* workspace_dev, float* out_dev,
-                         int B, int H, int W) {
-    return rdn_forward_v8(stream, DIINN_RDN_ALGO_X3, sfe1_dev, packed_dev, packed_wino_dev, nullptr, packed_x3_dev, biases_dev, workspace_dev, out_dev, B, H, W);
+    if ((((size_t)planes) & 15) || (((size_t)w4ws) & 15)) return DIINN_ERR_INVALID_ARG;
+    if (!sfe1_dev || !packed_dev || !biases_dev || !planes || !out_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    const long long hw = (long long)H * W;
+    // Winograd blocks are 16 x 8 pixels and a workgroup walks all input channels: faster than the split-K kernel from
+    // about 90 x 90 pixels up (tools/r02_ab_env.sh: 96x96 3.6 vs 4.5 ms, 64x64 3.4 vs 2.1 ms per trunk)
+    const long long wino_min = knob(diinn_knobs().enc_wino_min);
+    const bool wino = (packed_wino_dev || packed_wino4_dev) && (long long)B * hw >= wino_min;
+    // F(4x4, 3x3) (csrc/diinn_winograd4.hip): 1.78x fewer MFMAs again, in work items of 128 x 4 pixels x one output half.
+    // Both kernels run in rounds of one workgroup per CU, and measured over 192 .. 512-pixel maps one F(4x4) round
+    // costs 1.40 F(2x2) rounds of whole blocks (16 x 8 pixels x both halves; a round of halves 0.57; r04 measured 1.44, r05 1.40): the cheaper one
+    // by that count runs.  DIINN_ENC_WINO4_MIN = n >= 0 replaces the rule by "from n pixels on".
+    const bool wino4 = packed_wino4_dev && wino && diinn_rdn_wino4_applies(B, H, W);
+    if (wino && !wino4 && !packed_wino_dev) return DIINN_ERR_INVALID_ARG;   // this map runs F(2x2): its image is needed
+    // the F(4x4) kernel's split area: its arrival counters (the first 2 KiB) are zeroed here, once per forward, whatever a
+    // caller or an aborted launch left there (a memset node: capture-safe).  NOT the sticky status word behind them (word
+    // 1023 of the first 4 KiB, which the area's owner zeroes once when it allocates): a hand-off that gave up stays
+    // visible -- NaN features from then on -- until diinn_conv_wino4_ws_status has cleared it
+    const size_t w4ws_floats = w4ws ? diinn_conv_wino4_workspace_floats() : 0;
+    if (wino4 && w4ws) {
+        st = hip_status(hipMemsetAsync(w4ws, 0, DIINN_WINO4_COUNTER_BYTES, (hipStream_t)stream));
+        if (st) return st;
+    }
+    float* buf[2] = {planes, planes + (size_t)B * 576 * hw};                   // dense buffers [B,576,H,W]
+    float* gff_in = planes + (size_t)2 * B * 576 * hw;                           // [B,1024,H,W]
+    float* tmp = gff_in + (size_t)B * 1024 * hw;                                 // [B,64,H,W]
+    // split-bf16 3x3 layers (csrc/diinn_conv_x3.hip; optional): blocks of 32 x 8 pixels; they pay from about 0.8 blocks
+    // per CU on (measured per trunk, x3 vs Winograd: 160x160 7.8 vs 6.2 ms, 192x192 7.2 vs 9.3, 224x224 7.5 vs 11.4, 256x256 8.6 vs 11.8,
+    // 384x384 20.8 vs 28.0, 512x512 32.9 vs 46.5)
+    const bool x3 = packed_x3_dev && (long long)B * hw >= knob(diinn_knobs().enc_x3_min);
+    // small maps (csrc/diinn_conv_t16.hip): the direct sum in units of (1 .. 3 rows x 16 pixels, 16 outputs) where the split-K
+    // kernel's units leave compute units idle; the same weight image (per trunk: 48x48 1.95 -> 1.57 ms, 24x24 1.92 -> 0.88; profiles/r06_enc_trunk_small_maps.txt)
+    const bool t16 = !wino && !x3 && diinn_conv_t16_applies(B, H, W) != 0 &&
+                     ((((size_t)sfe1_dev) | ((size_t)planes) | ((size_t)packed_dev)) & 15) == 0;   // (its 16-byte LDS-DMA pieces; else the split-K kernel, as before)
+    RdnWeights wt{packed_dev, packed_wino_dev, packed_wino4_dev, packed_x3_dev, biases_dev};
+    auto conv = [&](const float* in, long long in_bs, int cin, int taps, const float* res, long long res_bs,
+                    float* o0, long long o0_bs, float* o1, long long o1_bs, int relu) {
+        const RdnWeights::Slices l = wt.next(cin, taps);
+        return (x3 && taps == 9 && !o1)
+            ? diinn_conv3x3_x3(stream, in, in_bs, cin, l.wx, l.bias, res, res_bs, o0, o0_bs, relu, B, H, W)
+            : (wino4 && taps == 9 && !o1)
+            ? diinn_conv_wino4_ws(stream, in, in_bs, cin, l.wu4, l.bias, res, res_bs, o0, o0_bs, relu, B, H, W, w4ws, w4ws_floats)
+            : (wino && taps == 9 && !o1)
+            ? diinn_conv_wino(stream, in, in_bs, cin, l.wu, l.bias, res, res_bs, o0, o0_bs, relu, B, H, W)
+            : (t16 && taps == 9 && !o1)
+            ? diinn_conv_t16(stream, in, in_bs, cin, l.w, l.bias, res, res_bs, o0, o0_bs, relu, B, H, W)
+            : (t16 && taps == 1 && cin <= 640)
+            ? diinn_conv1x1_t16(stream, in, in_bs, cin, l.w, l.bias, res, res_bs, o0, o0_bs, o1, o1_bs, relu, B, H, W)
+            : diinn_conv_ksplit(stream, in, in_bs, cin, taps, l.w, l.bias, res, res_bs, o0, o0_bs, o1, o1_bs, relu, B, H, W);
+    };
+    float* xs = tmp + (size_t)B * 64 * hw;                                       // x3 only: the block's channels in split format
+    const long long xs_bs16 = 144 * hw;                                          // 72 groups x (hi, lo) planes of 16-byte pixels
+    // SFENet2: 64 -> 64 into channels [0,64) of the first dense buffer (rdn.py:97); x3: also groups 0..7 of the split buffer
+    if (x3) {
+        const RdnWeights::Slices l = wt.next(64, 9);
+        st = diinn_conv3x3_x3_split(stream, sfe1_dev, 64 * hw, xs, xs_bs16, 0, 64, l.wx, l.bias, buf[0], 576 * hw, 0, B, H, W);
+    } else {
+        st = conv(sfe1_dev, 64 * hw, 64, 9, nullptr, 0, buf[0], 576 * hw, nullptr, 0, 0);
+    }
+    if (st) return st;
+    for (int d = 0; d < 16; ++d) {
+        float* cur = buf[d & 1];
+        float* nxt = buf[(d + 1) & 1];
+        if (x3) {
+            // inside the trunk the layers exchange their activations already split (csrc/diinn_conv_x3.hip): every dense conv
+            // reads ALL its inputs from the split buffer (two 16-byte copies per staged pixel instead of eight loads and a
+            // conversion, redone by each of the up to eight layers that read a channel) and appends its outputs to it --
+            // ONLY to it: the fp32 planes of the dense channels have no reader left, which halves the store burst at the end
+            // of every layer (at 256x256 the epilogue's 33 MB were 10 of a layer's 23-92 us); the fusion layer reads the
+            // split buffer whole and writes the next block's first 64 channels back in place, next to the planes
+            for (int c = 0; c < 8; ++c) {
+                const RdnWeights::Slices l = wt.next(64 * (c + 1), 9);
+                st = diinn_conv3x3_x3_split(stream, nullptr, 0, xs, xs_bs16, 8 * (c + 1), 64 * (c + 1), l.wx, l.bias,
+                                            nullptr, 0, 1, B, H, W);
+                if (st) return st;
+            }
+            const RdnWeights::Slices l = wt.next(576, 1);
+            st = diinn_conv1x1_x3_split(stream, xs, xs_bs16, 576, l.wx, l.bias, cur, 576 * hw, nxt, 576 * hw,
+                                        gff_in + (size_t)64 * d * hw, 1024 * hw, B, H, W);
+            if (st) return st;
+            continue;
+        }
+        for (int c = 0; c < 8; ++c) {                            // dense 3x3 convs: read channels [0, 64(c+1)), append 64 (rdn.py:15-17)
+            st = conv(cur, 576 * hw, 64 * (c + 1), 9, nullptr, 0, cur + (size_t)64 * (c + 1) * hw, 576 * hw, nullptr, 0, 1);
+            if (st) return st;
+        }
+        // LFF 1x1 576 -> 64 plus the block input (rdn.py:34): next block's input and the d-th slice of the global fusion input
+        st = conv(cur, 576 * hw, 576, 1, cur, 576 * hw, nxt, 576 * hw, gff_in + (size_t)64 * d * hw, 1024 * hw, 0);
+        if (st) return st;
+    }
+    // GFF: 1x1 1024 -> 64, then 3x3 64 -> 64, plus the shallow features (rdn.py:100-103)
+    st = conv(gff_in, 1024 * hw, 1024, 1, nullptr, 0, tmp, 64 * hw, nullptr, 0, 0);
+    if (st) return st;
+    return conv(tmp, 64 * hw, 64, 9, sfe1_dev, 64 * hw, out_dev, 64 * hw, nullptr, 0, 0);
 }
 
 }  // extern "C"

@@ -31,11 +31,10 @@
 extern "C" {
 #endif
 
-#define DIINN_ABI_VERSION 9
-/* What each ABI number added: INTEGRATION.md, "ABI history".  v9 (this header): ONE trunk entry point (diinn_rdn_forward_ex; the four
- * one-algorithm entry points are wrappers kept for this number only), the F(4x4) split hand-off fails loudly (sticky status word,
- * diinn_conv_wino4_ws_status), the training step's own kernels for the hoisted conv's weight gradient and its Winograd forward
- * (diinn_backward_cell_sum_ex, diinn_unfold_tiled, diinn_sum_parts, diinn_precompute_P_wpu), the small-map kernels (diinn_conv_t16, diinn_conv1x1_t16). */
+#define DIINN_ABI_VERSION 10
+/* What each ABI number added: INTEGRATION.md, "ABI history".  v10 (this header): the four one-algorithm trunk entry points of
+ * ABI <= 8 and their two workspace-size queries are removed; diinn_rdn_forward_ex(algo, ...) is the trunk's only entry point, its
+ * buffers sized by diinn_rdn_planes_floats and diinn_conv_wino4_workspace_floats. */
 
 /* status codes */
 #define DIINN_OK                 0
@@ -500,24 +499,6 @@ int    diinn_conv1x1_t16(void* stream, const float* in_dev, long long in_batch_s
                          const float* res_dev, long long res_batch_stride,
                          float* out0_dev, long long out0_batch_stride, float* out1_dev, long long out1_batch_stride,
                          int relu, int B, int H, int W);
-
-/* DEPRECATED, kept for this ABI number only: the one-algorithm trunk entry points of ABI <= 8 = diinn_rdn_forward_ex with algo
- * DIRECT / WINO / WINO4 / X3 and ONE workspace laid out [F(4x4) split area][planes] (diinn_rdn_workspace_floats = the split
- * area + 2,240 floats per pixel; diinn_rdn_x3_workspace_floats: + 576 per pixel), any content: as before v9 these entry points zero
- * the area's 4 KiB of control words themselves at every forward (so they keep no sticky status: a hand-off that gives up is NaN in
- * that forward's output only). */
-size_t diinn_rdn_workspace_floats(int B, int H, int W);
-size_t diinn_rdn_x3_workspace_floats(int B, int H, int W);
-int    diinn_rdn_forward(void* stream, const float* sfe1_dev, const float* packed_dev, const float* biases_dev,
-                         float* workspace_dev, float* out_dev, int B, int H, int W);
-int    diinn_rdn_forward_wino(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                              const float* biases_dev, float* workspace_dev, float* out_dev, int B, int H, int W);
-int    diinn_rdn_forward_wino4(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                               const float* packed_wino4_dev, const float* biases_dev, float* workspace_dev, float* out_dev,
-                               int B, int H, int W);
-int    diinn_rdn_forward_x3(void* stream, const float* sfe1_dev, const float* packed_dev, const float* packed_wino_dev,
-                            const float* packed_x3_dev, const float* biases_dev, float* workspace_dev, float* out_dev,
-                            int B, int H, int W);
 
 /* Launch geometry of decode_kernel (the throughput kernel: workgroups of 16 x 8 pixels) for HR rows [y0, y1). */
 int diinn_decode_launch_info(int B, int Hu, int Wu, int y0, int y1,

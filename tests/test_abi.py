@@ -39,7 +39,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 
 
 def test_abi_version_and_status_strings(lib):
-    assert lib.diinn_abi_version() == 9
+    assert lib.diinn_abi_version() == 10
     assert lib.diinn_status_string(0) == b"ok"
     assert b"invalid" in lib.diinn_status_string(1)
 
@@ -309,7 +309,7 @@ def test_tile_entry_point_validates_ranges_and_strides(lib):
 
 
 def test_conv_wino4_entry_point_validates_its_arguments(lib):
-    """diinn_conv_wino4 / diinn_rdn_forward_wino4 (Winograd F(4x4,3x3) encoder layers): null pointers, channel counts that are
+    """diinn_conv_wino4 / diinn_rdn_forward_ex (Winograd F(4x4,3x3) encoder layers): null pointers, channel counts that are
     not multiples of 8, unaligned images and empty maps are refused before anything is launched (no GPU needed)."""
     import ctypes as C
     d = C.c_void_p(4096)                                         # never dereferenced: every call below fails validation
@@ -320,15 +320,10 @@ def test_conv_wino4_entry_point_validates_its_arguments(lib):
     assert conv(cin=12) == 2 and conv(cin=0) == 2
     assert conv(packed=C.c_void_p(4100)) == 1                    # the weight image is read with 16-byte loads
     assert conv(b=0) == 1 and conv(h=0) == 1
-    assert lib.diinn_rdn_forward_wino4(None, d, d, d, None, d, d, d, 1, 64, 64) == 1     # without the F(4x4) image
-    # the F(2x2) image may be NULL only where the map takes F(4x4): 128 x 128 runs F(2x2), so a NULL there is refused (before
-    # anything is launched)
-    assert lib.diinn_rdn_wino4_applies(1, 128, 128) == 0
-    assert lib.diinn_rdn_forward_wino4(None, d, d, None, d, d, d, d, 1, 128, 128) == 1
     assert lib.diinn_rdn_wino4_packed_floats() == lib.diinn_rdn_wino_packed_floats() // 16 * 36
     # the workspace form: too small / misaligned workspaces (validated before the launch)
     wsf = lib.diinn_conv_wino4_workspace_floats()
-    assert wsf == 1024 + 2 * (256 + 8) * 16384 and lib.diinn_rdn_workspace_floats(1, 8, 8) == wsf + 64 * 2240
+    assert wsf == 1024 + 2 * (256 + 8) * 16384
 
     def conv_ws(ws=d, floats=wsf, cin=64):
         return lib.diinn_conv_wino4_ws(None, d, cin * 64 * 64, cin, d, d, None, 0, d, 64 * 64 * 64, 1, 1, 64, 64, ws, floats)
@@ -344,15 +339,38 @@ def test_conv_wino4_entry_point_validates_its_arguments(lib):
         assert ex(algo, planes=None) == 1 and ex(algo, planes=C.c_void_p(4100)) == 1 and ex(algo, area=C.c_void_p(4100)) == 1
         assert ex(algo, b=0) == 1 and ex(algo, h=0) == 1
     assert ex("wino", wino=None) == 1 and ex("wino4", wino4=None) == 1 and ex("x3", x3=None) == 1 and ex("x3", wino=None) == 1
-    assert ex("wino4", wino=None, h=128, w=128) == 1             # 128 x 128 runs F(2x2): its image is needed (as the v8 wrapper)
+    # the F(2x2) image may be NULL only where the map takes F(4x4): 128 x 128 runs F(2x2), so a NULL there is refused (before
+    # anything is launched)
+    assert lib.diinn_rdn_wino4_applies(1, 128, 128) == 0
+    assert ex("wino4", wino=None, h=128, w=128) == 1
     assert lib.diinn_rdn_forward_ex(None, 5, d, d, d, d, d, d, d, d, d, 1, 64, 64) == 1 and \
         lib.diinn_rdn_forward_ex(None, -1, d, d, d, d, d, d, d, d, d, 1, 64, 64) == 1
     assert lib.diinn_rdn_planes_floats(A["wino4"], 1, 8, 8) == 64 * 2240 and lib.diinn_rdn_planes_floats(A["x3"], 2, 8, 8) == 128 * 2816
+    assert lib.diinn_rdn_planes_floats(A["x3"], 1, 8, 8) == 64 * 2816
     assert lib.diinn_rdn_planes_floats(7, 1, 8, 8) == 0 and lib.diinn_rdn_planes_floats(0, 0, 8, 8) == 0
-    assert lib.diinn_rdn_x3_workspace_floats(1, 8, 8) == wsf + 64 * 2816   # the deprecated wrappers' single workspace
     st = C.c_int(0)
     assert lib.diinn_conv_wino4_ws_status(None, None, 0, C.byref(st)) == 1 and lib.diinn_conv_wino4_ws_status(None, d, 0, None) == 1
     info = (C.c_int * 4)()
     assert lib.diinn_decode_kernel_info(1, 96, 96, 0, 96, 0, 96, 0, info) == 0 and info[0] in (1, 3)
     assert lib.diinn_decode_kernel_info(1, 96, 96, 0, 97, 0, 96, 0, info) == 1 and lib.diinn_decode_kernel_info(1, 96, 96, 0, 96, 0, 96, 9, info) == 2
     assert lib.diinn_decode_kernel_info(1, 1024, 1024, 0, 1024, 0, 1024, 0, info) == 0 and list(info) == [1, 64, 128, 1]
+
+
+def test_trunk_weight_image_sizes_follow_the_module_layers(lib):
+    """The C++ side's one list of the trunk's 147 layers sizes every weight image; the module's _trunk_layers() (the state-dict
+    side, what the packers walk) must give the same sums: 64 Cin taps for the split-K image, 16 / 36 / 9 floats per (output,
+    input) pair of the 130 3x3 layers for the F(2x2) / F(4x4) / split-bf16 images, plus 64 x 576 per local fusion for the last."""
+    import diinn_amd.modules as M
+    sizes = (lib.diinn_rdn_packed_floats(), lib.diinn_rdn_wino_packed_floats(), lib.diinn_rdn_wino4_packed_floats(),
+             lib.diinn_rdn_x3_packed_floats())
+    assert sizes == (21_962_752, 37_879_808, 85_229_568, 21_897_216)
+    enc = M.make_rdn()
+    layers = enc._trunk_layers()
+    assert len(layers) == 147
+    assert all(l.weight.shape[0] == 64 for l in layers)
+    pairs3 = sum(64 * l.weight.shape[1] for l in layers if l.kernel_size == (3, 3))
+    assert sum(1 for l in layers if l.kernel_size == (3, 3)) == 130
+    assert sum(l.weight.numel() for l in layers) == sizes[0]
+    assert 16 * pairs3 == sizes[1] and 36 * pairs3 == sizes[2]
+    assert 9 * pairs3 + 64 * 576 * len(enc.RDBs) == sizes[3]
+    assert all(rdb.LFF.weight.shape == (64, 576, 1, 1) for rdb in enc.RDBs)

@@ -364,11 +364,10 @@ def test_rdn_handoff_status_is_sticky_across_forwards(knobs):
 
 
 @pytest.mark.gpu
-def test_deprecated_trunk_entry_points_take_an_uninitialised_workspace():
-    """The one-algorithm entry points of ABI <= 8 (wrappers of diinn_rdn_forward_ex since v9) promised to zero the split area's
-    control words themselves: a workspace full of garbage (every word 0xFFFFFFFF: a set status word, full counters) must give the
-    features of the module's own forward, bit for bit, on a map whose F(4x4) layers split their last round; likewise the F(2x2)
-    and direct wrappers."""
+def test_trunk_entry_point_takes_uninitialised_buffers():
+    """diinn_rdn_forward_ex with planes and a split area full of garbage (every word 0xFFFFFFFF: full arrival counters, slabs),
+    the area's status word zeroed as its owner does once: the features of the module's own forward, bit for bit, with the
+    algorithm that forward takes -- F(4x4) on a map whose last round splits, F(2x2), the direct sum, and split bf16."""
     import ctypes as C
     import diinn_amd._native as N
     import diinn_amd.modules as M
@@ -378,23 +377,30 @@ def test_deprecated_trunk_entry_points_take_an_uninitialised_workspace():
     enc = M.make_rdn().to(dev).eval()
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for (b, h, w) in [(1, 200, 180), (1, 100, 120), (1, 40, 44)]:
+    assert lib.diinn_rdn_wino4_applies(1, 200, 180) == 1 and lib.diinn_rdn_wino4_applies(1, 100, 120) == 0
+    for (b, h, w, algo) in [(1, 200, 180, N.RDN_ALGO_WINO4), (1, 100, 120, N.RDN_ALGO_WINO), (1, 40, 44, N.RDN_ALGO_DIRECT),
+                            (1, 256, 256, N.RDN_ALGO_X3)]:
         x = torch.rand(b, 3, h, w, device=dev)
+        enc.hip_split_bf16 = algo == N.RDN_ALGO_X3
         with torch.no_grad():
             want = enc(x)
             sfe1 = enc._sfe1_hip(x)
+        enc.hip_split_bf16 = False
         packed, biases = enc._hip_packed(dev)
-        ws = torch.full((lib.diinn_rdn_workspace_floats(b, h, w),), float("nan"), device=dev)
-        ws.view(torch.int32).fill_(-1)
-        out = torch.empty_like(want)
-        if lib.diinn_rdn_wino4_applies(b, h, w):
-            st = lib.diinn_rdn_forward_wino4(stream, ptr(sfe1), ptr(packed), None, ptr(enc._hip_packed_wino4(dev)), ptr(biases), ptr(ws), ptr(out), b, h, w)
-        elif b * h * w >= 8192:
-            st = lib.diinn_rdn_forward_wino(stream, ptr(sfe1), ptr(packed), ptr(enc._hip_packed_wino(dev)), ptr(biases), ptr(ws), ptr(out), b, h, w)
-        else:
-            st = lib.diinn_rdn_forward(stream, ptr(sfe1), ptr(packed), ptr(biases), ptr(ws), ptr(out), b, h, w)
+        wino = enc._hip_packed_wino(dev) if algo in (N.RDN_ALGO_WINO, N.RDN_ALGO_X3) else None
+        wino4 = enc._hip_packed_wino4(dev) if algo == N.RDN_ALGO_WINO4 else None
+        x3 = enc._hip_packed_x3(dev) if algo == N.RDN_ALGO_X3 else None
+        planes = torch.empty(lib.diinn_rdn_planes_floats(algo, b, h, w), dtype=torch.float32, device=dev)
+        area = torch.empty(lib.diinn_conv_wino4_workspace_floats(), dtype=torch.float32, device=dev)
+        planes.view(torch.int32).fill_(-1)
+        area.view(torch.int32).fill_(-1)
+        area[512:1024].zero_()                                    # bytes [2048, 4096): the status word (word 1023)
+        out = torch.full_like(want, float("nan"))
+        st = lib.diinn_rdn_forward_ex(stream, algo, ptr(sfe1), ptr(packed), ptr(wino), ptr(wino4), ptr(x3), ptr(biases),
+                                      ptr(planes), ptr(area), ptr(out), b, h, w)
         assert st == 0
-        torch.cuda.synchronize()
+        status = C.c_int(1)
+        assert lib.diinn_conv_wino4_ws_status(stream, ptr(area), 0, C.byref(status)) == 0 and status.value == 0, (b, h, w)
         assert bool(torch.isfinite(out).all()) and torch.equal(out, want), (b, h, w)
     assert M.RDN.handoff_status(clear=False) == 0
 

@@ -184,7 +184,7 @@ def test_set_split_bf16_switches_both_modes():
 @pytest.mark.gpu
 def test_rdn_weight_images_are_built_on_demand():
     """the derived weight images of the encoder are built only where a kernel reads them -- a map that runs
-    F(4x4,3x3) layers never builds the F(2x2) image (diinn_rdn_forward_wino4 takes NULL for it), a split-K map builds
+    F(4x4,3x3) layers never builds the F(2x2) image (diinn_rdn_forward_ex takes NULL for it there), a split-K map builds
     neither -- and free_unused_images() drops them without changing a result."""
     import diinn_amd._native as N
     import diinn_amd.modules as M

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""RDN encoder forward: HIP trunk (conv_ksplit_kernel, C ABI diinn_rdn_forward) vs PyTorch-ROCm/MIOpen, eager and
+"""RDN encoder forward: HIP trunk (C ABI diinn_rdn_forward_ex) vs PyTorch-ROCm/MIOpen, eager and
 hipGraph-replayed, over input sizes -- locates the cross-over behind RDN.hip_trunk_max_pixels.
 usage: enc_trunk_time.py [SIZE ...]"""
 import os
