@@ -30,6 +30,10 @@
 
 constexpr int T16_WAVES = 8, T16_MAXR = 3;
 constexpr int T16_GROUP = 16;                                  // input channels per step / weight run
+// The kernels find a weight run's wave as r8 / runs = (r8 * inv_runs) >> 16, inv_runs = ceil(65536 / runs), runs = Cin / 64,
+// r8 < 8 runs (two runs of 8 per group of 16 channels, Cin / 16 groups): exact for runs <= 103, first wrong at runs = 104
+// (tests/test_encoder_trunk.py enumerates it).  The entry point stops well inside that (the trunk's widest layer: 576).
+constexpr int T16_MAX_CIN = 4096;
 constexpr int T16_STAGE = T16_GROUP * (32 * (T16_MAXR + 2) - 16);   // 2,304 floats = 9 KiB: the largest stage (3 rows)
 constexpr int T16_LDS_FLOATS = T16_WAVES * 2 * T16_STAGE;      // 147,456 bytes
 static_assert(T16_LDS_FLOATS * 4 <= 160 * 1024 && T16_WAVES * T16_MAXR * 4 * 64 <= T16_LDS_FLOATS, "LDS budget");
@@ -127,7 +131,7 @@ __device__ __forceinline__ void conv_t16_body(const ConvT16Params& p, float* __r
         // direct-sum image: lane (k = lane >> 4, m = lane & 15) takes output 16 quarter + m and, of the group's 16 channels,
         // the run of 8 number k >> 1 at h = k & 1 -- k-step e multiplies the group's channels 8 (k >> 1) + 2 e + (k & 1)
         const int runs = p.Cin / 64;
-        const unsigned inv_runs = p.inv_runs;                     // r / runs = (r * inv_runs) >> 16 for r < 128
+        const unsigned inv_runs = p.inv_runs;                     // r / runs = (r * inv_runs) >> 16 for r < 8 runs, Cin <= T16_MAX_CIN
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.Cin * (64 * 9 * 4), 0x00020000);
         const int wlane = (quarter >> 1) * (8 * 9 * runs * 1024) + ((lane >> 4) & 1) * 512 + (16 * (quarter & 1) + (lane & 15)) * 16;
         f32x4 wr[2][9];
@@ -249,6 +253,7 @@ __global__ __launch_bounds__(512, 2) void conv_t16_kernel(const ConvT16Params p)
 // the reduction through LDS, two destinations.  The split-K kernel's 1x1 form stages a chunk, multiplies, stages the next.
 constexpr int T16_1X1_MAXG = 5;                                // groups per wave: Cin <= 640
 static_assert(T16_1X1_MAXG * T16_GROUP * 48 <= 2 * T16_STAGE, "the 1x1 stages fit the wave's share of the LDS");
+static_assert(T16_1X1_MAXG * T16_WAVES * T16_GROUP <= T16_MAX_CIN && T16_MAX_CIN / 64 <= 103, "the run division is exact");
 
 template <int NR>
 __device__ __forceinline__ void conv1x1_t16_body(const ConvT16Params& p, float* __restrict__ lds, int quarter, int b, int y0, int x0) {
@@ -277,7 +282,7 @@ __device__ __forceinline__ void conv1x1_t16_body(const ConvT16Params& p, float* 
     if (my > 0) {
         float* __restrict__ ring = lds + wave * 2 * T16_STAGE;
         const int runs = p.Cin / 64;
-        const unsigned inv_runs = p.inv_runs;                     // r / runs = (r * inv_runs) >> 16 for r < 128
+        const unsigned inv_runs = p.inv_runs;                     // r / runs = (r * inv_runs) >> 16 for r < 8 runs, Cin <= T16_MAX_CIN
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.Cin * (64 * 4), 0x00020000);
         // the split-K kernel's 1x1 image: [half 2][wave 8][run Cin/64][h 2][i 32][4] (conv_t16_body's lane mapping, one tap)
         const int wlane = (quarter >> 1) * (8 * runs * 1024) + ((lane >> 4) & 1) * 512 + (16 * (quarter & 1) + (lane & 15)) * 16;
@@ -402,7 +407,7 @@ int diinn_conv_t16(void* stream, const float* in_dev, long long in_batch_stride,
     if (!in_dev || !packed_w_dev || !bias_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
-    if (Cin <= 0 || Cin % 64 || (W & 3)) return DIINN_ERR_UNSUPPORTED;
+    if (Cin <= 0 || Cin % 64 || Cin > T16_MAX_CIN || (W & 3)) return DIINN_ERR_UNSUPPORTED;
     if ((((size_t)in_dev) & 15) || (((size_t)packed_w_dev) & 15) || (in_batch_stride & 3)) return DIINN_ERR_INVALID_ARG;
     ConvT16Params p;
     const int slots = t16_plan((long long)B * ((W + 15) / 16), H, W, Cin, &p);

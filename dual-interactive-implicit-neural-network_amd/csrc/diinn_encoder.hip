@@ -729,7 +729,11 @@ int diinn_rdn_forward_ex(void* stream, int algo, const float* sfe1_dev, const fl
     // F(4x4, 3x3) (csrc/diinn_winograd4.hip): 1.78x fewer MFMAs again, in work items of 128 x 4 pixels x one output half.
     // Both kernels run in rounds of one workgroup per CU, and measured over 192 .. 512-pixel maps one F(4x4) round
     // costs 1.40 F(2x2) rounds of whole blocks (16 x 8 pixels x both halves; a round of halves 0.57; r04 measured 1.44, r05 1.40): the cheaper one
-    // by that count runs.  DIINN_ENC_WINO4_MIN = n >= 0 replaces the rule by "from n pixels on".
+    // by that count runs.  A partly filled last F(4x4) round is split and costs 0.27 + 0.86 r of one, but never less than 0.49 where
+    // it is the map's only round (w4_rounds): maps that F(2x2) does in one round of halves -- 92 .. 96-pixel squares, 64 x 128,
+    // 104 x 80 -- stay on F(2x2) (3.6 against 4.15 ms), maps just above that (100 x 148, 153 x 102: 6.2 against 4.5 .. 5.0) take
+    // F(4x4).  tests/test_encoder_trunk.py replays every measured A/B table against the rule.
+    // DIINN_ENC_WINO4_MIN = n >= 0 replaces the rule by "from n pixels on".
     const bool wino4 = packed_wino4_dev && wino && diinn_rdn_wino4_applies(B, H, W);
     if (wino && !wino4 && !packed_wino_dev) return DIINN_ERR_INVALID_ARG;   // this map runs F(2x2): its image is needed
     // the F(4x4) kernel's split area: its arrival counters (the first 2 KiB) are zeroed here, once per forward, whatever a

@@ -602,14 +602,19 @@ static W4Plan w4_plan(long long total, int n, int ncu, bool have_ws) {
 
 // the kernel's time for a map of `total` work items over the whole trunk, in rounds of whole items: the whole rounds + what a
 // last round filled to r = R / N costs once it is split, 0.27 + 0.86 r of a round (measured on 112 .. 208-pixel maps:
-// profiles/r05_enc_trunk_times.txt); diinn_rdn_wino4_applies compares it with the F(2x2) kernel's rounds
+// profiles/r05_enc_trunk_times.txt); diinn_rdn_wino4_applies compares it with the F(2x2) kernel's rounds.  That line was fitted
+// from r = 0.2 up and does not reach down: a map that is ONE thinly filled round costs 0.49 of a round however few its items
+// (profiles/enc_wino4_ab_small_maps.txt: 4.13 .. 4.22 ms per trunk at 32 .. 44 items = r 0.12 .. 0.17, of the 8.6 ms a 256 x 256 map's one whole
+// round takes in profiles/r05_enc_trunk_times.txt -- a ratio across two sessions, not one measurement; the
+// line says 0.38 .. 0.42 and sent 92 .. 96-pixel squares, 64 x 128, 72 x 120 to F(4x4), 15 % behind F(2x2)'s 3.6 ms)
 __attribute__((visibility("hidden"))) double w4_rounds(long long total, bool have_ws) {
     const int ncu = w4_cus();
     if (ncu < 2) return (double)total;
     const long long whole = total / ncu, R = total % ncu;
     if (R == 0) return (double)whole;
     const W4Plan pl = w4_plan(total, 36, ncu, have_ws);          // (would the trunk's average layer be split at all?)
-    const double last = pl.items ? 0.27 + 0.86 * (double)R / ncu : 1.0;
+    double last = pl.items ? 0.27 + 0.86 * (double)R / ncu : 1.0;
+    if (whole == 0 && last < 0.49) last = 0.49;
     return (double)whole + (last < 1.0 ? last : 1.0);
 }
 

@@ -476,8 +476,9 @@ size_t diinn_rdn_x3_packed_floats(void);
  * workgroup owns one quarter and 1 .. 3 consecutive rows of a strip and streams its quarter's weights once -- so that all
  * compute units work where the split-K kernel's (32 pixels x 32 outputs) units number fewer than the compute units.
  * diinn_conv_t16: addressing, epilogue and packed_w_dev as diinn_conv_ksplit with taps = 9 (it reads the SAME image) and one
- *   destination; W % 4 == 0, Cin % 64 == 0, and a map whose strips' rows can be dealt at most 3 to a workgroup
- *   (DIINN_ERR_UNSUPPORTED otherwise).  diinn_conv_t16_applies: 1 if the trunk gives this map's 3x3 layers to this kernel on
+ *   destination; W % 4 == 0, Cin % 64 == 0, Cin <= 4096 (the kernel's division by Cin / 64 is a 16-bit multiplier, exact up to
+ *   Cin = 6592), and a map whose strips' rows can be dealt at most 3 to a workgroup (DIINN_ERR_UNSUPPORTED otherwise, before
+ *   any device call).  diinn_conv_t16_applies: 1 if the trunk gives this map's 3x3 layers to this kernel on
  *   the current device (a map below the Winograd kernels', with fewer split-K units than compute units; DIINN_ENC_NO_T16 = 1:
  *   never).  Results differ from diinn_conv_ksplit's by the order of the fp32 sum only. */
 int    diinn_conv_t16(void* stream, const float* in_dev, long long in_batch_stride, int Cin,
