@@ -328,13 +328,13 @@ int diinn_metasr_decode(void* stream, const float* feat_dev, const float* packed
     if (st) return st;
     if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
     if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    int gx, gy, gz, blk;
+    diinn_decode_launch_info(B, Hu, Wu, 0, Hu, &gx, &gy, &gz, &blk);
+    if (gy > 65535 || gz > 65535) return DIINN_ERR_TOO_LARGE;   // every argument is judged before the first launch
     UnfoldParams u{feat_dev, workspace_dev, B, H, W};
     hipLaunchKernelGGL(unfold_cells_kernel, dim3(W, H, B), dim3(192), 0, (hipStream_t)stream, u);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_status(e);
-    int gx, gy, gz, blk;
-    diinn_decode_launch_info(B, Hu, Wu, 0, Hu, &gx, &gy, &gz, &blk);
-    if (gy > 65535 || gz > 65535) return DIINN_ERR_TOO_LARGE;
     MetaParams p;
     p.U = workspace_dev; p.Wt = packed_dev; p.out = out_dev;
     p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu;
@@ -346,14 +346,16 @@ int diinn_metasr_decode(void* stream, const float* feat_dev, const float* packed
 
 int diinn_liif_decode(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
                       float* out_dev, int B, int H, int W, int Hu, int Wu) {
-    if (!out_dev || !workspace_dev) return DIINN_ERR_INVALID_ARG;
-    int st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, 0, H, 4);   // first 256 channels of P
+    if (!feat_dev || !packed_dev || !out_dev || !workspace_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
     if (st) return st;
     if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
     if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
     int gx, gy, gz, blk;
     diinn_decode_launch_info(B, Hu, Wu, 0, Hu, &gx, &gy, &gz, &blk);
-    if (gy > 65535 || gz > 65535) return DIINN_ERR_TOO_LARGE;
+    if (gy > 65535 || gz > 65535) return DIINN_ERR_TOO_LARGE;   // every argument is judged before the first launch
+    st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, 0, H, 4);   // first 256 channels of P
+    if (st) return st;
     LiifParams p;
     p.P = workspace_dev; p.Wt = packed_dev; p.out = out_dev;
     p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu;

@@ -222,12 +222,15 @@ def decode_window(feat_win: torch.Tensor, feat_row0: int, full_h: int, packed: t
 
 def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: torch.Tensor, size: Sequence[int],
                 rows: Tuple[int, int], cols: Tuple[int, int], out: torch.Tensor,
-                sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32") -> torch.Tensor:
+                sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", mode: int = 3) -> torch.Tensor:
     """Decode the HR tile rows x cols = [y0,y1) x [x0,x1) from a P window (``diinn_precompute_P_win``'s output: LR rows
     [p_row0, p_row0 + p_rows) of the [B,H,W,1024] image, ``shape`` = (B, H, W) of the full map) INTO ``out``, any fp32
     view of shape [B,3,y1-y0,x1-x0] with unit stride along x -- a tensor of its own or a window of a larger canvas;
     nothing else of the canvas is written.  Bit-identical to the same pixels of ``decode_features``.  The reference's
-    analogue is ``batched_step``'s column strips (diinn.py:149-160).  C ABI: ``diinn_decode_tile_win``."""
+    analogue is ``batched_step``'s column strips (diinn.py:149-160).  C ABI: ``diinn_decode_tile_win``.
+
+    ``mode`` 1 / 2 (fp32 only): ``p_win`` must already hold the per-cell modulation chain in slots 1..3 of the rows the
+    tile reads (``diinn_cell_chain`` after ``diinn_precompute_P_win``)."""
     lib = _native.load()
     _require_cuda(p_win, "p_win")
     _require_cuda(packed, "packed weights")
@@ -242,12 +245,17 @@ def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: 
     if p_win.dtype != torch.float32 or not p_win.is_contiguous() or p_win.numel() % (b * w * P_CHANNELS):
         raise ValueError("p_win must be a contiguous fp32 buffer of B * rows * W * 1024 floats")
     p_rows = p_win.numel() // (b * w * P_CHANNELS)
+    if mode not in (1, 2, 3):
+        raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-3")
+    if mode != 3 and compute != "f32":
+        raise ValueError("modes 1 and 2 run in fp32 only")
+    comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
     with torch.cuda.device(p_win.device):
         stream = torch.cuda.current_stream().cuda_stream
         st = lib.diinn_decode_tile_win(C.c_void_p(stream), C.c_void_p(p_win.data_ptr()), int(p_row0), p_rows,
                                        C.c_void_p(packed.data_ptr()), C.c_void_p(out.data_ptr()),
                                        out.stride(2), out.stride(1), out.stride(0), b, h, w, hu, wu, y0, y1, x0, x1,
-                                       int(sin_mode), _native.COMPUTE[compute])
+                                       int(sin_mode), comp)
     _native.check(st, "diinn_decode_tile_win")
     return out
 
@@ -304,6 +312,9 @@ def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequenc
     b, _, h, w = feat.shape
     if out is None:
         out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
+    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != feat.device:
+        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
     need = lib.diinn_workspace_bytes(b, h, w)
     if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
@@ -360,6 +371,9 @@ def metasr_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Seque
     b, _, h, w = feat.shape
     if out is None:
         out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
+    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != feat.device:
+        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
     need = lib.diinn_metasr_workspace_bytes(b, h, w)
     if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)

@@ -156,9 +156,13 @@ def make_syn_inp(b: int, h: int, w: int, hu: int, wu: int) -> Tuple[torch.Tensor
 
 
 @torch.no_grad()
-def decode_reference_form_f64(sd, feat, size: Sequence[int]) -> torch.Tensor:
+def decode_reference_form_f64(sd, feat, size: Sequence[int], mode: int = 3, ratio_f64: bool = False) -> torch.Tensor:
     """The same mathematics in float64 (coordinates and indices stay the reference's fp32 tables):
-    a ground truth against which the fp32 reference and the fp32 HIP path can both be measured."""
+    a ground truth against which the fp32 reference and the fp32 HIP path can both be measured.
+    ``mode`` 1 / 2: the ablation variants (diinn.py:116-131), with weights of that mode's shapes.
+    ``ratio_f64=True`` keeps the scale ratio a double, as the reference module itself does once it has been cast with
+    ``.double()`` (``x.new_tensor`` takes x's dtype, diinn.py:166, while the coordinates stay ``.float()``, :98-103):
+    what the d64 fixtures were captured with.  The two differ by the fp32 rounding of one input, <= 6e-8 relative."""
     sd64 = {k: _as_t(v).double() for k, v in sd.items()}
     feat = _as_t(feat).double()
     b, c, h, w = feat.shape
@@ -166,7 +170,10 @@ def decode_reference_form_f64(sd, feat, size: Sequence[int]) -> torch.Tensor:
     syn, idx_h, idx_w = make_syn_inp(b, h, w, hu, wu)
     u = unfold3x3(feat)
     x = u[:, :, torch.from_numpy(idx_h.astype(np.int64))][:, :, :, torch.from_numpy(idx_w.astype(np.int64))]
-    return _step_mode3(sd64, x, syn.double())
+    syn = syn.double()
+    if ratio_f64:
+        syn[:, 2] = (h * w) / (hu * wu)
+    return _step_mode3(sd64, x, syn, mode)
 
 
 @torch.no_grad()

@@ -47,11 +47,16 @@ def liif_rel_cell(n_in: int, n_out: int) -> np.float32:
 
 
 @torch.no_grad()
-def liif_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[int]) -> torch.Tensor:
+def liif_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[int],
+                              dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """[B,3,Hu,Wu]: gather the unfolded features of the 4 shifted nearest cells, run the 580->256^4->3 ReLU
-    MLP on each, blend by the diagonally swapped areas (liif.py:59-127)."""
-    w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in sd.items()}
-    feat = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.float32))
+    MLP on each, blend by the diagonally swapped areas (liif.py:59-127).
+
+    ``dtype=torch.float64``: the index and coordinate tables stay the reference's fp32 tables (they are inputs of the
+    arithmetic, as in diinn_oracle.decode_reference_form_f64); the MLP, the areas and the blend run in float64 -- the
+    truth the fp32 reference and the fp32 kernel are both measured against (the reference itself cannot run in double)."""
+    w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dtype) for k, v in sd.items()}
+    feat = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.float32)).to(dtype)
     b, c, h, wd = feat.shape
     hu, wu = int(size[0]), int(size[1])
     u = unfold3x3(feat)                                           # [B,576,H,W]
@@ -63,7 +68,7 @@ def liif_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[in
             iw, rw = liif_axis_tables(wd, wu, vy)
             q = u[:, :, torch.from_numpy(ih.astype(np.int64))][:, :, :, torch.from_numpy(iw.astype(np.int64))]
             q = q.permute(0, 2, 3, 1)                             # [B,Hu,Wu,576]
-            rel = torch.empty((b, hu, wu, 4))
+            rel = torch.empty((b, hu, wu, 4), dtype=dtype)
             rel[..., 0] = torch.from_numpy(rh)[None, :, None]
             rel[..., 1] = torch.from_numpy(rw)[None, None, :]
             rel[..., 2] = cell_h

@@ -45,9 +45,12 @@ def metasr_r_rev(h: int, hu: int) -> np.float32:
 
 
 @torch.no_grad()
-def metasr_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[int]) -> torch.Tensor:
-    w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in sd.items()}
-    feat = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.float32))
+def metasr_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[int],
+                                dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``dtype=torch.float64``: the fp32 index / coordinate tables are kept (inputs of the arithmetic); the
+    meta-network and the contraction with the unfolded features run in float64."""
+    w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dtype) for k, v in sd.items()}
+    feat = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.float32)).to(dtype)
     b, c, h, wd = feat.shape
     hu, wu = int(size[0]), int(size[1])
     ih, rh = metasr_axis_tables(h, hu)
@@ -55,7 +58,7 @@ def metasr_query_reference_form(sd: Dict[str, np.ndarray], feat, size: Sequence[
     u = unfold3x3(feat)
     q = u[:, :, torch.from_numpy(ih.astype(np.int64))][:, :, :, torch.from_numpy(iw.astype(np.int64))]
     q = q.permute(0, 2, 3, 1).reshape(-1, 1, 576)
-    inp = torch.empty((b, hu, wu, 3))
+    inp = torch.empty((b, hu, wu, 3), dtype=dtype)
     inp[..., 0] = torch.from_numpy(rh)[None, :, None]
     inp[..., 1] = torch.from_numpy(rw)[None, None, :]
     inp[..., 2] = float(metasr_r_rev(h, hu))

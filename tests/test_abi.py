@@ -374,3 +374,38 @@ def test_trunk_weight_image_sizes_follow_the_module_layers(lib):
     assert 16 * pairs3 == sizes[1] and 36 * pairs3 == sizes[2]
     assert 9 * pairs3 + 64 * 576 * len(enc.RDBs) == sizes[3]
     assert all(rdb.LFF.weight.shape == (64, 576, 1, 1) for rdb in enc.RDBs)
+
+
+def test_cell_chain_validates_its_arguments(lib):
+    """diinn_cell_chain (decoder modes 1 and 2): NULL pointers and LR row ranges outside the map are refused before any
+    device call, so this runs without a GPU (the fake pointers are never touched)."""
+    import diinn_amd._native as N
+    fake = C.c_void_p(4096)
+
+    def chain(P=fake, packed=fake, b=1, h=16, w=16, r0=0, r1=16):
+        return lib.diinn_cell_chain(None, P, packed, b, h, w, r0, r1)
+    assert chain(P=None) == N.ERR_INVALID_ARG and chain(packed=None) == N.ERR_INVALID_ARG
+    assert chain(r0=-1) == N.ERR_INVALID_ARG
+    assert chain(r1=17) == N.ERR_INVALID_ARG
+    assert chain(r0=5, r1=5) == N.ERR_INVALID_ARG and chain(r0=9, r1=3) == N.ERR_INVALID_ARG
+    assert chain(b=0) == N.ERR_INVALID_ARG and chain(h=0) == N.ERR_INVALID_ARG and chain(w=0) == N.ERR_INVALID_ARG
+
+
+def test_baseline_decoders_validate_every_argument_before_the_first_launch(lib):
+    """diinn_liif_decode / diinn_metasr_decode enqueue two kernels each; every argument -- the HR size and the grid limits
+    included -- is judged before the first of them, so a bad call leaves the workspace untouched.  On a machine without a
+    GPU a launch would answer DIINN_ERR_HIP: INVALID_ARG here means nothing was launched."""
+    import diinn_amd._native as N
+    fake = C.c_void_p(4096)                                      # never dereferenced
+    for fn in (lib.diinn_liif_decode, lib.diinn_metasr_decode):
+        assert fn(None, fake, fake, fake, fake, 1, 8, 8, 0, 16) == N.ERR_INVALID_ARG
+        assert fn(None, fake, fake, fake, fake, 1, 8, 8, 16, 0) == N.ERR_INVALID_ARG
+        assert fn(None, fake, fake, fake, fake, 1, 8, 8, -3, 16) == N.ERR_INVALID_ARG
+        assert fn(None, fake, fake, fake, fake, 0, 8, 8, 16, 16) == N.ERR_INVALID_ARG
+        for null in range(4):
+            ptrs = [fake] * 4
+            ptrs[null] = None
+            assert fn(None, *ptrs, 1, 8, 8, 16, 16) == N.ERR_INVALID_ARG
+        # HR rows beyond the grid's y limit (65,535 blocks of 8 rows), and an image of >= 2e9 pixels
+        assert fn(None, fake, fake, fake, fake, 1, 8, 8, 8 * 65535 + 1, 16) == N.ERR_TOO_LARGE
+        assert fn(None, fake, fake, fake, fake, 1, 8, 8, 50000, 50000) == N.ERR_TOO_LARGE

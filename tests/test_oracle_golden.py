@@ -1,7 +1,10 @@
 """CPU: the oracle (oracle/diinn_oracle.py) against the fixtures captured from the REAL
 reference decoder (tests/golden/make_golden.py imports /root/reference in the build container).
 This is what pins the oracle; the GPU tests then compare the HIP path with it."""
+import os
+
 import numpy as np
+import pytest
 import torch
 
 import diinn_amd.synth as synth
@@ -143,3 +146,66 @@ def test_oracle_modes_1_and_2_match_reference(golden):
         ref = golden[f"mode{mode}/out_24x20_79x66"]
         got = orc.decode_reference_form(sd, feat, (79, 66), 30000, mode=mode).numpy()
         assert float(np.abs(got - ref).max()) <= 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# round 8: modes 1 and 2 at edge shapes (tests/golden/make_golden_r8.py), fp32 and float64
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def gold8():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "diinn_golden_r8.npz"))
+
+
+def _r8_cases(g):
+    for k in g.files:
+        if k.startswith("meta/"):
+            b, h, w, hu, wu, gain = g[k]
+            yield k[5:], int(b), int(h), int(w), int(hu), int(wu), float(gain)
+
+
+def test_r8_fixture_holds_every_case(gold8):
+    cases = list(_r8_cases(gold8))
+    assert [c[1:] for c in cases] == [(1, 1, 1, 5, 7, 1.0), (1, 1, 9, 4, 30, 1.0), (3, 7, 5, 23, 18, 1.0), (2, 12, 10, 31, 27, 2.0),
+                                      (1, 13, 3, 40, 9, 1.0), (1, 16, 12, 8, 6, 1.0), (1, 4, 3, 110, 9, 1.0), (2, 17, 33, 40, 100, 3.0)]
+    for name, b, h, w, hu, wu, gain in cases:
+        for mode in (1, 2):
+            assert gold8[f"out/mode{mode}/{name}"].shape == gold8[f"d64/mode{mode}/{name}"].shape == (b, 3, hu, wu)
+            assert gold8[f"out/mode{mode}/{name}"].dtype == gold8[f"d64/mode{mode}/{name}"].dtype == np.float32
+    for tag in ("liif", "metasr"):
+        assert sorted(k.split("/")[2] for k in gold8.files if k.startswith(f"out/{tag}/")) == sorted(c[0] for c in cases[:6])
+
+
+def test_oracle_modes_1_and_2_match_r8_reference_outputs(gold8):
+    """decode_reference_form(mode=1|2) on a 1x1 map, 1-row and 3-column maps, batches, down-scaling, the ATen small-output
+    index path (4x3 -> 110x9) and the gain-3 stress case (bit-equal here; 1e-6 for other hosts)."""
+    for mode in (1, 2):
+        for name, b, h, w, hu, wu, gain in _r8_cases(gold8):
+            sd = synth.decoder_state_dict(123, gain, mode=mode)
+            ref = gold8[f"out/mode{mode}/{name}"]
+            got = orc.decode_reference_form(sd, synth.encoder_features(123, b, h, w), (hu, wu), None, mode=mode).numpy()
+            assert got.shape == ref.shape
+            assert float(np.abs(got - ref).max()) <= 1e-6 * max(1.0, float(np.abs(ref).max())), (mode, name)
+
+
+def test_float64_oracle_modes_1_and_2_meet_the_float64_reference(gold8):
+    """decode_reference_form_f64(mode=, ratio_f64=True) against ref64 = out + d64 at 1e-9 x max(1, |ref|).  Measured:
+    <= 3.0e-13 relative (the gain-3 case; what is left is d64's own storage in fp32).  ratio_f64: the reference module
+    cast with .double() keeps its coordinates fp32 but builds the scale ratio as a double (diinn.py:166); with the fp32
+    ratio every fp32 path uses, the float64 oracle sits up to 3.6e-8 relative from ref64 (gain 3; <= 1e-13 at gain 1) --
+    the effect of rounding that one input, 250 times below the gain-3 noise of 9e-5."""
+    worst32 = 0.0
+    for mode in (1, 2):
+        for name, b, h, w, hu, wu, gain in _r8_cases(gold8):
+            sd = synth.decoder_state_dict(123, gain, mode=mode)
+            feat = synth.encoder_features(123, b, h, w)
+            ref32 = gold8[f"out/mode{mode}/{name}"]
+            ref64 = ref32.astype(np.float64) + gold8[f"d64/mode{mode}/{name}"].astype(np.float64)
+            scale = max(1.0, float(np.abs(ref32).max()))
+            got = orc.decode_reference_form_f64(sd, feat, (hu, wu), mode=mode, ratio_f64=True).numpy()
+            assert got.dtype == np.float64
+            assert float(np.abs(got - ref64).max()) <= 1e-9 * scale, (mode, name)
+            got32r = orc.decode_reference_form_f64(sd, feat, (hu, wu), mode=mode).numpy()
+            worst32 = max(worst32, float(np.abs(got32r - ref64).max()) / scale)
+            # the reference's own fp32 noise dwarfs the rounding of the ratio
+            assert float(np.abs(got32r - ref64).max()) <= 0.01 * max(float(np.abs(gold8[f"d64/mode{mode}/{name}"]).max()), 1e-9), (mode, name)
+    assert worst32 <= 1e-7
