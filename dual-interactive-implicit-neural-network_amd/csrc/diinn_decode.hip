@@ -14,7 +14,9 @@
 //                         B-operand layout of the next (diinn_layout.h), so activations
 //                         never touch LDS or HBM.  Weights stream from the packed image.
 //                         <KPART=false>: decoder modes 1/2 (with cell_chain_kernel);
-//                         <SAVE>: training forward, also writes k_i, s_i as tiled planes
+//                         <SAVE>: training forward, also writes k_i, s_i as tiled planes;
+//                         <HEAD3>: decoder mode 4, the head is the 27 per-pixel tap values of the 3x3 conv
+//   head3x3_reflect_kernel : decoder mode 4, the reflect-padded 9-point gather over the tap buffer
 //   decode_bf16_kernel, decode_bf16x2_kernel : bf16 operands in layers 1..3 (optional paths)
 //   bwd_layer_kernel (+ bwd_head_kernel), plane_gemm_lds_kernel, plane_rowdot_kernel, cell_sum_kernel :
 //                         backward pass of the decoder (training)
@@ -31,13 +33,21 @@
 struct TagCoopF { static constexpr bool value = false; };
 struct TagCoopT { static constexpr bool value = true; };
 
-template <int SIN_MODE, bool KPART = true, bool SAVE = false>
+// HEAD3 = true (decoder mode 4, diinn.py:89-90,140-147: last_layer = Conv2d(256, 3, 3, padding=1, 'reflect') over the HR grid): a
+// 3x3 convolution of the 256-channel image q3 is a 1x1 map to 27 numbers per pixel, T[k][c] = sum_ch Lw[c][ch][ky][kx] q3[ch]
+// (k = 3 ky + kx), followed by a 9-point gather (head3x3_reflect_kernel).  The first half depends on the pixel alone, so the layers
+// run exactly as in mode 3 and the head forms 27 dot products in place of 3, in the same lane-half split and the same (m, g, e)
+// order; they go to the TAP BUFFER p.out = [B][p.Orows rows from p.Orow0][Wu][TAP_STRIDE] (k major, c minor, one pad float: seven
+// 16-byte stores per pixel).  The head table (27 x 256 floats, natural channel order) sits in LDS behind the Q0 rows of `tab`.
+// (TAPS, TAP_STRIDE and the head image's layout: diinn_layout.h)
+template <int SIN_MODE, bool KPART = true, bool SAVE = false, bool HEAD3 = false>
 __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
+    static_assert(!(HEAD3 && SAVE), "mode 4 is inference only");
     // The small tables of layer 0 and of the head go through LDS: a vector-memory instruction blocks its wave for
     // ~60 cycles (stamps), and a wave reading them straight from the packed image issued 128 + 96
     // of those per tile.  Rows: Q0h, Q0w, t = fma(Q0r, ratio, bQ0) (the pixel-independent part of the sine
     // argument, the same first fma the per-pixel chain used to start with: results are bit-identical), L0, L1, L2.
-    __shared__ __attribute__((aligned(16))) float tab[6 * HID + 4];      // + the head bias bL
+    __shared__ __attribute__((aligned(16))) float tab[(HEAD3 ? 3 + TAPS : 6) * HID + 4];      // + the head bias bL
     // Inference (no SAVE) keeps the synthesis branch in REVOLUTIONS: weights, biases and the Q0 table come from the
     // sections divided by 2 pi (WLR, BQR, Q0R), so every sine is v_fract + v_sin instead of a 5-op reduction (each VALU
     // instruction costs ~3 cycles of fp32-MFMA issue).  The training forward saves sine arguments in radians and
@@ -58,6 +68,8 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
             *(f32x4*)(tab + 2 * HID + 4 * i) = t;
+        } else if constexpr (HEAD3) {
+            // (the 27 head rows are loaded by all four waves below; mode 4's bias and both validity words belong to the gather)
         } else if (part == 2) {
             *(f32x4*)(tab + 3 * HID + 4 * i) = *(const f32x4*)(p.Wt + OFF_L + 0 * HID + 4 * i);
             *(f32x4*)(tab + 4 * HID + 4 * i) = *(const f32x4*)(p.Wt + OFF_L + 1 * HID + 4 * i);
@@ -70,6 +82,11 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
                 const unsigned nanm = SAVE ? 0u : derived_nan_mask(p.Wt);
                 *(f32x4*)(tab + 6 * HID) = or_bits(bl, nanm);
             }
+        }
+        if constexpr (HEAD3) {
+#pragma unroll
+            for (int v = threadIdx.x; v < TAPS * HID / 4; v += 256)
+                *(f32x4*)(tab + 3 * HID + 4 * v) = *(const f32x4*)(p.head3 + 4 * v);
         }
     }
     const int lane = threadIdx.x & 63;
@@ -259,6 +276,36 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
 #endif
     }
 
+    if constexpr (HEAD3) {
+        // ---- mode 4: the 27 tap values T[k][c] = Lw[c][:][ky][kx] . q3 of this pixel   (diinn.py:146, first half)
+        float o[TAPS];
+#pragma unroll
+        for (int r = 0; r < TAPS; ++r) o[r] = 0.0f;
+        const float* __restrict__ L = tab + 3 * HID + 4 * h;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c0 = 32 * m + 8 * g;
+#pragma unroll
+                for (int r = 0; r < TAPS; ++r) {
+                    const f32x4 l = *(const f32x4*)(L + r * HID + c0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[r] = __builtin_fmaf(l[e], q[16 * m + 4 * g + e], o[r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TAPS; ++r) o[r] += __shfl_xor(o[r], 32);
+        if (valid && h == 0) {
+            float* t = p.out + (((long long)b * p.Orows + (y - p.Orow0)) * p.Wu + x) * TAP_STRIDE;
+#pragma unroll
+            for (int v = 0; v < TAP_STRIDE / 4; ++v)
+                *(f32x4*)(t + 4 * v) = f32x4{o[4 * v], o[4 * v + 1], o[4 * v + 2], 4 * v + 3 < TAPS ? o[(4 * v + 3) % TAPS] : 0.0f};
+        }
+        STAMP(5);
+        return;
+    }
     // ---- head: out = L . q3 + bL   (diinn.py:138)
     float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
     {
@@ -733,7 +780,130 @@ static int decode_impl(void* stream, const float* feat_dev, const float* packed_
                             compute, pw, ow);
 }
 
+// ---------------------------------------------------------------------------------
+// head3x3_reflect_kernel (decoder mode 4, diinn.py:89-90,146: the second half of the 3x3 'reflect' head):
+//   out[b, c, y, x] = bL[c] + sum_{k = 0..8} T[b, refl(y + ky - 1, Hu), refl(x + kx - 1, Wu)][k][c],   k = 3 ky + kx,
+//   refl(-1, n) = 1, refl(n, n) = n - 2 (PyTorch 'reflect': needs n >= 2).
+// One thread per HR pixel, the nine taps added in the fixed order k = 0..8 starting from the bias: deterministic, and a band is
+// bit-identical to the same rows of a whole-image decode.  Reflection is applied to IMAGE coordinates; the tap buffer holds rows
+// [ty0, ty0 + trows) = [max(0, y0 - 1), min(Hu, y1 + 1)), which contain every reflected row of the band (row -1 -> 1, Hu -> Hu - 2).
+// Neighbouring threads read neighbouring 112-byte pixel records: every line of the tap buffer is used whole.  Both validity
+// words (the body image's derived sections, the head image's own) are folded into the bias, so a wrong image answers NaN.
+// ---------------------------------------------------------------------------------
+struct Head3Params {
+    const float* taps;     // [B][trows][Wu][TAP_STRIDE]
+    const float* Wt;       // body image (validity word only)
+    const float* head3;    // head image (bias, validity word)
+    float* out;            // [B,3,Orows,Wu] = HR rows [Orow0, Orow0 + Orows)
+    int Hu, Wu, y0, y1, ty0, trows, Orow0, Orows;
+};
+constexpr int H3_BLOCK_W = 64, H3_BLOCK_H = 4;
+
+__global__ __launch_bounds__(256) void head3x3_reflect_kernel(const Head3Params p) {
+    const int x = blockIdx.x * H3_BLOCK_W + (threadIdx.x & (H3_BLOCK_W - 1));
+    const int y = p.y0 + blockIdx.y * H3_BLOCK_H + (threadIdx.x / H3_BLOCK_W);
+    const int b = blockIdx.z;
+    if (x >= p.Wu || y >= p.y1) return;
+    const unsigned nanm = derived_nan_mask(p.Wt) |
+        (__builtin_bit_cast(unsigned, p.head3[HEAD3_BIAS + 3]) == DIINN_HEAD3X3_MAGIC ? 0u : 0x7fc00000u);
+    float a0 = or_bits(p.head3[HEAD3_BIAS + 0], nanm);
+    float a1 = or_bits(p.head3[HEAD3_BIAS + 1], nanm);
+    float a2 = or_bits(p.head3[HEAD3_BIAS + 2], nanm);
+    const float* __restrict__ tb = p.taps + (size_t)b * p.trows * p.Wu * TAP_STRIDE;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        int yy = y + ky - 1;
+        yy = yy < 0 ? 1 : (yy >= p.Hu ? p.Hu - 2 : yy);
+        const float* __restrict__ row = tb + (size_t)(yy - p.ty0) * p.Wu * TAP_STRIDE;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            int xx = x + kx - 1;
+            xx = xx < 0 ? 1 : (xx >= p.Wu ? p.Wu - 2 : xx);
+            const float* __restrict__ t = row + (size_t)xx * TAP_STRIDE + 3 * (3 * ky + kx);
+            a0 += t[0];
+            a1 += t[1];
+            a2 += t[2];
+        }
+    }
+    const size_t plane = (size_t)p.Orows * p.Wu;
+    float* o = p.out + (size_t)b * 3 * plane + (size_t)(y - p.Orow0) * p.Wu + x;
+    o[0] = a0;
+    o[plane] = a1;
+    o[2 * plane] = a2;
+}
+
+// Mode 4, HR rows [y0,y1) of the image from P: the tap form of decode_kernel over the extended rows [ty0,ty1), then the gather.
+// `ow`: the rows `out_dev` holds.  fp32 only, the throughput kernel only (no 16-pixel latency twin).
+static int decode_mode4_band_impl(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
+                                  float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                  int sin_mode, RowWin pw, RowWin ow) {
+    if (!P_dev || !packed_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    int ty0, ty1, r0, r1;
+    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);      // Hu, Wu >= 2 and 0 <= y0 < y1 <= Hu
+    if (st) return st;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    st = check_window(pw.row0, pw.rows, H, r0, r1);
+    if (st) return st;
+    st = check_window(ow.row0, ow.rows, Hu, y0, y1);
+    if (st) return st;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
+    const int gy = (ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
+    const dim3 hgrid((Wu + H3_BLOCK_W - 1) / H3_BLOCK_W, (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H, B);
+    if (gy > 65535 || hgrid.y > 65535) return DIINN_ERR_TOO_LARGE;
+    DecodeParams p;
+    p.P = P_dev; p.Wt = packed_dev; p.out = taps_dev; p.head3 = head_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = ty0; p.y1 = ty1;
+    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
+    p.Prow0 = pw.row0; p.Prows = pw.rows; p.Orow0 = ty0; p.Orows = ty1 - ty0;      // rows of the tap buffer
+    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_bs = 0; p.o_ps = 0; p.o_rs = 0;           // (unused by the tap form)
+    p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;
+    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
+#ifdef DIINN_STAMPS
+    p.stamps = nullptr;
+#endif
+    const int small = diinn_uses_small_output_kernel(Hu, Wu);
+    p.ah = make_axis(H, Hu, small);
+    p.aw = make_axis(W, Wu, small);
+    const dim3 grid(gx, gy, B);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    st = hip_status(hipGetLastError());
+    if (st) return st;
+    const Head3Params hp{taps_dev, packed_dev, head_dev, out_dev, Hu, Wu, y0, y1, ty0, ty1 - ty0, ow.row0, ow.rows};
+    hipLaunchKernelGGL(head3x3_reflect_kernel, hgrid, dim3(256), 0, (hipStream_t)stream, hp);
+    return hip_status(hipGetLastError());
+}
+
 extern "C" {
+
+int diinn_decode_mode4_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
+                            float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                            int sin_mode) {
+    return decode_mode4_band_impl(stream, P_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
+                                  RowWin{0, H}, RowWin{0, Hu});
+}
+
+int diinn_decode_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
+                       float* workspace_dev, float* taps_dev, float* out_dev,
+                       int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!workspace_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
+    int ty0, ty1, r0, r1;
+    int st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
+    if (st) return st;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    const RowWin full{0, H};
+    st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, r0, r1, 16, 0, &full, &full, true);
+    if (st) return st;
+    return decode_mode4_band_impl(stream, workspace_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1,
+                                  sin_mode, full, RowWin{0, Hu});
+}
 
 int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B, int H, int W, int r0, int r1) {
     return cell_chain_impl(stream, P_dev, packed_dev, B, H, W, r0, r1, RowWin{0, H});

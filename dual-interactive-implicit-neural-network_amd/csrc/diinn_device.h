@@ -3,8 +3,8 @@
 // path, and the small host-side helpers of the C ABI launch functions.
 //
 // Translation units (all built with hipcc --offload-arch=gfx950 -O3 -ffp-contract=off; build.py: HIP_SOURCES + HOST_SOURCES):
-//   diinn_decode.hip           decode_kernel (+ modes 1/2 chain, training forward), decode_coop16_kernel (latency form),
-//                              and the decode entry points of the C ABI
+//   diinn_decode.hip           decode_kernel (+ modes 1/2 chain, training forward, mode 4's tap form), decode_coop16_kernel (latency
+//                              form), head3x3_reflect_kernel (mode 4's 9-point gather) and the decode entry points of the C ABI
 //   diinn_precompute.hip       precompute_P_kernel (direct fp32), precompute_P_bf16_kernel / _bf16_wide_kernel, launch_P
 //   diinn_precompute_wino.hip  precompute_P_wino_kernel (the fp32 hoisted conv in Winograd F(2x2,3x3) form: inference)
 //   diinn_precompute_x3.hip    precompute_P_x3_kernel (the hoisted conv in split-bf16 arithmetic: DIINN_COMPUTE_BF16X3, large maps)
@@ -123,7 +123,10 @@ struct DecodeParams {
     int pg[6];             // decode_bf16_coop8p_kernel: block grid (x, y, z), super-tile grid (x, y), super-tiles per XCD
     float ratio;           // fp32(H*W / (Hu*Wu))   (diinn.py:166)
     Axis ah, aw;
-    float* acts;           // training forward only (SAVE): saved activations, tiled planes [4 layers][ntiles][512][32]
+    union {
+        float* acts;       // training forward only (SAVE): saved activations, tiled planes [4 layers][ntiles][512][32]
+        const float* head3;   // decoder mode 4 only (HEAD3): the packed 3x3 head image (diinn_pack_head3x3); `out` is the tap buffer
+    };
     long long npix;        // SAVE: B*Hu*Wu
 #ifdef DIINN_STAMPS
     unsigned long long* stamps;   // diagnostic build only: 8 x u64 per wave (never in the shipped library)

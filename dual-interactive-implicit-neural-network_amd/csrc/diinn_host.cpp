@@ -410,6 +410,38 @@ int diinn_lr_rows_for_band(int H, int Hu, int Wu, int y0, int y1, int* r0, int* 
     return DIINN_OK;
 }
 
+// ---- decoder mode 4: the 3x3 reflect-padded head (diinn_layout.h "decoder mode 4") -----------------------------
+size_t diinn_head3x3_packed_floats(void) { return HEAD3_FLOATS; }
+
+int diinn_pack_head3x3(const float* Lw, const float* Lb, float* packed) {
+    if (!Lw || !Lb || !packed) return DIINN_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; ++k)                                 // k = 3 ky + kx: Lw is [3][256][3][3]
+        for (int c = 0; c < NOUT; ++c)
+            for (int ch = 0; ch < HID; ++ch)
+                packed[(size_t)(3 * k + c) * HID + ch] = Lw[((size_t)c * HID + ch) * 9 + k];
+    for (int c = 0; c < NOUT; ++c) packed[HEAD3_BIAS + c] = Lb[c];
+    const uint32_t magic = DIINN_HEAD3X3_MAGIC;
+    std::memcpy(packed + HEAD3_BIAS + 3, &magic, 4);
+    return DIINN_OK;
+}
+
+int diinn_mode4_rows(int H, int Hu, int Wu, int y0, int y1, int* ty0, int* ty1, int* r0, int* r1) {
+    if (Hu < 2 || Wu < 2 || !ty0 || !ty1 || !r0 || !r1) return DIINN_ERR_INVALID_ARG;   // 'reflect' needs two rows and two columns
+    if (H <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
+    const int a = y0 > 0 ? y0 - 1 : 0, b = y1 < Hu ? y1 + 1 : Hu;
+    const int st = diinn_lr_rows_for_band(H, Hu, Wu, a, b, r0, r1);
+    if (st) return st;
+    *ty0 = a;
+    *ty1 = b;
+    return DIINN_OK;
+}
+
+size_t diinn_mode4_taps_bytes(int B, int Hu, int Wu, int y0, int y1) {
+    if (B <= 0 || Hu < 2 || Wu < 2 || y0 < 0 || y1 > Hu || y0 >= y1) return 0;
+    const int a = y0 > 0 ? y0 - 1 : 0, b = y1 < Hu ? y1 + 1 : Hu;
+    return (size_t)B * (size_t)(b - a) * (size_t)Wu * TAP_STRIDE * sizeof(float);
+}
+
 int diinn_window_rows(int H, int Hu, int Wu, int y0, int y1,
                       int* feat_row0, int* feat_rows, int* p_row0, int* p_rows) {
     int r0, r1;

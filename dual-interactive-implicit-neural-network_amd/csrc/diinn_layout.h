@@ -113,6 +113,17 @@ constexpr size_t OFF_WL16   = OFF_WPX + SZ_WPX;
 constexpr size_t SZ_WL16    = 3 * WL16_LAYER;              // 393,216 floats = 1.5 MiB
 constexpr size_t PACKED_FLOATS = OFF_WL16 + SZ_WL16;       // 4,691,204
 
+// ---- decoder mode 4 (diinn.py:89-90: last_layer = Conv2d(256, 3, 3, padding=1, padding_mode='reflect')) ----
+// The 3x3 head is a SEPARATE small image (diinn_pack_head3x3; the body image above is the mode-3 image with a zero 1x1 head):
+//   [r 27][ch 256]  value = last_layer.weight[ c ][ ch ][ ky ][ kx ],  r = 3 k + c,  k = 3 ky + kx   (natural channel order),
+//   then bL[3] and the image's own validity word DIINN_HEAD3X3_MAGIC.
+// decode_kernel<HEAD3> writes, per HR pixel, the 27 values T[r] = row r . q3 to the TAP BUFFER, pixel-major
+// [b][row - ty0][x][TAP_STRIDE] (r in 0..26, one pad float); head3x3_reflect_kernel gathers nine of them per output.
+constexpr int    TAPS         = 27;
+constexpr int    TAP_STRIDE   = 28;
+constexpr size_t HEAD3_BIAS   = (size_t)TAPS * HID;
+constexpr size_t HEAD3_FLOATS = HEAD3_BIAS + 4;                // 6,916
+
 // channel held by activation register (m, r) of lane-half h
 DIINN_HD int chan_of(int kk /* = 16*m + r */, int h) {
     const int m = kk >> 4, r = kk & 15;

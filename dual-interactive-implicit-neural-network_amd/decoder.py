@@ -47,7 +47,8 @@ def pack_state_dict(sd, prefix: str = "", mode: int = 3) -> torch.Tensor:
     SURVEY.md App. A.1 (init_q=False).  Modes 2 and 3 share the layout (K.i is [256, 832]: 256
     chained inputs, then the 576 unfolded features); mode 1's K.i is [256, 256] (no feature
     columns, diinn.py:53-60) and is widened with zero feature columns, so P_i = bK_i for i >= 1.
-    Calls the C ABI ``diinn_pack_weights`` (include/diinn_hip.h)."""
+    Mode 4 gives the BODY image: the mode-3 image of the same K / Q tensors with a zero 1x1 head; its 3x3 head is a
+    second image (``pack_head3x3``).  Calls the C ABI ``diinn_pack_weights`` (include/diinn_hip.h)."""
     lib = _native.load()
 
     def get(name, shape):
@@ -69,7 +70,10 @@ def pack_state_dict(sd, prefix: str = "", mode: int = 3) -> torch.Tensor:
     q0w = get("Q.0.0.weight", (HIDDEN, 3)); q0b = get("Q.0.0.bias", (HIDDEN,))
     qw = [get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) for i in (1, 2, 3)]
     qb = [get(f"Q.{i}.0.bias", (HIDDEN,)) for i in (1, 2, 3)]
-    lw = get("last_layer.weight", (3, HIDDEN)); lb = get("last_layer.bias", (3,))
+    if mode == 4:
+        lw = np.zeros((3, HIDDEN), np.float32); lb = np.zeros((3,), np.float32)
+    else:
+        lw = get("last_layer.weight", (3, HIDDEN)); lb = get("last_layer.bias", (3,))
 
     packed = np.empty(lib.diinn_packed_weight_floats(), dtype=np.float32)
     f3 = _native._f3
@@ -81,6 +85,33 @@ def pack_state_dict(sd, prefix: str = "", mode: int = 3) -> torch.Tensor:
         _native.fptr(lw), _native.fptr(lb), _native.fptr(packed))
     _native.check(st, "diinn_pack_weights")
     return torch.from_numpy(packed)
+
+
+def pack_head3x3(sd, prefix: str = "") -> torch.Tensor:
+    """Mode 4's head, ``last_layer.weight`` [3,256,3,3] and ``last_layer.bias`` [3] (diinn.py:89-90), -> its packed host
+    image (1-D fp32 CPU tensor; C ABI ``diinn_pack_head3x3``: [27][256] with row 3 (3 ky + kx) + c, the bias, a validity
+    word)."""
+    lib = _native.load()
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
+        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
+
+    lw = get("last_layer.weight", (3, HIDDEN, 3, 3)); lb = get("last_layer.bias", (3,))
+    packed = np.empty(lib.diinn_head3x3_packed_floats(), dtype=np.float32)
+    _native.check(lib.diinn_pack_head3x3(_native.fptr(lw), _native.fptr(lb), _native.fptr(packed)), "diinn_pack_head3x3")
+    return torch.from_numpy(packed)
+
+
+def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    """((ty0, ty1), (r0, r1)): the HR rows whose tap values mode 4 needs for output rows [y0,y1) (one more row each way,
+    clipped to the image) and the LR rows those read (C ABI ``diinn_mode4_rows``)."""
+    lib = _native.load()
+    a, b, r0, r1 = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    _native.check(lib.diinn_mode4_rows(h, hu, wu, y0, y1, C.byref(a), C.byref(b), C.byref(r0), C.byref(r1)),
+                  "diinn_mode4_rows")
+    return (a.value, b.value), (r0.value, r1.value)
 
 
 def axis_tables(n_in: int, n_out: int, small_output: bool = False) -> Tuple[np.ndarray, np.ndarray]:
@@ -116,7 +147,8 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
 def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
                     out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     rows: Optional[Tuple[int, int]] = None, sin_mode: int = _native.SIN_DEFAULT,
-                    compute: str = "f32", mode: int = 3) -> torch.Tensor:
+                    compute: str = "f32", mode: int = 3, head: Optional[torch.Tensor] = None,
+                    taps: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode encoder features ``feat`` [B,64,H,W] to RGB [B,3,Hu,Wu].
 
     ``rows=(y0,y1)`` computes only that HR row band (tile sharding across GPUs);
@@ -125,8 +157,11 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
     "bf16_full" (bf16 operands in layers 1..3 / also in the hoisted conv, fp32 accumulate; ~2e-3 relative) or
     "bf16x3" (split bf16: hi + lo bf16 operands, three bf16 MFMA products per term; held to f32's 1e-4 bound).  ``mode`` 3 (default) is the
     reference's final model; modes 1 and 2 (packed with ``pack_state_dict(..., mode=...)``) run fp32
-    only.  Enqueues two kernels (three for modes 1/2: + the per-cell modulation chain) on the
-    current stream; never synchronises."""
+    only.  Mode 4 (fp32 only) takes the body image as ``packed`` (``pack_state_dict(..., mode=4)``) and the 3x3 head
+    image as ``head`` (``pack_head3x3``); ``taps`` is its second workspace, ``diinn_mode4_taps_bytes`` bytes for the
+    rows decoded (allocated if None).  A row band of mode 4 is bit-identical to the same rows of a whole-image decode.
+    Enqueues two kernels (three for modes 1/2: + the per-cell modulation chain; three for mode 4: + the 9-point
+    gather) on the current stream; never synchronises."""
     lib = _native.load()
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
@@ -149,10 +184,31 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
     elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous() \
             or workspace.device != feat.device:
         raise ValueError(f"workspace must be a contiguous buffer of >= {need} bytes on feat's device")
-    if mode not in (1, 2, 3):
-        raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-3")
+    if mode not in (1, 2, 3, 4):
+        raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-4")
     if mode != 3 and compute != "f32":
-        raise ValueError("modes 1 and 2 run in fp32 only")
+        raise ValueError("modes 1, 2 and 4 run in fp32 only")
+    if mode == 4:
+        if head is None:
+            raise ValueError("mode 4 needs its 3x3 head image: head=pack_head3x3(state_dict) on feat's device")
+        _require_cuda(head, "head image")
+        if hu < 2 or wu < 2:
+            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+        tneed = lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1)
+        if tneed == 0:
+            raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
+        if taps is None:
+            taps = torch.empty(tneed // 4, dtype=torch.float32, device=feat.device)
+        elif taps.numel() * taps.element_size() < tneed or not taps.is_contiguous() or taps.device != feat.device:
+            raise ValueError(f"taps must be a contiguous buffer of >= {tneed} bytes on feat's device")
+        with torch.cuda.device(feat.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            st = lib.diinn_decode_mode4(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                        C.c_void_p(head.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                        C.c_void_p(taps.data_ptr()), C.c_void_p(out.data_ptr()),
+                                        b, h, w, hu, wu, y0, y1, int(sin_mode))
+        _native.check(st, "diinn_decode_mode4")
+        return out
     comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
     with torch.cuda.device(feat.device):
         stream = torch.cuda.current_stream().cuda_stream
@@ -206,7 +262,8 @@ def decode_window(feat_win: torch.Tensor, feat_row0: int, full_h: int, packed: t
             or out_win.device != feat_win.device:
         raise ValueError("out_win must be a contiguous fp32 [B,3,y1-y0,Wu] tensor on feat_win's device")
     if mode not in (1, 2, 3):
-        raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-3")
+        raise NotImplementedError(f"mode {mode}: windows and tiles cover modes 1-3 (mode 4's 3x3 head reads its "
+                                  f"neighbours' rows and columns: decode it with decode_features(rows=...))")
     if mode != 3 and compute != "f32":
         raise ValueError("modes 1 and 2 run in fp32 only")
     comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
@@ -246,7 +303,8 @@ def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: 
         raise ValueError("p_win must be a contiguous fp32 buffer of B * rows * W * 1024 floats")
     p_rows = p_win.numel() // (b * w * P_CHANNELS)
     if mode not in (1, 2, 3):
-        raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-3")
+        raise NotImplementedError(f"mode {mode}: windows and tiles cover modes 1-3 (mode 4's 3x3 head reads its "
+                                  f"neighbours' rows and columns: decode it with decode_features(rows=...))")
     if mode != 3 and compute != "f32":
         raise ValueError("modes 1 and 2 run in fp32 only")
     comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
@@ -393,9 +451,9 @@ class ImplicitDecoder(nn.Module):
 
     Every mode registers the reference's parameters (so any reference checkpoint
     loads); the MI355X kernels implement the paper's final variant, ``mode=3,
-    init_q=False`` (README.md:111-112 of the reference), and the ablation modes 1 and 2, whose
-    modulation branch depends on the LR cell only.  Mode 4 and ``init_q=True`` raise
-    ``NotImplementedError`` in ``forward``."""
+    init_q=False`` (README.md:111-112 of the reference), the ablation modes 1 and 2, whose
+    modulation branch depends on the LR cell only, and mode 4, mode 3 with a 3x3 reflect-padded
+    head (inference, fp32).  ``init_q=True`` raises ``NotImplementedError`` in ``forward``."""
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32"):
@@ -427,8 +485,15 @@ class ImplicitDecoder(nn.Module):
         # P workspaces, one per (device, stream) that called forward: two streams decoding through one module concurrently
         # must not share the hoisted conv's image (at most _MAX_WORKSPACES kept, oldest dropped)
         self._workspaces: "Dict[tuple, torch.Tensor]" = {}
+        # mode 4: the head image (cached with the body image) and the tap workspaces, kept like the P workspaces
+        self._packed_head: Optional[torch.Tensor] = None
+        self._tap_workspaces: "Dict[tuple, torch.Tensor]" = {}
 
     _MAX_WORKSPACES = 4
+    # mode 4 decodes at most this many HR rows per call, which caps the tap buffer at B x 256 x Wu x 112 bytes.  254, not 256: a
+    # middle chunk needs the tap values of one more row each way, and 256 tap rows are a whole number of decode_kernel's 8-row
+    # blocks (258 rows start a 33rd block row: at 1024 x 1024 a ninth round of workgroups per chunk, 7.40 against 6.47 ms measured)
+    MODE4_CHUNK_ROWS = 254
 
     # -- packed-weight cache ---------------------------------------------------
     def _weights_key(self, device):
@@ -439,14 +504,22 @@ class ImplicitDecoder(nn.Module):
         if self._packed is None or self._packed_key != key:
             sd = self.state_dict()
             self._packed = pack_state_dict(sd, mode=self.mode).to(device)
+            self._packed_head = pack_head3x3(sd).to(device) if self.mode == 4 else None
             self._packed_key = key
         return self._packed
 
+    def packed_head(self, device) -> torch.Tensor:
+        """Mode 4: the 3x3 head image on ``device`` (packed and cached together with the body image)."""
+        if self.mode != 4:
+            raise ValueError("only mode 4 has a 3x3 head image")
+        self.packed_weights(device)
+        return self._packed_head
+
     def _check_supported(self):
-        if self.mode not in (1, 2, 3) or self.init_q:
+        if self.mode not in (1, 2, 3, 4) or self.init_q:
             raise NotImplementedError(
-                f"diinn_amd HIP decode path implements modes 1-3 with init_q=False (mode 3 is the reference's "
-                f"final model; mode 4's 3x3 head is not tile-independent); got mode={self.mode}, init_q={self.init_q}")
+                f"diinn_amd HIP decode path implements modes 1-4 with init_q=False (mode 3 is the reference's "
+                f"final model; init_q=True is not covered); got mode={self.mode}, init_q={self.init_q}")
         if self.in_channels != IN_CHANNELS or self.hidden_dims != [HIDDEN] * 4:
             raise NotImplementedError("diinn_amd HIP decode path is built for in_channels=64, hidden_dims=[256]*4")
 
@@ -456,34 +529,61 @@ class ImplicitDecoder(nn.Module):
         ``bsize`` is the reference's column-strip size (diinn.py:149-160), a
         memory knob there.  The fused kernels keep every per-pixel intermediate
         in registers, so it is accepted and ignored (results are identical for
-        any value; the reference's hang for bsize < H_up cannot occur)."""
+        any value; the reference's hang for bsize < H_up cannot occur).
+
+        Mode 4: the reference's ``batched_step`` applies the head's reflect padding at every column-strip edge, so
+        the reference's own result depends on ``bsize`` there.  This path reproduces ``bsize=None``, the whole-image
+        convolution, for any ``bsize``.  Inference only (``torch.no_grad()``), fp32; the image is decoded in chunks
+        of at most ``MODE4_CHUNK_ROWS`` HR rows, which bounds the tap workspace and changes no bit of the result."""
         self._check_supported()
+        wants_grad = bsize is None and torch.is_grad_enabled() and (
+            x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
+        # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
+        if wants_grad and (self.mode != 3 or self.compute != "f32"):
+            raise NotImplementedError(
+                "diinn_amd: autograd through the HIP decode path covers mode 3 in fp32 (the reference's final "
+                "model); call modes 1/2/4 or the bf16 path under torch.no_grad()")
         _require_cuda(x, "x")
-        if bsize is None and torch.is_grad_enabled() and (
-                x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # reference: bsize=None runs step() under autograd (training, sr_module.py:128)
-            if self.mode != 3 or self.compute != "f32":
-                raise NotImplementedError(
-                    "diinn_amd: autograd through the HIP decode path covers mode 3 in fp32 (the reference's final "
-                    "model); call modes 1/2 or the bf16 path under torch.no_grad()")
+        if wants_grad:
             from .training import decode_with_grad
             return decode_with_grad(self, x, size)
         b, c, h, w = x.shape
         need = b * h * w * P_CHANNELS
-        if torch.cuda.is_current_stream_capturing():
+        capturing = torch.cuda.is_current_stream_capturing()
+        key = None if capturing else (str(x.device), torch.cuda.current_stream(x.device).cuda_stream)
+
+        def cached(cache, numel):
             # hipGraph capture (modules._GraphReplay): the captured kernels keep the workspace pointer for the
-            # graph's lifetime, so it must come from the graph's private pool -- the cached workspace below is
+            # graph's lifetime, so it must come from the graph's private pool -- the cached workspace is
             # replaced (and its block recycled) as soon as a larger input arrives
-            workspace = None
-        else:
-            key = (str(x.device), torch.cuda.current_stream(x.device).cuda_stream)
-            workspace = self._workspaces.get(key)
-            if workspace is None or workspace.numel() < need:
-                self._workspaces.pop(key, None)
-                while len(self._workspaces) >= self._MAX_WORKSPACES:
-                    self._workspaces.pop(next(iter(self._workspaces)))
-                workspace = self._workspaces[key] = torch.empty(need, dtype=torch.float32, device=x.device)
+            if capturing:
+                return torch.empty(numel, dtype=torch.float32, device=x.device)
+            ws = cache.get(key)
+            if ws is None or ws.numel() < numel:
+                cache.pop(key, None)
+                while len(cache) >= self._MAX_WORKSPACES:
+                    cache.pop(next(iter(cache)))
+                ws = cache[key] = torch.empty(numel, dtype=torch.float32, device=x.device)
+            return ws
+
+        workspace = cached(self._workspaces, need)
         with torch.no_grad():
             packed = self.packed_weights(x.device)
-            return decode_features(x, packed, size, workspace=workspace, sin_mode=self.sin_mode,
-                                   compute=self.compute, mode=self.mode)
+            if self.mode != 4:
+                return decode_features(x, packed, size, workspace=workspace, sin_mode=self.sin_mode,
+                                       compute=self.compute, mode=self.mode)
+            if self.compute != "f32":
+                raise ValueError("mode 4 runs in fp32 only")
+            hu, wu = size
+            hu, wu = int(hu), int(wu)
+            if hu < 2 or wu < 2:
+                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+            chunk = self.MODE4_CHUNK_ROWS
+            # (rows [0, chunk + 1) reach one tap row each way unless the image ends first: the largest band of the loop below)
+            taps = cached(self._tap_workspaces, _native.load().diinn_mode4_taps_bytes(b, hu, wu, 1, min(hu, chunk + 1)) // 4)
+            out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
+            for y0 in range(0, hu, chunk):
+                decode_features(x, packed, (hu, wu), out=out, workspace=workspace, rows=(y0, min(hu, y0 + chunk)),
+                                sin_mode=self.sin_mode, mode=4, head=self._packed_head, taps=taps)
+            return out

@@ -394,7 +394,7 @@ class _GraphReplay:
                 # private pool: workspaces, activations, the result) or kept alive by the entry below (packed
                 # weight images, which live in module caches that a later call may replace)
                 static_y = self._forward_eager(static_x, size, bsize)
-            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2")]
+            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_packed_head", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2")]
             entry = (graph, static_x, static_y, keep)
             self._graph_cache[key] = entry
         graph, static_x, static_y = entry[:3]
@@ -439,6 +439,9 @@ class DIINN(nn.Module, _GraphReplay):
         With one rank this is ``forward``.  The reference has no multi-GPU inference (benchmarks.py:13: devices=1)."""
         import torch.distributed as dist
         from . import sharded as S
+        if self.decoder.mode == 4:
+            raise NotImplementedError("forward_sharded does not cover mode 4 (its 3x3 head reads the neighbouring band's "
+                                      "rows); use forward, which decodes mode 4 in row chunks on one GPU")
         if not dist.is_initialized() or dist.get_world_size(group) == 1:
             out = self._forward_eager(x, size, None)
             return out if gather_to is not None else (out, (0, int(size[0])))

@@ -79,7 +79,8 @@ def normalish(seed: int, name: str, shape) -> np.ndarray:
 def decoder_param_shapes(mode: int = 3) -> "OrderedDict[str, tuple]":
     """Reference ``ImplicitDecoder(mode=mode, init_q=False).state_dict()`` layout
     (diinn.py:53-92).  Mode 1 chains k -> K[i] (256 inputs); modes 2-4 feed
-    [k or q ; unfolded features] (832 inputs)."""
+    [k or q ; unfolded features] (832 inputs).  Mode 4's head is the 3x3 conv of diinn.py:89-90; tensors are drawn by
+    name, so every other tensor (and every tensor of modes 1-3) keeps its bits."""
     shapes: "OrderedDict[str, tuple]" = OrderedDict()
     for i in range(N_LAYERS):
         kin = UNFOLD if i == 0 else (HIDDEN if mode == 1 else HIDDEN + UNFOLD)
@@ -88,7 +89,7 @@ def decoder_param_shapes(mode: int = 3) -> "OrderedDict[str, tuple]":
         shapes[f"K.{i}.0.bias"] = (HIDDEN,)
         shapes[f"Q.{i}.0.weight"] = (HIDDEN, qin, 1, 1)
         shapes[f"Q.{i}.0.bias"] = (HIDDEN,)
-    shapes["last_layer.weight"] = (3, HIDDEN, 1, 1)
+    shapes["last_layer.weight"] = (3, HIDDEN, 3, 3) if mode == 4 else (3, HIDDEN, 1, 1)
     shapes["last_layer.bias"] = (3,)
     return shapes
 

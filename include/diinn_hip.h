@@ -244,6 +244,45 @@ int diinn_decode_tile_win(void* stream, const float* P_win_dev, int p_row0, int 
  * (diinn.py:118-121,126-129), for LR rows [r0,r1); k_i overwrites the P_i slot (i = 1..3) of P_dev. */
 int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B, int H, int W, int r0, int r1);
 
+/* ---- decoder mode 4: the 3x3 reflect-padded head (diinn.py:89-90,140-147) -------------------------------------
+ * Mode 4 is mode 3 up to the last activation q3; its head is last_layer = Conv2d(256, 3, 3, padding=1,
+ * padding_mode='reflect') over the HR grid.  A 3x3 convolution of a 256-channel image is a 1x1 map to 27 numbers per pixel
+ * followed by a 9-point gather:
+ *     T[b, y, x, k, c] = sum_ch Lw[c, ch, ky, kx] * q3[b, ch, y, x]                     k = 3 ky + kx
+ *     out[b, c, y, x]  = Lb[c] + sum_k T[b, refl(y + ky - 1, Hu), refl(x + kx - 1, Wu), k, c]     (k = 0..8, in that order)
+ *     refl(-1, n) = 1, refl(n, n) = n - 2     (PyTorch 'reflect': Hu >= 2 and Wu >= 2, else DIINN_ERR_INVALID_ARG -- the
+ *                                              reference raises there too)
+ * The first line runs inside the register-resident decode kernel (27 dot products in place of mode 3's 3), the second is a
+ * small kernel of its own over the TAP BUFFER.  fp32 only; inference only.
+ *
+ * IMAGES.  The body image is diinn_pack_weights of the K / Q tensors with a ZERO 1x1 head (Lw [3,256] and Lb all zero);
+ * the head is a second, small image: diinn_pack_head3x3(Lw [3][256][3][3], Lb [3]) writes diinn_head3x3_packed_floats()
+ * floats, [27][256] with row 3 k + c = Lw[c][:][ky][kx] (natural channel order), then Lb[3], then the head image's own
+ * validity word DIINN_HEAD3X3_MAGIC.  A head image without that word, or a body image without DIINN_PACKED_MAGIC, answers
+ * NaN in every output.
+ *
+ * ROWS.  To produce HR rows [y0,y1) the tap form runs on [ty0,ty1) = [max(0, y0-1), min(Hu, y1+1)): every reflected row
+ * index of the band lies in that range.  diinn_mode4_rows reports it together with the LR rows [r0,r1) =
+ * diinn_lr_rows_for_band(H, Hu, Wu, ty0, ty1) that P must hold.  The tap buffer is [B][ty1-ty0][Wu][28] floats (k major, c
+ * minor, one pad float: seven 16-byte stores per pixel), diinn_mode4_taps_bytes bytes (0 for invalid arguments).
+ *
+ * diinn_decode_mode4_band: P_dev [B,H,W,1024] holding rows [r0,r1) -> out_dev[b, :, y0:y1, :] of a contiguous [B,3,Hu,Wu]
+ *   tensor.  Two kernels.  A band is BIT-IDENTICAL to the same rows of a whole-image decode (reflection is applied to image
+ *   coordinates, never to band edges; the gather adds in a fixed order).
+ * diinn_decode_mode4: diinn_precompute_P on rows [r0,r1), then diinn_decode_mode4_band (cf. diinn_decode_ex).
+ * Neither allocates or synchronises. */
+#define DIINN_HEAD3X3_MAGIC 0x44494833u   /* "DIH3" */
+size_t diinn_head3x3_packed_floats(void);
+int    diinn_pack_head3x3(const float* Lw, const float* Lb, float* packed);
+int    diinn_mode4_rows(int H, int Hu, int Wu, int y0, int y1, int* ty0, int* ty1, int* r0, int* r1);
+size_t diinn_mode4_taps_bytes(int B, int Hu, int Wu, int y0, int y1);
+int    diinn_decode_mode4_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
+                               float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                               int sin_mode);
+int    diinn_decode_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
+                          float* workspace_dev, float* taps_dev, float* out_dev,
+                          int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+
 /* ---- training ------------------------------------
  * TILED PLANES.  Every per-pixel training buffer is a group of C channel rows over npix = B*Hu*Wu
  * pixels (pixel index (b*Hu + y)*Wu + x), stored as [ceil(npix/32) tiles][C rows][32 pixels] fp32:
