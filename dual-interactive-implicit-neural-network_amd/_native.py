@@ -22,7 +22,7 @@ SIN_HW_REDUCED = 2
 # default: 2-term reduction in revolutions + v_sin_f32 (max abs error 2.5e-7 for |x| <= 1e4, measured in
 # tests/test_gpu_parity.py::test_device_sine_accuracy); SIN_ACCURATE (1e-7) costs ~4 % more time
 SIN_DEFAULT = SIN_HW_REDUCED
-ABI_VERSION = 10
+ABI_VERSION = 11
 PACKED_MAGIC = 0x44493038
 HEAD3X3_MAGIC = 0x44494833             # validity word of the mode-4 head image (diinn_pack_head3x3)
 PACKED_MAGIC_WPU = 0x44495750          # a training image: permutation sections + section 13 (WPU) filled on the device
@@ -142,11 +142,9 @@ SIGNATURES = {
                                       C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),
     "diinn_plane_rowdot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_longlong, C.c_int]),
-    "diinn_backward_cell_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+    "diinn_backward_cell_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_sum_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
-    "diinn_backward_cell_sum_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_unfold_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_training_plane_floats": (C.c_longlong, [C.c_longlong, C.c_int]),
     "diinn_decode_train_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -704,8 +704,8 @@ int diinn_plane_rowdot(void* stream, const float* A_dev, int a_rows, const float
     return hip_status(hipGetLastError());
 }
 
-int diinn_backward_cell_sum_ex(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
-                               float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu) {
+int diinn_backward_cell_sum(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
+                            float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu) {
     if (!G_dev || !seg_h_dev || !seg_w_dev || !dP_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -718,11 +718,6 @@ int diinn_backward_cell_sum_ex(void* stream, const float* G_dev, const int32_t* 
     CellSumParams p{G_dev, dP_dev, dP_tiled_dev, seg_h_dev, seg_w_dev, B, H, W, Hu, Wu, (npix + PLANE_TILE - 1) / PLANE_TILE};
     hipLaunchKernelGGL(cell_sum_kernel, dim3((unsigned)(((long long)H * W + 255) / 256), (unsigned)B, PCH), dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
-}
-
-int diinn_backward_cell_sum(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
-                            float* dP_dev, int B, int H, int W, int Hu, int Wu) {
-    return diinn_backward_cell_sum_ex(stream, G_dev, seg_h_dev, seg_w_dev, dP_dev, nullptr, B, H, W, Hu, Wu);
 }
 
 int diinn_unfold_tiled(void* stream, const float* feat_dev, float* out_tiled_dev, int rows, int B, int H, int W) {

@@ -8,15 +8,17 @@ records ~30 ATen ops per call on the materialised [B,576,Hu,Wu] tensor.  Here:
             inference kernel that additionally writes every layer's rectified modulation k_i and sine
             argument s_i as [channel][pixel] planes -- all the backward pass needs.
   backward  ``backward_fused``: the per-pixel chain (gates and the transposed stacked GEMMs
-            g_q[i-1] = Wq_i^T g_a + Qw_i^T g_s) runs on bwd_head_kernel + 3 x bwd_layer_kernel (C ABI
-            ``diinn_backward_data``), which leave the gate gradients G_i and the activations q_i as
-            tiled planes; every parameter gradient is then one GEMM over the pixel axis per layer
-            (plane_gemm_lds_kernel, split-K, no atomics), two skinny products (plane_rowdot_kernel), a
-            per-cell segment sum (cell_sum_kernel) and the 3x3 conv's input/weight gradients (MIOpen
-            through torch.nn.grad).
-            ``backward_from_saved`` states the same gradients in device-agnostic tensor algebra; it
-            is the unit-tested formula sheet (CPU, against the reference's own .grad fixtures) and
-            the on-GPU cross-check of the fused path.  The forward has no CPU form.
+            g_q[i-1] = Wq_i^T g_a + Qw_i^T g_s) runs on 3 x bwd_layer_kernel (C ABI
+            ``diinn_backward_data``; the head's gates are computed inside layer 3's kernel), which leave
+            the gate gradients G_i and the activations q_i as tiled planes; every parameter gradient is
+            then one GEMM over the pixel axis per layer (plane_gemm_lds_kernel, split-K, no atomics),
+            two skinny products (plane_rowdot_kernel), a per-cell segment sum (cell_sum_kernel) and the
+            3x3 conv's gradients on the library's kernels as well (``_conv_grads_native``: unfold + the
+            plane GEMM for the weight, the encoder's convolution kernels for the input).
+            ``backward_from_saved`` states the same gradients in device-agnostic tensor algebra (the
+            conv's from torch.nn.grad); it is the unit-tested formula sheet (CPU, against the
+            reference's own .grad fixtures) and the on-GPU cross-check of the fused path.  The forward
+            has no CPU form.
 
 Weights change every optimiser step, so the packed image is rebuilt on the device each forward by one
 gather through a permutation index derived once from the host packer (``pack_gather_index``).
@@ -24,12 +26,10 @@ gather through a permutation index derived once from the host packer (``pack_gat
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from . import _native
 
@@ -53,13 +53,7 @@ PARAM_SHAPES: Dict[str, Tuple[int, ...]] = {
     "last_layer.weight": (3, HIDDEN, 1, 1), "last_layer.bias": (3,),
 }
 
-# backward_fused: the hoisted conv's gradients on the library's own kernels instead of torch.nn.grad (MIOpen).  Measured at B = 16,
-# 48x48 x4 (tools/train_conv_grads_ab.py): the input gradient is a 1024 -> 64 3x3 convolution = the encoder's Winograd kernel
-# (0.19 ms against MIOpen's 0.39); the weight gradient as unfold + plane GEMM costs 0.5 ms MORE than MIOpen's implicit GEMM
-# (im2col and two layout copies of 85-151 MB around a 0.42 ms GEMM), so it is available, not the default.
-NATIVE_CONV_DGRAD = True
-NATIVE_CONV_WGRAD = True
-NATIVE_SUM_PARTS = os.environ.get("DIINN_TRAIN_TORCH_SUM") != "1"       # (A/B: torch.sum over the slice axis instead of sum_parts_kernel)
+# backward_fused calls no framework convolution, GEMM or reduction of partials: the A/B runs that settled that are in DESIGN_HISTORY.md.
 WGRAD_KSPLIT = 64          # pixel-axis splits of the weight-gradient GEMM: 4 output blocks x 64 = one workgroup per CU
 ROWDOT_SPLITS = 1024       # workgroups of the skinny products (HBM-bound)
 
@@ -122,7 +116,6 @@ def pack_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
     return packed
 
 
-TRAIN_P_WINOGRAD = True    # the training forward's hoisted conv on the fp32 Winograd kernel (0.21 against 0.48 ms at B = 16, 48 x 48)
 _WPU_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 _section_cache: Dict[int, Tuple[int, int]] = {}
 
@@ -135,15 +128,20 @@ def _section(i: int) -> Tuple[int, int]:
     return _section_cache[i]
 
 
+def _hoisted_conv_weight(p: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """Wx [1024,64,3,3] of P = conv3x3(feat; Wx) + bK: the unfold columns of the four K weights, stacked over the layers."""
+    wx = torch.cat([p["K.0.0.weight"].reshape(HIDDEN, UNFOLD)]
+                   + [p[f"K.{i}.0.weight"].reshape(HIDDEN, HIDDEN + UNFOLD)[:, HIDDEN:] for i in (1, 2, 3)], 0)
+    return wx.reshape(4 * HIDDEN, IN_CHANNELS, 3, 3).contiguous()
+
+
 def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor]) -> None:
-    """Section 13 (WPU) of a gathered image, on the device: U = G Wx G^T per (output, input) pair in float64 in the host
+    """Section 13 (WPU) of a gathered image, on the device (what diinn_precompute_P_wpu, the training forward's hoisted conv on the
+    fp32 Winograd kernel, reads): U = G Wx G^T per (output, input) pair in float64 in the host
     packer's own operation order (csrc/diinn_host.cpp: (G g) first, then (.) G^T, sums left to right), rounded once, column 2
     negated, laid out [mt 32][row i 4][sg 8][col j 4][lane 64][e 4] -- bit-identical to diinn_pack_weights' section -- and
     the validity word DIINN_PACKED_MAGIC_WPU ("this training image holds WPU and nothing else derived")."""
-    p = dict(zip(PARAM_NAMES, params))
-    wx = torch.cat([p["K.0.0.weight"].detach().reshape(HIDDEN, UNFOLD)]
-                   + [p[f"K.{i}.0.weight"].detach().reshape(HIDDEN, HIDDEN + UNFOLD)[:, HIDDEN:] for i in (1, 2, 3)], 0)
-    w = wx.reshape(4 * HIDDEN, IN_CHANNELS, 3, 3).to(torch.float64)
+    w = _hoisted_conv_weight({name: t.detach() for name, t in zip(PARAM_NAMES, params)}).to(torch.float64)
     g = torch.tensor(_WPU_G, dtype=torch.float64, device=w.device)
     gi = [g[:, a].view(1, 1, 4, 1) for a in range(3)]
     t = gi[0] * w[:, :, 0:1, :] + gi[1] * w[:, :, 1:2, :] + gi[2] * w[:, :, 2:3, :]          # [O, C, i 4, b 3]
@@ -166,8 +164,7 @@ def _pack_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
         _gather_index_dev[key] = idx
     flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params] + [torch.zeros(1, device=dev)])
     packed = flat.index_select(0, idx)
-    if TRAIN_P_WINOGRAD:
-        _fill_wpu(packed, params)
+    _fill_wpu(packed, params)
     return packed
 
 
@@ -261,7 +258,10 @@ def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tens
 
     dp = torch.cat(d_p, dim=1).contiguous()                       # [B,1024,H,W]
     d_bk = dp.sum((0, 2, 3)).view(4, HIDDEN)
-    d_feat = _conv_and_assemble(p, feat, dp, d_wq, d_bk, grads, need_feat_grad)
+    wx = _hoisted_conv_weight(p)
+    d_wx = torch.nn.grad.conv2d_weight(feat, wx.shape, dp, padding=1)
+    d_feat = torch.nn.grad.conv2d_input(feat.shape, wx, dp, padding=1) if need_feat_grad else None
+    _assemble_k_grads(grads, d_wx, d_wq, d_bk)
     return d_feat, [grads[name] for name in PARAM_NAMES]
 
 
@@ -348,31 +348,14 @@ def _wino4_workspace(dev) -> torch.Tensor:
     return M.RDN._w4_area(dev)
 
 
-def _conv_and_assemble(p: Dict[str, torch.Tensor], feat: torch.Tensor, dp: torch.Tensor, d_wq, d_bk,
-                       grads: Dict[str, torch.Tensor], need_feat_grad: bool, native: bool = False,
-                       a_t: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
-    """P = conv3x3(feat; Wx[1024,64,3,3]) + bK: weight / input gradients of that one convolution (``native``: the
-    library's kernels, else torch.nn.grad = MIOpen on the GPU), then the K.i gradients in the reference's [256, 256+576] layout."""
-    wx = torch.cat([p["K.0.0.weight"].reshape(HIDDEN, UNFOLD)]
-                   + [p[f"K.{i}.0.weight"].reshape(HIDDEN, HIDDEN + UNFOLD)[:, HIDDEN:] for i in (1, 2, 3)], 0)
-    wx = wx.reshape(4 * HIDDEN, IN_CHANNELS, 3, 3).contiguous()
-    nat_w, nat_d = (native if isinstance(native, tuple) else (bool(native), bool(native)))
-    d_wx = d_feat = None
-    if nat_w or (nat_d and need_feat_grad):
-        wkey = tuple((p[f"K.{i}.0.weight"].data_ptr(), p[f"K.{i}.0.weight"]._version) for i in range(4))
-        d_wx, d_feat = _conv_grads_native(feat, wx, dp, need_feat_grad and nat_d, want_weight=nat_w, wkey=wkey,
-                                          wpins=tuple(p[f"K.{i}.0.weight"] for i in range(4)), a_t=a_t)
-    if d_wx is None:
-        d_wx = torch.nn.grad.conv2d_weight(feat, wx.shape, dp, padding=1)
-    if d_feat is None and need_feat_grad:
-        d_feat = torch.nn.grad.conv2d_input(feat.shape, wx, dp, padding=1)
+def _assemble_k_grads(grads: Dict[str, torch.Tensor], d_wx: torch.Tensor, d_wq, d_bk) -> None:
+    """The K.i gradients in the reference's [256, 256+576] layout: (dWq_i | layer i's rows of dWx); K.0 has no Wq."""
     d_wx = d_wx.reshape(4, HIDDEN, UNFOLD)
     grads["K.0.0.weight"] = d_wx[0].reshape(HIDDEN, UNFOLD, 1, 1)
     grads["K.0.0.bias"] = d_bk[0]
     for i in (1, 2, 3):
         grads[f"K.{i}.0.weight"] = torch.cat([d_wq[i], d_wx[i]], dim=1).reshape(HIDDEN, HIDDEN + UNFOLD, 1, 1)
         grads[f"K.{i}.0.bias"] = d_bk[i]
-    return d_feat
 
 
 PLANE_TILE = 32
@@ -425,7 +408,7 @@ def _geometry(b: int, h: int, w: int, hu: int, wu: int, dev) -> dict:
 def _sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[groups, nparts, n] -> [groups, n]: the split partials of a GEMM / rowdot launch added in slice order (sum_parts_kernel)."""
     groups, nparts, n = part.shape
-    if n % 4 or not part.is_contiguous() or not NATIVE_SUM_PARTS:
+    if n % 4 or not part.is_contiguous():
         return part.sum(1)
     out = torch.empty((groups, n), dtype=torch.float32, device=part.device)
     with torch.cuda.device(part.device):
@@ -438,12 +421,12 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
                    packed: torch.Tensor, size: Sequence[int],
                    need_feat_grad: bool = True) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """The same gradients as ``backward_from_saved``, on the HIP kernels throughout:
-      diinn_backward_data   bwd_head_kernel + 3 x bwd_layer_kernel: the per-pixel chain; leaves the gate
-                            gradients G_i = (g_a,i ; g_s,i) and the activations q_i as tiled planes
+      diinn_backward_data   3 x bwd_layer_kernel (the head's gates inside layer 3's): the per-pixel chain; leaves the
+                            gate gradients G_i = (g_a,i ; g_s,i) and the activations q_i as tiled planes
       diinn_plane_gemm_nt   [dWq_i ; dQw_i | bias sums] = G_i [512 x N] . q_{i-1}^T [N x 256], split over pixels
       diinn_plane_rowdot    the two skinny products (layer 0 against (rel_h, rel_w, ratio, 1); head against g_out)
-      diinn_backward_cell_sum   dP = per-cell sums of g_a
-    and the 3x3 convolution's input/weight gradients from MIOpen (torch.nn.grad).
+      diinn_backward_cell_sum   dP = per-cell sums of g_a, NCHW and tiled over the cell axis
+      _conv_grads_native    the 3x3 convolution's weight gradient (unfold + plane GEMM) and input gradient (encoder conv kernels)
     ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward."""
     lib = _native.load()
     p = dict(zip(PARAM_NAMES, params))
@@ -469,10 +452,8 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     # the hoisted conv's weight gradient on the library's own GEMM wants dP tiled over the cell axis as well: cell_sum_kernel
     # writes it (a ragged last tile's padding must be zero: the GEMM reads whole tiles)
     cells = b * h * w
-    a_t = None
-    if NATIVE_CONV_WGRAD:
-        a_t = (torch.empty if cells % PLANE_TILE == 0 else torch.zeros)(((cells + PLANE_TILE - 1) // PLANE_TILE, 4 * HIDDEN, PLANE_TILE),
-                                                                        dtype=torch.float32, device=dev)
+    a_t = (torch.empty if cells % PLANE_TILE == 0 else torch.zeros)(((cells + PLANE_TILE - 1) // PLANE_TILE, 4 * HIDDEN, PLANE_TILE),
+                                                                    dtype=torch.float32, device=dev)
     ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -486,8 +467,8 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
                       "diinn_plane_rowdot")
         _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(gout_t), ptr(partl), HIDDEN, n, rsplit),
                       "diinn_plane_rowdot")
-        _native.check(lib.diinn_backward_cell_sum_ex(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t) if a_t is not None else None,
-                                                     b, h, w, hu, wu), "diinn_backward_cell_sum_ex")
+        _native.check(lib.diinn_backward_cell_sum(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t), b, h, w, hu, wu),
+                      "diinn_backward_cell_sum")
     grads: Dict[str, torch.Tensor] = {}
     dl = _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: q_3 . (g_out ; 0)^T
     grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
@@ -505,7 +486,10 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     d_bk[0] = d0[:HIDDEN, 3]
     grads["Q.0.0.weight"] = d0[HIDDEN:, :3].reshape(HIDDEN, 3, 1, 1)
     grads["Q.0.0.bias"] = d0[HIDDEN:, 3]
-    d_feat = _conv_and_assemble(p, feat, dp, d_wq, d_bk, grads, need_feat_grad, native=(NATIVE_CONV_WGRAD, NATIVE_CONV_DGRAD), a_t=a_t)
+    kw = tuple(p[f"K.{i}.0.weight"] for i in range(4))
+    d_wx, d_feat = _conv_grads_native(feat, _hoisted_conv_weight(p), dp, need_feat_grad, wkey=tuple((t.data_ptr(), t._version) for t in kw),
+                                      wpins=kw, a_t=a_t)
+    _assemble_k_grads(grads, d_wx, d_wq, d_bk)
     return d_feat, [grads[name] for name in PARAM_NAMES]
 
 
@@ -536,11 +520,9 @@ class DecodeMode3Function(torch.autograd.Function):
         out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            # the hoisted conv: the Winograd kernel when the image carries its section (DIINN_PACKED_MAGIC_WPU: _fill_wpu), else
-            # the direct kernel, which reads permutation sections only
-            p_fn = lib.diinn_precompute_P_wpu if TRAIN_P_WINOGRAD else lib.diinn_precompute_P
-            _native.check(p_fn(stream, C.c_void_p(feat_c.data_ptr()), C.c_void_p(packed.data_ptr()),
-                               C.c_void_p(workspace.data_ptr()), b, h, w, 0, h), "diinn_precompute_P")
+            # the hoisted conv on the Winograd kernel: the image carries its section (DIINN_PACKED_MAGIC_WPU: _fill_wpu)
+            _native.check(lib.diinn_precompute_P_wpu(stream, C.c_void_p(feat_c.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                                     C.c_void_p(workspace.data_ptr()), b, h, w, 0, h), "diinn_precompute_P_wpu")
             _native.check(lib.diinn_decode_train_fwd(stream, C.c_void_p(workspace.data_ptr()),
                                                      C.c_void_p(packed.data_ptr()), C.c_void_p(out.data_ptr()),
                                                      C.c_void_p(acts.data_ptr()), b, h, w, hu, wu, int(sin_mode)),

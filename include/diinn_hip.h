@@ -31,10 +31,11 @@
 extern "C" {
 #endif
 
-#define DIINN_ABI_VERSION 10
-/* What each ABI number added: INTEGRATION.md, "ABI history".  v10 (this header): the four one-algorithm trunk entry points of
+#define DIINN_ABI_VERSION 11
+/* What each ABI number added: INTEGRATION.md, "ABI history".  v10: the four one-algorithm trunk entry points of
  * ABI <= 8 and their two workspace-size queries are removed; diinn_rdn_forward_ex(algo, ...) is the trunk's only entry point, its
- * buffers sized by diinn_rdn_planes_floats and diinn_conv_wino4_workspace_floats. */
+ * buffers sized by diinn_rdn_planes_floats and diinn_conv_wino4_workspace_floats.  v11 (this header): diinn_backward_cell_sum
+ * takes dP_tiled_dev (may be NULL); the v9 entry point of that signature, its name suffixed _ex, is removed. */
 
 /* status codes */
 #define DIINN_OK                 0
@@ -338,16 +339,14 @@ int diinn_sum_parts(void* stream, const float* part_dev, float* out_dev, int gro
  * nearest LR cell is (cy, cx): the adjoint of the nearest-exact replication of diinn.py:168, i.e. the
  * gradient at the hoisted 3x3 convolution's output, NCHW [B][1024][H][W].  seg_h_dev [H+1] / seg_w_dev
  * [W+1] (int32, device) give the first HR row / column of every LR row / column (last entry Hu / Wu);
- * the index tables are monotone, so a cell's pixels form a rectangle.  Deterministic (no atomics). */
+ * the index tables are monotone, so a cell's pixels form a rectangle.  Deterministic (no atomics).
+ * dP_tiled_dev (may be NULL) additionally receives the same sums as a tiled plane group over the CELL axis,
+ * [ceil(B H W / 32)][1024][32]: the A operand of the hoisted conv's weight-gradient GEMM, dWx^T [576(+64) x 1024] =
+ * unfold . dP^T (diinn_plane_gemm_nt).  Its B operand diinn_unfold_tiled writes: the reference's F.unfold(feat, 3, padding=1)
+ * (diinn.py:168; row = c * 9 + ky * 3 + kx) as a tiled group [ceil(B H W / 32)][rows][32], rows >= 576, the rows past 576 zero.
+ * With these two the decoder's training step has no library convolution left (sr_module.py:127-137). */
 int diinn_backward_cell_sum(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
-                            float* dP_dev, int B, int H, int W, int Hu, int Wu);
-/* _ex: additionally (dP_tiled_dev non-NULL) the same sums as a tiled plane group over the CELL axis, [ceil(B H W / 32)][1024][32]:
- * the A operand of the hoisted conv's weight-gradient GEMM, dWx^T [576(+64) x 1024] = unfold . dP^T (diinn_plane_gemm_nt), whose
- * B operand diinn_unfold_tiled writes: the reference's F.unfold(feat, 3, padding=1) (diinn.py:168; row = c * 9 + ky * 3 + kx) as a
- * tiled group [ceil(B H W / 32)][rows][32], rows >= 576, the rows past 576 zero.  With these two the decoder's training step has
- * no library convolution left (sr_module.py:127-137). */
-int diinn_backward_cell_sum_ex(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
-                               float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu);
+                            float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu);
 int diinn_unfold_tiled(void* stream, const float* feat_dev, float* out_tiled_dev, int rows, int B, int H, int W);
 
 /* ---- LIIF comparison decoder ------------------------

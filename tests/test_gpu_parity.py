@@ -943,7 +943,7 @@ def test_image_without_derived_sections_is_refused(dev):
     off, size = C.c_size_t(), C.c_size_t()
     N.check(lib.diinn_packed_section(6, C.byref(off), C.byref(size)), "section")
     word = off.value + 3
-    assert gathered[word:word + 1].view(torch.int32).item() == (N.PACKED_MAGIC_WPU if T.TRAIN_P_WINOGRAD else 0)
+    assert gathered[word:word + 1].view(torch.int32).item() == N.PACKED_MAGIC_WPU
     assert host[word:word + 1].view(torch.int32).item() == N.PACKED_MAGIC
     feat = torch.from_numpy(synth.encoder_features(5, 1, 24, 20)).to(dev)
     good = D.decode_features(feat, host, (79, 66))

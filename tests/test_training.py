@@ -334,9 +334,9 @@ def test_cell_sum_and_unfold_kernels():
         cells = b * h * w
         tc = (cells + 31) // 32
         dp_t = torch.zeros((tc, 1024, 32), device=dev)
-        N.check(lib.diinn_backward_cell_sum_ex(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), ptr(dp), ptr(dp_t), b, h, w, hu, wu), "cell_sum")
+        N.check(lib.diinn_backward_cell_sum(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), ptr(dp), ptr(dp_t), b, h, w, hu, wu), "cell_sum")
         dp2 = torch.full((b, 1024, h, w), float("nan"), device=dev)
-        N.check(lib.diinn_backward_cell_sum(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), ptr(dp2), b, h, w, hu, wu), "cell_sum")
+        N.check(lib.diinn_backward_cell_sum(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), ptr(dp2), None, b, h, w, hu, wu), "cell_sum")
         torch.cuda.synchronize()
         assert torch.equal(dp, dp2)
         ga = T.untile_planes(g_t, n)[:, :256].reshape(1024, n)                       # g_a rows of the four layers
@@ -350,7 +350,7 @@ def test_cell_sum_and_unfold_kernels():
         assert torch.equal(u_t, T.tile_planes(torch.cat([unf, unf.new_zeros((64, cells))], 0)))
     assert lib.diinn_unfold_tiled(stream, ptr(feat), ptr(u_t), 100, b, h, w) == N.ERR_INVALID_ARG
     assert lib.diinn_unfold_tiled(stream, None, ptr(u_t), 640, b, h, w) == N.ERR_INVALID_ARG
-    assert lib.diinn_backward_cell_sum_ex(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), None, None, b, h, w, hu, wu) == N.ERR_INVALID_ARG
+    assert lib.diinn_backward_cell_sum(stream, ptr(g_t), ptr(geo["seg_h"]), ptr(geo["seg_w"]), None, None, b, h, w, hu, wu) == N.ERR_INVALID_ARG
 
 
 @pytest.mark.gpu
