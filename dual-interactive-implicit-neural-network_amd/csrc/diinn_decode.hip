@@ -14,7 +14,8 @@
 //                         B-operand layout of the next (diinn_layout.h), so activations
 //                         never touch LDS or HBM.  Weights stream from the packed image.
 //                         <KPART=false>: decoder modes 1/2 (with cell_chain_kernel);
-//                         <SAVE>: training forward, also writes k_i, s_i as tiled planes;
+//                         <SAVE>: training forward, also writes k_i, s_i as tiled planes (with KPART=false: the modes-1/2
+//                         training forward, k_i of the pixel's cell replicated per pixel);
 //                         <HEAD3>: decoder mode 4, the head is the 27 per-pixel tap values of the 3x3 conv
 //   head3x3_reflect_kernel : decoder mode 4, the reflect-padded 9-point gather over the tap buffer
 //   decode_bf16_kernel, decode_bf16x2_kernel : bf16 operands in layers 1..3 (optional paths)
@@ -965,8 +966,9 @@ int diinn_decode_tile_win(void* stream, const float* P_win_dev, int p_row0, int 
                             OutView{y0, y1 > y0 ? y1 - y0 : 1, x0, out_batch_stride, out_plane_stride, out_row_stride});
 }
 
-int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
-                           float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+// The training forward, KPART = true (mode 3) or false (modes 1/2: P_dev holds the per-cell chain, diinn_cell_chain)
+static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
+                          float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode, bool kpart) {
     if (!P_dev || !packed_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -991,6 +993,15 @@ int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed
     const int small = diinn_uses_small_output_kernel(Hu, Wu);
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
+    if (!kpart) {
+        if (sin_mode == DIINN_SIN_HW)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (sin_mode == DIINN_SIN_HW_REDUCED)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        return hip_status(hipGetLastError());
+    }
     if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
@@ -998,6 +1009,16 @@ int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed
     else
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
+}
+
+int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
+                           float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true);
+}
+
+int diinn_decode_train_fwd_qonly(void* stream, const float* chain_dev, const float* packed_dev, float* out_dev,
+                                 float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    return train_fwd_impl(stream, chain_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, false);
 }
 
 int diinn_decode(void* stream, const float* feat_dev, const float* packed_dev,

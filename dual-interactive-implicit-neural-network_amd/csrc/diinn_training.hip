@@ -15,6 +15,7 @@
 //                    (the rows are read in accumulator order, so no shuffle is needed), streams the
 //                    transposed weights (WLT section) exactly like the forward kernel streams WL, and
 //                    its epilogue applies the gates of layer i-1 and writes G_{i-1} and q_{i-1}.
+// bwd_layer_kernel<., KPART=false> + cell_chain_bwd_kernel : decoder modes 1 and 2 (the modulation chain lives on the LR cells).
 // plane_gemm_lds_kernel / plane_rowdot_kernel : the parameter gradients, GEMMs over the pixel axis of the
 //                    planes written here (dW_i = G_i q_{i-1}^T ...).
 // All planes are tiled (see PLANE_TILE above): acts, G [4][ntiles][512][32]; Q [4][ntiles][256][32].
@@ -88,7 +89,13 @@ __global__ __launch_bounds__(256) void bwd_head_kernel(const BwdParams p) {
 // back (1.2 GB): the loads that fetched G_3's groups fetch (k_3, s_3) instead, a group is turned into (g_a,3 ; g_s,3) right before
 // its first MFMAs and stored from there (G_3 and q_3 are still needed: the weight-gradient GEMM, the cell sums, dL).  Same
 // formulas in the same order as bwd_head_kernel: bit-identical planes.
-template <bool HEAD>
+//
+// KPART = false (decoder modes 1 and 2, diinn.py:116-131): the modulation branch does not see q, so g_q,i-1 = Qw_i^T g_s,i alone --
+// the B operand is g_s,i only and only the synthesis pieces of the WLT stream are fetched: half the MFMAs, half the weight stream,
+// half the operand loads.  The gates of layer i-1 are the same (g_a then is the gradient at k_i's pre-activation BEFORE the per-cell
+// chain: cell_chain_bwd_kernel finishes it), so G_{i-1} and q_{i-1} leave in the same planes.  Every KPART branch is `if constexpr`
+// on code that KPART = true keeps whole: those instantiations compile as before.
+template <bool HEAD, bool KPART = true>
 __global__ __launch_bounds__(256, 1) void bwd_layer_kernel(const BwdParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -122,7 +129,7 @@ __global__ __launch_bounds__(256, 1) void bwd_layer_kernel(const BwdParams p) {
         for (int e = 0; e < 4; ++e) {
             const int kk = 4 * kg + e;
             const unsigned so = (unsigned)(32 * (kk >> 4) + (kk & 3) + 8 * ((kk & 15) >> 2)) * PLANE_ROW_BYTES;
-            ga[kk] = ld_plane(HEAD ? act_li : inG, voff, so);
+            if constexpr (HEAD || KPART) ga[kk] = ld_plane(HEAD ? act_li : inG, voff, so);   // (KPART = false: g_a,i is no operand)
             gs[kk] = ld_plane(HEAD ? act_li : inG, voff, so + HID * PLANE_ROW_BYTES);
         }
     };
@@ -175,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void bwd_layer_kernel(const BwdParams p) {
     f32x4 rk[PF], rq[PF];
 #pragma unroll
     for (int d = 0; d < PF; ++d) {
-        rk[d] = ld_piece(wrs, lane_off, wp + (2 * d + 0) * PIECE_BYTES);
+        if constexpr (KPART) rk[d] = ld_piece(wrs, lane_off, wp + (2 * d + 0) * PIECE_BYTES);
         rq[d] = ld_piece(wrs, lane_off, wp + (2 * d + 1) * PIECE_BYTES);
     }
 
@@ -199,18 +206,23 @@ __global__ __launch_bounds__(256, 1) void bwd_layer_kernel(const BwdParams p) {
 #pragma unroll
         for (int kg = 0; kg < WL_KG; ++kg) {
             const int s = m * WL_KG + kg;
-            const f32x4 wk = rk[s % PF];
             const f32x4 wq = rq[s % PF];
             if constexpr (HEAD) {
                 if (m == 0) head_group(kg);                       // (its loads went out BLD groups = 64 MFMAs ago)
                 if (m == 1) head_store_group(kg);                 // 8 stores behind 8 MFMAs (in M-tile 0 they would sit beside the
             }                                                     // group's 8 loads, ~76 VALU instructions and 4 q_3 stores)
+            if constexpr (KPART) {
+                const f32x4 wk = rk[s % PF];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                ak = MFMA32(wk[e], ga[4 * kg + e], ak);
-                as = MFMA32(wq[e], gs[4 * kg + e], as);
+                for (int e = 0; e < 4; ++e) {
+                    ak = MFMA32(wk[e], ga[4 * kg + e], ak);
+                    as = MFMA32(wq[e], gs[4 * kg + e], as);
+                }
+                rk[s % PF] = ld_piece(wrs, lane_off, wp + (2 * (s + PF) + 0) * PIECE_BYTES);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) as = MFMA32(wq[e], gs[4 * kg + e], as);
             }
-            rk[s % PF] = ld_piece(wrs, lane_off, wp + (2 * (s + PF) + 0) * PIECE_BYTES);
             rq[s % PF] = ld_piece(wrs, lane_off, wp + (2 * (s + PF) + 1) * PIECE_BYTES);
             if (m == 0 && kg + BLD < WL_KG) load_group(kg + BLD); // rest of the B operand, BLD groups ahead
             if (m > 0 && kg == 0) {                               // saved planes of tile m-1, used from kg = 8 on
@@ -227,7 +239,7 @@ __global__ __launch_bounds__(256, 1) void bwd_layer_kernel(const BwdParams p) {
             }
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pg[r] = ak[r] + as[r];
+        for (int r = 0; r < 16; ++r) pg[r] = KPART ? ak[r] + as[r] : as[r];
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -313,6 +325,113 @@ __global__ __launch_bounds__(256) void cell_sum_kernel(const CellSumParams p) {
     if (p.dP_tiled) {
         const long long n = (long long)b * p.H * p.W + cell;
         p.dP_tiled[((size_t)(n >> 5) * PCH + plane) * PLANE_TILE + (size_t)(n & 31)] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// cell_chain_bwd_kernel (training backward, decoder modes 1 and 2): cell_chain_kernel's scheme run backwards.
+// In those modes the modulation chain lives on the LR cells, k_0 = relu(P_0), k_i = relu(Kk_i k_{i-1} + P_i) (diinn.py:116-131),
+// and the per-pixel backward leaves, per cell, S_i = sum over the cell's pixels of g_q,i sin(s_i) [k_i > 0] (cell_sum_kernel).
+// The gradient at the chain's pre-activations is then
+//     g_a,3 = S_3,      g_a,i-1 = [k_{i-1} > 0] (Kk_i^T g_a,i) + S_{i-1},      dP_i = g_a,i.
+// A wave owns one tile of 32 consecutive flattened cells (b, cy, cx) and keeps their 256-channel g_a,i in registers as the MFMA B
+// operand (the accumulator of one layer IS the operand of the next, diinn_layout.h); it streams the modulation pieces (part 0) of
+// the transposed section WLT, which hold Kk_i^T in every packed image.  The mask is the sign of the chain workspace's slot i-1
+// (slots 1..3 hold k_i, slot 0 the pre-activation P_0: cell_chain_kernel).  S is read as the tiled group cell_sum_kernel writes; dP
+// leaves in both of that kernel's layouts -- NCHW for the conv's input gradient, tiled over cells for the weight-gradient GEMMs --
+// and the tiled output may BE the S buffer (a wave reads a row of its tile before it writes it; no other wave touches the tile).
+// k_tiled (optional): k_0..k_2 as a tiled group [tiles][768][32] over cells, the B operand of dKk_i = g_a,i k_{i-1}^T
+// (diinn_plane_gemm_nt), written from the values the mask is read from.  Lanes past the last cell read zeros and store nothing.
+// ---------------------------------------------------------------------------------
+struct ChainBwdParams {
+    const float* S;          // tiled over cells [ntiles][1024][32], rows 256 i + ch = S_i
+    const float* ws;         // chain workspace [cells][1024]
+    const float* Wt;         // packed image
+    float* dP;               // [B][1024][H][W]
+    float* dP_tiled;         // [ntiles][1024][32]
+    float* k_tiled;          // optional: [ntiles][768][32]
+    long long cells, ntiles;
+    int HW;
+};
+
+__global__ __launch_bounds__(256, 1) void cell_chain_bwd_kernel(const ChainBwdParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31;
+    const long long tile = (long long)blockIdx.x * 4 + wave;
+    if (tile >= p.ntiles) return;                                // wave-uniform
+    const long long cell = tile * PLANE_TILE + j;
+    const bool valid = cell < p.cells;
+    const long long cc = valid ? cell : p.cells - 1;            // lanes past the end read the last cell's mask (and store nothing)
+    const unsigned voff = valid ? 4u * j + 4u * h * PLANE_ROW_BYTES : 0xFFFFFFF0u;
+    const __amdgpu_buffer_rsrc_t inS = tile_rsrc(p.S, tile, PCH);
+    const __amdgpu_buffer_rsrc_t outT = tile_rsrc(p.dP_tiled, tile, PCH);
+    const bool emit_k = p.k_tiled != nullptr;                    // wave-uniform
+    const __amdgpu_buffer_rsrc_t outK = tile_rsrc(emit_k ? p.k_tiled : p.dP_tiled, tile, 3 * HID);
+    const float* __restrict__ Wc = p.ws + (size_t)cc * PCH + 4 * h;
+    const long long bi = cc / p.HW;
+    float* const dN = p.dP + ((size_t)bi * PCH + 4 * h) * p.HW + (size_t)(cc - bi * p.HW);   // plane 4 h of this lane's cell
+    // element (plane 256 i + chan_of(kk, h)) of this lane's cell, both layouts
+    auto put = [&](int i, int kk, float v) {
+        const int row = i * HID + 32 * (kk >> 4) + (kk & 3) + 8 * ((kk & 15) >> 2);      // + 4 h: in voff / dN
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), outT, (int)voff, (int)((unsigned)row * PLANE_ROW_BYTES), 0);
+        if (valid) dN[(size_t)row * p.HW] = v;
+    };
+
+    float ga[128];
+#pragma unroll
+    for (int kk = 0; kk < 128; ++kk) {
+        const unsigned so = (unsigned)(3 * HID + 32 * (kk >> 4) + (kk & 3) + 8 * ((kk & 15) >> 2)) * PLANE_ROW_BYTES;
+        ga[kk] = ld_act(inS, voff, so);
+    }
+#pragma unroll
+    for (int kk = 0; kk < 128; ++kk) put(3, kk, ga[kk]);        // dP_3 = S_3
+
+    constexpr int PF = DECODE_PREFETCH;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);   // reads past the end return 0
+    const int lane_off = lane * 16;
+#pragma unroll 1
+    for (int li = 3; li >= 1; --li) {
+        const int wp = (int)((OFF_WLT + (size_t)(li - 1) * WL_LAYER) * sizeof(float));
+        f32x4 rk[PF];
+#pragma unroll
+        for (int d = 0; d < PF; ++d) rk[d] = ld_piece(wrs, lane_off, wp + (2 * d) * PIECE_BYTES);
+        const float* __restrict__ Wl = Wc + (li - 1) * HID;      // slot li-1: k_{li-1} (P_0 for li = 1)
+        float gn[128];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            f32x4 kv[4];
+            float sv[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) kv[g] = *(const f32x4*)(Wl + 32 * m + 8 * g);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                sv[r] = ld_act(inS, voff, (unsigned)((li - 1) * HID + 32 * m + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES);
+            f32x16 ak;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ak[r] = 0.0f;
+#pragma unroll
+            for (int kg = 0; kg < WL_KG; ++kg) {
+                const int s = m * WL_KG + kg;
+                const f32x4 wk = rk[s % PF];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ak = MFMA32(wk[e], ga[4 * kg + e], ak);
+                rk[s % PF] = ld_piece(wrs, lane_off, wp + (2 * (s + PF)) * PIECE_BYTES);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float kvr = kv[r >> 2][r & 3];
+                const float v = (kvr > 0.0f ? ak[r] : 0.0f) + sv[r];
+                gn[16 * m + r] = v;
+                put(li - 1, 16 * m + r, v);
+                if (emit_k)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, relu0(kvr)), outK, (int)voff,
+                                                          (int)((unsigned)((li - 1) * HID + 32 * m + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES), 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 128; ++i) ga[i] = gn[i];
     }
 }
 
@@ -634,6 +753,41 @@ int diinn_sum_parts(void* stream, const float* part_dev, float* out_dev, int gro
 long long diinn_training_plane_floats(long long npix, int rows) {
     if (npix <= 0 || rows <= 0 || npix > DIINN_TRAIN_MAX_PIXELS) return -1;
     return (npix + PLANE_TILE - 1) / PLANE_TILE * rows * PLANE_TILE;
+}
+
+int diinn_backward_data_qonly(void* stream, const float* gout_planes_dev, const float* acts_dev,
+                              const float* packed_dev, float* G_dev, float* Q_dev, long long npix) {
+    if (!gout_planes_dev || !acts_dev || !packed_dev || !G_dev || !Q_dev) return DIINN_ERR_INVALID_ARG;
+    const int stp = check_npix(npix);
+    if (stp) return stp;
+    BwdParams p;
+    p.Wt = packed_dev; p.acts = acts_dev; p.gout = gout_planes_dev; p.G = G_dev; p.Q = Q_dev;
+    p.npix = npix; p.ntiles = (npix + PLANE_TILE - 1) / PLANE_TILE; p.layer = 0;
+    const unsigned blocks = (unsigned)((p.ntiles + 3) / 4);
+    for (int layer = 3; layer >= 1; --layer) {
+        p.layer = layer;
+        if (layer == 3) hipLaunchKernelGGL((bwd_layer_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((bwd_layer_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_status(e);
+    }
+    return DIINN_OK;
+}
+
+int diinn_cell_chain_bwd(void* stream, const float* S_tiled_dev, const float* chain_dev, const float* packed_dev,
+                         float* dP_dev, float* dP_tiled_dev, float* k_tiled_dev, int B, int H, int W) {
+    if (!S_tiled_dev || !chain_dev || !packed_dev || !dP_dev || !dP_tiled_dev) return DIINN_ERR_INVALID_ARG;
+    const int st = check_dims(B, H, W);
+    if (st) return st;
+    if ((long long)H * W > 2147483000LL) return DIINN_ERR_TOO_LARGE;
+    if ((((size_t)S_tiled_dev) | ((size_t)chain_dev) | ((size_t)packed_dev) | ((size_t)dP_tiled_dev) | ((size_t)k_tiled_dev)) & 15)
+        return DIINN_ERR_INVALID_ARG;                            // 16-byte loads of the mask and the weight pieces
+    const long long cells = (long long)B * H * W;
+    const long long ntiles = (cells + PLANE_TILE - 1) / PLANE_TILE;
+    if ((ntiles + 3) / 4 > 2147483000LL) return DIINN_ERR_TOO_LARGE;
+    ChainBwdParams p{S_tiled_dev, chain_dev, packed_dev, dP_dev, dP_tiled_dev, k_tiled_dev, cells, ntiles, H * W};
+    hipLaunchKernelGGL(cell_chain_bwd_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
 }
 
 int diinn_backward_data(void* stream, const float* gout_planes_dev, const float* acts_dev,

@@ -11,7 +11,7 @@ Mirrors /root/reference/src/models/components/diinn.py:
 The compute is the HIP path and only the HIP path: CPU tensors, a missing
 library or decoder variants the kernels do not cover raise instead of silently
 falling back.  PyTorch is used for device memory and the stream; under autograd
-(training, mode 3) the forward is the HIP kernel with saved activations and the
+(training, modes 1-3, fp32) the forward is the HIP kernel with saved activations and the
 backward is library GEMMs over those (training.py).
 """
 from __future__ import annotations
@@ -540,10 +540,10 @@ class ImplicitDecoder(nn.Module):
             x.requires_grad or any(p.requires_grad for p in self.parameters()))
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
-        if wants_grad and (self.mode != 3 or self.compute != "f32"):
+        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32"):
             raise NotImplementedError(
-                "diinn_amd: autograd through the HIP decode path covers mode 3 in fp32 (the reference's final "
-                "model); call modes 1/2/4 or the bf16 path under torch.no_grad()")
+                "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 (mode 3 is the reference's "
+                "final model, modes 1/2 its ablations); call mode 4 or the bf16 path under torch.no_grad()")
         _require_cuda(x, "x")
         if wants_grad:
             from .training import decode_with_grad

@@ -1,4 +1,4 @@
-"""Training path of the mode-3 decoder: autograd through the HIP kernels.
+"""Training path of the decoder, modes 1-3: autograd through the HIP kernels.
 
 The reference trains by calling ``ImplicitDecoder.forward(x, size, bsize=None)`` with autograd on
 (diinn.py:170-171 -> step(), :132-139; caller SRLitModule.training_step, sr_module.py:127-129), which
@@ -19,6 +19,11 @@ records ~30 ATen ops per call on the materialised [B,576,Hu,Wu] tensor.  Here:
             conv's from torch.nn.grad); it is the unit-tested formula sheet (CPU, against the
             reference's own .grad fixtures) and the on-GPU cross-check of the fused path.  The forward
             has no CPU form.
+
+Modes 1 and 2 (diinn.py:116-131; the paper's ablations): the modulation chain k_i depends on the LR cell only, so the forward is
+precompute_P, cell_chain_kernel, decode_kernel<KPART=false, SAVE> (``diinn_decode_train_fwd_qonly``) and the backward is the
+per-pixel chain without its modulation half (``diinn_backward_data_qonly``), the cell sums, then cell_chain_kernel's scheme run
+backwards (``diinn_cell_chain_bwd``): ``backward_fused_modes12``, with ``backward_from_saved_modes12`` as its formula sheet.
 
 Weights change every optimiser step, so the packed image is rebuilt on the device each forward by one
 gather through a permutation index derived once from the host packer (``pack_gather_index``).
@@ -53,32 +58,50 @@ PARAM_SHAPES: Dict[str, Tuple[int, ...]] = {
     "last_layer.weight": (3, HIDDEN, 1, 1), "last_layer.bias": (3,),
 }
 
+
+
+def param_shapes(mode: int = 3) -> Dict[str, Tuple[int, ...]]:
+    """PARAM_SHAPES for decoder ``mode``: modes 2 and 3 share them; mode 1's K.1..3 see k alone, [256,256,1,1] (diinn.py:53-60)."""
+    if mode != 1:
+        return PARAM_SHAPES
+    return {**PARAM_SHAPES, **{f"K.{i}.0.weight": (HIDDEN, HIDDEN, 1, 1) for i in (1, 2, 3)}}
+
+
 # backward_fused calls no framework convolution, GEMM or reduction of partials: the A/B runs that settled that are in DESIGN_HISTORY.md.
 WGRAD_KSPLIT = 64          # pixel-axis splits of the weight-gradient GEMM: 4 output blocks x 64 = one workgroup per CU
 ROWDOT_SPLITS = 1024       # workgroups of the skinny products (HBM-bound)
 
-_gather_index_cpu: Optional[torch.Tensor] = None
-_gather_index_dev: Dict[str, torch.Tensor] = {}
+_gather_index_cpu: Dict[int, torch.Tensor] = {}          # keyed by weight layout: 1 (mode 1) or 3 (modes 2 and 3)
+_gather_index_dev: Dict[tuple, torch.Tensor] = {}
 
 
-def pack_gather_index() -> torch.Tensor:
+def _layout(mode: int) -> int:
+    if mode not in (1, 2, 3):
+        raise ValueError(f"the training path covers decoder modes 1-3, got {mode}")
+    return 1 if mode == 1 else 3
+
+
+def pack_gather_index(mode: int = 3) -> torch.Tensor:
     """int64 [packed floats]: packed[i] = flat[index[i]] where ``flat`` is the 18 reference tensors
     flattened in PARAM_NAMES order followed by one 0.0 (padding and the bf16 section point at it).
-    Derived by packing a state dict whose values are their own flat position (exact in fp32)."""
-    global _gather_index_cpu
-    if _gather_index_cpu is not None:
-        return _gather_index_cpu
+    Derived by packing a state dict whose values are their own flat position (exact in fp32).
+    Mode 1 (K.1..3 are [256,256]): the feature columns the host packer widens them with are zeros, so
+    those places -- layers 1..3 of the hoisted conv -- point at the appended zero as well."""
+    layout = _layout(mode)
+    if layout in _gather_index_cpu:
+        return _gather_index_cpu[layout]
     from .decoder import pack_state_dict
     lib = _native.load()
+    shapes = param_shapes(layout)
     sd = {}
     pos = 1
     for name in PARAM_NAMES:
-        n = int(np.prod(PARAM_SHAPES[name]))
-        sd[name] = np.arange(pos, pos + n, dtype=np.float32).reshape(PARAM_SHAPES[name])
+        n = int(np.prod(shapes[name]))
+        sd[name] = np.arange(pos, pos + n, dtype=np.float32).reshape(shapes[name])
         pos += n
     total = pos - 1
     assert total < (1 << 24)
-    packed = pack_state_dict(sd, mode=3).numpy()
+    packed = pack_state_dict(sd, mode=layout).numpy()
     idx = np.rint(packed).astype(np.int64) - 1
     off, size = C.c_size_t(), C.c_size_t()
     for section in (7, 9, 10, 11, 12, 13, 14, 15, 16):          # inference-only sections: derived values, not a permutation
@@ -95,22 +118,22 @@ def pack_gather_index() -> torch.Tensor:
     if not used.all():
         raise RuntimeError("packed image does not reference every parameter element")
     idx[idx < 0] = total                                # the appended zero
-    _gather_index_cpu = torch.from_numpy(idx)
-    return _gather_index_cpu
+    _gather_index_cpu[layout] = torch.from_numpy(idx)
+    return _gather_index_cpu[layout]
 
 
 _packed_cache: tuple = (None, None, None)          # (key, packed image, the parameter tensors the key describes)
 
 
-def pack_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
+def pack_on_device(params: Sequence[torch.Tensor], mode: int = 3) -> torch.Tensor:
     """Reference-ordered parameter tensors (PARAM_NAMES) on a GPU -> packed image on that GPU.
     The last image is kept while no parameter has been modified (a training step decodes once per
-    scale with the same weights, sr_module.py:116-121)."""
+    scale with the same weights, sr_module.py:116-121).  ``mode`` 1: the tensors have mode 1's shapes."""
     global _packed_cache
-    key = tuple((p.data_ptr(), p._version) for p in params)
+    key = (_layout(mode), *((p.data_ptr(), p._version) for p in params))
     if _packed_cache[0] == key:
         return _packed_cache[1]
-    packed = _pack_on_device(params)
+    packed = _pack_on_device(params, mode)
     # the entry keeps the tensors alive: their addresses cannot be handed to other weights while the key is cached
     _packed_cache = (key, packed, tuple(p.detach() for p in params))
     return packed
@@ -128,20 +151,25 @@ def _section(i: int) -> Tuple[int, int]:
     return _section_cache[i]
 
 
-def _hoisted_conv_weight(p: Dict[str, torch.Tensor]) -> torch.Tensor:
-    """Wx [1024,64,3,3] of P = conv3x3(feat; Wx) + bK: the unfold columns of the four K weights, stacked over the layers."""
-    wx = torch.cat([p["K.0.0.weight"].reshape(HIDDEN, UNFOLD)]
-                   + [p[f"K.{i}.0.weight"].reshape(HIDDEN, HIDDEN + UNFOLD)[:, HIDDEN:] for i in (1, 2, 3)], 0)
+def _hoisted_conv_weight(p: Dict[str, torch.Tensor], mode: int = 3) -> torch.Tensor:
+    """Wx [1024,64,3,3] of P = conv3x3(feat; Wx) + bK: the unfold columns of the four K weights, stacked over the layers.
+    Mode 1: K.1..3 have no feature columns (P_i = bK_i there): Wx is K.0's [256,64,3,3] alone."""
+    k0 = p["K.0.0.weight"].reshape(HIDDEN, UNFOLD)
+    if mode == 1:
+        return k0.reshape(HIDDEN, IN_CHANNELS, 3, 3).contiguous()
+    wx = torch.cat([k0] + [p[f"K.{i}.0.weight"].reshape(HIDDEN, HIDDEN + UNFOLD)[:, HIDDEN:] for i in (1, 2, 3)], 0)
     return wx.reshape(4 * HIDDEN, IN_CHANNELS, 3, 3).contiguous()
 
 
-def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor]) -> None:
+def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor], mode: int = 3) -> None:
     """Section 13 (WPU) of a gathered image, on the device (what diinn_precompute_P_wpu, the training forward's hoisted conv on the
     fp32 Winograd kernel, reads): U = G Wx G^T per (output, input) pair in float64 in the host
     packer's own operation order (csrc/diinn_host.cpp: (G g) first, then (.) G^T, sums left to right), rounded once, column 2
     negated, laid out [mt 32][row i 4][sg 8][col j 4][lane 64][e 4] -- bit-identical to diinn_pack_weights' section -- and
     the validity word DIINN_PACKED_MAGIC_WPU ("this training image holds WPU and nothing else derived")."""
-    w = _hoisted_conv_weight({name: t.detach() for name, t in zip(PARAM_NAMES, params)}).to(torch.float64)
+    w = _hoisted_conv_weight({name: t.detach() for name, t in zip(PARAM_NAMES, params)}, mode).to(torch.float64)
+    if mode == 1:                                                # layers 1..3 of the conv are zero (the host packer's widened K.i)
+        w = torch.cat([w, w.new_zeros((3 * HIDDEN, IN_CHANNELS, 3, 3))], 0)
     g = torch.tensor(_WPU_G, dtype=torch.float64, device=w.device)
     gi = [g[:, a].view(1, 1, 4, 1) for a in range(3)]
     t = gi[0] * w[:, :, 0:1, :] + gi[1] * w[:, :, 1:2, :] + gi[2] * w[:, :, 2:3, :]          # [O, C, i 4, b 3]
@@ -155,16 +183,16 @@ def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor]) -> None:
     packed[word:word + 1].view(torch.int32).fill_(_native.PACKED_MAGIC_WPU)
 
 
-def _pack_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
+def _pack_on_device(params: Sequence[torch.Tensor], mode: int = 3) -> torch.Tensor:
     dev = params[0].device
-    key = str(dev)
+    key = (str(dev), _layout(mode))
     idx = _gather_index_dev.get(key)
     if idx is None:
-        idx = pack_gather_index().to(dev)
+        idx = pack_gather_index(mode).to(dev)
         _gather_index_dev[key] = idx
     flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params] + [torch.zeros(1, device=dev)])
     packed = flat.index_select(0, idx)
-    _fill_wpu(packed, params)
+    _fill_wpu(packed, params, mode)
     return packed
 
 
@@ -269,12 +297,14 @@ WGRAD_CONV_KSPLIT = 12     # pixel-axis splits of the hoisted conv's weight-grad
 
 
 def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, need_feat_grad: bool, want_weight: bool = True,
-                       wkey=None, wpins=None, a_t: Optional[torch.Tensor] = None):
+                       wkey=None, wpins=None, a_t: Optional[torch.Tensor] = None, rows: int = 4 * HIDDEN):
     """Gradients of P = conv3x3(feat; Wx[1024,64,3,3]) on the library's own kernels (no MIOpen in the decoder's step):
       weight:  dWx[o, (c,ky,kx)] = sum over cells of dP[o, cell] * unfold3x3(feat)[(c,ky,kx), cell] -- the plane GEMM over the
                cell axis (plane_gemm_lds_kernel; the 576 unfolded rows padded to 640 = 5 x 128);
       input :  d_feat = conv3x3(dP; Wx transposed and flipped) -- a 64-output 3x3 convolution over 1024 planes, i.e. the
-               encoder's convolution kernels (Winograd F(4x4) / F(2x2) / split-K by the same rule as the trunk)."""
+               encoder's convolution kernels (Winograd F(4x4) / F(2x2) / split-K by the same rule as the trunk).
+    ``rows`` < 1024 (decoder mode 1: 256, only P_0 is a convolution of the features): the conv is Wx[:rows], i.e. the first
+    ``rows`` planes of ``dp`` [B,1024,H,W] / rows of ``a_t`` are used and ``wx`` is [rows,64,3,3]."""
     from . import modules as M                                   # (pack functions; imported late: modules imports the decoder)
     lib = _native.load()
     b, c, h, w = feat.shape
@@ -296,18 +326,18 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
         # the product is taken transposed, dWx^T [640 x 1024] = unfold . dP^T: with 1024 = 4 x 256 columns it runs on the kernel's
         # 128 x 256 block form (113 TFLOP/s; the 128 x 128 form the 640 columns of dWx would need: 70)
         ks = max(1, min(WGRAD_CONV_KSPLIT, a_t.shape[0]))
-        part = torch.empty((ks, 640, 4 * HIDDEN), dtype=torch.float32, device=dev)
+        part = torch.empty((ks, 640, rows), dtype=torch.float32, device=dev)
     d_feat = None
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if want_weight:
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(b_t), 640, 0, ptr(a_t), 4 * HIDDEN, 0, ptr(part), 640, 4 * HIDDEN, n, ks, 0),
+            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(b_t), 640, 0, ptr(a_t), 4 * HIDDEN, 0, ptr(part), 640, rows, n, ks, 0),
                           "diinn_plane_gemm_nt")
-            d_wx = _sum_parts(part.view(1, ks, -1)).view(640, 4 * HIDDEN)[:UNFOLD].t()
+            d_wx = _sum_parts(part.view(1, ks, -1)).view(640, rows)[:UNFOLD].t()
         if need_feat_grad:
             d_feat = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
             zero = torch.zeros(64, dtype=torch.float32, device=dev)
-            cin = 4 * HIDDEN
+            cin, in_bs = rows, 4 * HIDDEN * h * w                # the planes convolved; the batch stride of dp
             form = "wino4" if lib.diinn_rdn_wino4_applies(b, h, w) else "wino" if n >= 8192 else "ksplit"
             # the transposed weight in the kernel's form: repacked only when a K weight changed (an optimizer step, a
             # load_state_dict), not on every backward call.  The Winograd transforms are taken in float64 and rounded once,
@@ -315,7 +345,7 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
             # One entry per (kernel form, device): a multi-scale step alternates forms without evicting each other.  An entry
             # PINS the weight tensors its key describes (as _packed_cache does): while it is cached their addresses cannot be
             # handed to another decoder's weights with equal version counts.
-            key = (str(dev), wkey)
+            key = (str(dev), wkey, rows)
             ent = _dgrad_pack.get((form, str(dev)))
             if wkey is None or ent is None or ent[0] != key:
                 wt = wx.flip(2, 3).permute(1, 0, 2, 3).contiguous()      # [64, 1024, 3, 3]
@@ -327,13 +357,13 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
             if form == "wino4":
                 ws = _wino4_workspace(dev)                       # (a partly filled last round is split over the input channels)
                 ws[:512].zero_()                                 # the arrival counters, whatever an aborted launch may have left (as the trunk does; never the sticky status word)
-                _native.check(lib.diinn_conv_wino4_ws(stream, ptr(dp), cin * h * w, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
+                _native.check(lib.diinn_conv_wino4_ws(stream, ptr(dp), in_bs, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
                                                       c * h * w, 0, b, h, w, ptr(ws), ws.numel()), "diinn_conv_wino4_ws")
             elif form == "wino":
-                _native.check(lib.diinn_conv_wino(stream, ptr(dp), cin * h * w, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
+                _native.check(lib.diinn_conv_wino(stream, ptr(dp), in_bs, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
                                                   c * h * w, 0, b, h, w), "diinn_conv_wino")
             else:
-                _native.check(lib.diinn_conv_ksplit(stream, ptr(dp), cin * h * w, cin, 9, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
+                _native.check(lib.diinn_conv_ksplit(stream, ptr(dp), in_bs, cin, 9, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
                                                     c * h * w, None, 0, 0, b, h, w), "diinn_conv_ksplit")
     return d_wx, d_feat
 
@@ -494,6 +524,234 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
 
 
 # ---------------------------------------------------------------------------
+# decoder modes 1 and 2 (diinn.py:116-131): the modulation chain lives on the LR cells
+# ---------------------------------------------------------------------------
+def cell_chain_planes(feat: torch.Tensor, params: Sequence[torch.Tensor], mode: int) -> torch.Tensor:
+    """k_i per LR cell, [4, 256, B*H*W] (cell index (b*H + cy)*W + cx), in plain tensor algebra:
+    k_0 = relu(P_0), k_i = relu(Kk_i k_{i-1} + P_i) with P = conv3x3(feat; Wx) + bK (mode 1: P_i = bK_i for i >= 1)."""
+    p = dict(zip(PARAM_NAMES, params))
+    b, _, h, w = feat.shape
+    cells = b * h * w
+    wx = _hoisted_conv_weight(p, mode)
+    conv = torch.nn.functional.conv2d(feat, wx, padding=1).permute(1, 0, 2, 3).reshape(-1, cells)     # [1024 or 256, cells]
+    ks = []
+    k = None
+    for i in range(4):
+        a = p[f"K.{i}.0.bias"].reshape(HIDDEN, 1).expand(HIDDEN, cells)
+        if i == 0 or mode != 1:
+            a = a + conv[i * HIDDEN:(i + 1) * HIDDEN]
+        if i:
+            a = a + p[f"K.{i}.0.weight"].reshape(HIDDEN, -1)[:, :HIDDEN] @ k
+        k = torch.relu(a)
+        ks.append(k)
+    return torch.stack(ks)
+
+
+def backward_from_saved_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor,
+                                params: Sequence[torch.Tensor], size: Sequence[int], mode: int,
+                                need_feat_grad: bool = True, cell_k: Optional[torch.Tensor] = None
+                                ) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+    """Gradients of the mode-1 / mode-2 decoder given d(loss)/d(out): ``backward_from_saved``'s counterpart.
+
+    acts [4,2,256,N]: k_i of the pixel's cell (replicated per pixel) and s_i; params in PARAM_NAMES order with ``mode``'s shapes;
+    cell_k [4,256,B*H*W]: k_i per LR cell (``cell_chain_planes``; recomputed from feat when None -- a cell that owns no
+    HR pixel does not appear in ``acts``).
+
+    With q_i = k_i[cell] * sin(s_i), s_0 = Q0 syn + bQ0, s_i = Qw_i q_{i-1} + bQ_i, k_0 = relu(P_0), k_i = relu(Kk_i k_{i-1} + P_i),
+    Kk_i = K.i.weight[:, :256], out = L q_3 + bL (diinn.py:116-131), per HR pixel (i = 3..0)
+        g_s,i = g_q,i * k_i * cos(s_i)        g^_a,i = g_q,i * sin(s_i) * [k_i > 0]        g_q,i-1 = Qw_i^T g_s,i   (no Wq^T g_a term)
+        dQw_i = g_s,i q_{i-1}^T               dbQ_i = sum over pixels of g_s,i
+    and per LR cell, with S_i = sum over the cell's pixels of g^_a,i:
+        g_a,3 = S_3        g_a,i-1 = [k_{i-1} > 0] * (Kk_i^T g_a,i) + S_{i-1}        dP_i = g_a,i
+        dKk_i = sum over cells of g_a,i k_{i-1}^T        dbK_i = sum over CELLS of g_a,i   (not the pixel sum of g^_a,i)
+    The conv's gradients come from dP: all 1024 rows in mode 2, layer 0's 256 rows in mode 1."""
+    if mode not in (1, 2):
+        raise ValueError("backward_from_saved_modes12 covers decoder modes 1 and 2")
+    p = dict(zip(PARAM_NAMES, params))
+    b, _, h, w = feat.shape
+    hu, wu = int(size[0]), int(size[1])
+    n = b * hu * wu
+    cells = b * h * w
+    dev = gout.device
+    idx_h, rel_h, idx_w, rel_w, ratio = coordinate_tensors(h, w, hu, wu, dev)
+    if cell_k is None:
+        cell_k = cell_chain_planes(feat, params, mode)
+    grads: Dict[str, torch.Tensor] = {}
+
+    g_out = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n)
+    lw = p["last_layer.weight"].reshape(3, HIDDEN)
+    q3 = acts[3, 0] * torch.sin(acts[3, 1])
+    grads["last_layer.weight"] = (g_out @ q3.t()).reshape(3, HIDDEN, 1, 1)
+    grads["last_layer.bias"] = g_out.sum(1)
+    del q3
+    g_q = lw.t() @ g_out                                          # [256, N]
+
+    s_cell: List[Optional[torch.Tensor]] = [None] * 4             # each [256, cells]
+    for i in (3, 2, 1, 0):
+        k, s = acts[i, 0], acts[i, 1]
+        g_a = g_q * torch.sin(s) * (k > 0)
+        g_s = g_q * k * torch.cos(s)
+        s_cell[i] = _cell_sum(g_a, b, hu, wu, h, w, idx_h, idx_w).permute(1, 0, 2, 3).reshape(HIDDEN, cells)
+        if i:
+            q_prev = acts[i - 1, 0] * torch.sin(acts[i - 1, 1])
+            grads[f"Q.{i}.0.weight"] = (g_s @ q_prev.t()).reshape(HIDDEN, HIDDEN, 1, 1)
+            grads[f"Q.{i}.0.bias"] = g_s.sum(1)
+            g_q = p[f"Q.{i}.0.weight"].reshape(HIDDEN, HIDDEN).t() @ g_s
+        else:
+            # syn = (rel_h, rel_w, ratio) per pixel (diinn.py:165-167): dQ0 = g_s syn^T without materialising syn
+            g_s4 = g_s.view(HIDDEN, b, hu, wu)
+            d_q0 = torch.stack([(g_s4.sum((1, 3)) * rel_h).sum(1), (g_s4.sum((1, 2)) * rel_w).sum(1),
+                                g_s4.sum((1, 2, 3)) * ratio], dim=1)
+            grads["Q.0.0.weight"] = d_q0.reshape(HIDDEN, 3, 1, 1)
+            grads["Q.0.0.bias"] = g_s.sum(1)
+    del g_a, g_s, g_q
+
+    d_p: List[Optional[torch.Tensor]] = [None] * 4                # each [256, cells]
+    d_kk: List[Optional[torch.Tensor]] = [None] * 4
+    g_a = s_cell[3]
+    d_p[3] = g_a
+    for i in (3, 2, 1):
+        kk = p[f"K.{i}.0.weight"].reshape(HIDDEN, -1)[:, :HIDDEN]
+        d_kk[i] = g_a @ cell_k[i - 1].t()
+        g_a = (cell_k[i - 1] > 0) * (kk.t() @ g_a) + s_cell[i - 1]
+        d_p[i - 1] = g_a
+    dp = torch.stack(d_p).view(4 * HIDDEN, b, h, w).permute(1, 0, 2, 3).contiguous()        # [B,1024,H,W]
+    d_bk = dp.sum((0, 2, 3)).view(4, HIDDEN)
+    wx = _hoisted_conv_weight(p, mode)
+    dpc = dp[:, :wx.shape[0]].contiguous()
+    d_wx = torch.nn.grad.conv2d_weight(feat, wx.shape, dpc, padding=1)
+    d_feat = torch.nn.grad.conv2d_input(feat.shape, wx, dpc, padding=1) if need_feat_grad else None
+    _assemble_k_grads_modes12(grads, d_wx, d_kk, d_bk, mode)
+    return d_feat, [grads[name] for name in PARAM_NAMES]
+
+
+def _assemble_k_grads_modes12(grads: Dict[str, torch.Tensor], d_wx: torch.Tensor, d_kk, d_bk, mode: int) -> None:
+    """The K.i gradients in the reference's layout: mode 2 (dKk_i | layer i's rows of dWx) [256,832]; mode 1 dKk_i [256,256]."""
+    d_wx = d_wx.reshape(-1, HIDDEN, UNFOLD)
+    grads["K.0.0.weight"] = d_wx[0].reshape(HIDDEN, UNFOLD, 1, 1)
+    grads["K.0.0.bias"] = d_bk[0]
+    for i in (1, 2, 3):
+        if mode == 1:
+            grads[f"K.{i}.0.weight"] = d_kk[i].reshape(HIDDEN, HIDDEN, 1, 1)
+        else:
+            grads[f"K.{i}.0.weight"] = torch.cat([d_kk[i], d_wx[i]], dim=1).reshape(HIDDEN, HIDDEN + UNFOLD, 1, 1)
+        grads[f"K.{i}.0.bias"] = d_bk[i]
+
+
+_cell_ones_cache: Dict[tuple, torch.Tensor] = {}
+
+
+def _cell_ones(cells: int, dev) -> torch.Tensor:
+    """The tiled 4-row group of ones over ``cells`` cells (zero padding): diinn_plane_rowdot against it sums dP over the cells.
+    Kept per (cell count, device) like the geometry constants (one entry per batch geometry of a training run)."""
+    key = (cells, str(dev))
+    ones = _cell_ones_cache.pop(key, None)
+    if ones is None:
+        ones = tile_planes(torch.ones((4, cells), dtype=torch.float32, device=dev))
+        while len(_cell_ones_cache) >= GEOMETRY_CACHE_ENTRIES:
+            _cell_ones_cache.pop(next(iter(_cell_ones_cache)))
+    _cell_ones_cache[key] = ones
+    return ones
+
+
+def backward_fused_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, chain: torch.Tensor,
+                           params: Sequence[torch.Tensor], packed: torch.Tensor, size: Sequence[int], mode: int,
+                           need_feat_grad: bool = True) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+    """The same gradients as ``backward_from_saved_modes12``, on the HIP kernels throughout:
+      diinn_backward_data_qonly  3 x bwd_layer_kernel<., KPART=false>: g_q,i-1 = Qw_i^T g_s,i; leaves G_i = (g^_a,i ; g_s,i) and q_i
+      diinn_plane_gemm_nt        [dQw_i | dbQ_i] = g_s,i [256 x N] . q_{i-1}^T, split over pixels
+      diinn_plane_rowdot         g_s,0 against (rel_h, rel_w, ratio, 1); the head against g_out
+      diinn_backward_cell_sum    S = per-cell sums of g^_a, tiled over the cell axis
+      diinn_cell_chain_bwd       the chain backwards: dP (in place of S, and NCHW) and k_0..k_2 tiled over cells
+      diinn_plane_gemm_nt        dKk_i = dP_i [256 x cells] . k_{i-1}^T;  diinn_plane_rowdot against ones: dbK = sum of dP over cells
+      _conv_grads_native         the 3x3 convolution's gradients from dP (mode 1: layer 0's 256 rows)
+    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward, ``chain`` its [B,H,W,1024] workspace."""
+    if mode not in (1, 2):
+        raise ValueError("backward_fused_modes12 covers decoder modes 1 and 2")
+    lib = _native.load()
+    p = dict(zip(PARAM_NAMES, params))
+    b, _, h, w = feat.shape
+    hu, wu = int(size[0]), int(size[1])
+    n = b * hu * wu
+    t = (n + PLANE_TILE - 1) // PLANE_TILE
+    cells = b * h * w
+    tc = (cells + PLANE_TILE - 1) // PLANE_TILE
+    dev = gout.device
+    if tuple(acts.shape) != (4, t, 2 * HIDDEN, PLANE_TILE) or not acts.is_contiguous():
+        raise ValueError("acts must be the contiguous tiled [4, T, 512, 32] buffer of the training forward")
+    if chain.numel() != cells * 4 * HIDDEN or not chain.is_contiguous():
+        raise ValueError("chain must be the contiguous [B,H,W,1024] workspace of the training forward")
+    geo = _geometry(b, h, w, hu, wu, dev)
+    seg_h, seg_w, syn_t = geo["seg_h"], geo["seg_w"], geo["syn_t"]
+    ones_t = _cell_ones(cells, dev)
+    gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
+    g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+    q = torch.empty((4, t, HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+    gout_t = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))     # 4-row right-hand side of the head product
+    # the weight-gradient GEMMs here have 256 rows = 2 output blocks (mode 3's: 512 rows = 4): twice the splits make one workgroup per CU
+    ksplit = max(1, min(2 * WGRAD_KSPLIT, t))
+    kcsplit = max(1, min(2 * WGRAD_KSPLIT, tc))
+    rsplit = max(1, min(ROWDOT_SPLITS, t))
+    rcsplit = max(1, min(ROWDOT_SPLITS, tc))
+    part = torch.empty((3, ksplit, HIDDEN, HIDDEN + 1), dtype=torch.float32, device=dev)
+    partk = torch.empty((3, kcsplit, HIDDEN, HIDDEN), dtype=torch.float32, device=dev)
+    part0 = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
+    partl = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
+    partb = torch.empty((2, rcsplit, 2 * HIDDEN, 4), dtype=torch.float32, device=dev)
+    dp = torch.empty((b, 4 * HIDDEN, h, w), dtype=torch.float32, device=dev)
+    alloc = torch.empty if cells % PLANE_TILE == 0 else torch.zeros      # (a ragged last tile's padding stays zero)
+    a_t = alloc((tc, 4 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+    k_t = alloc((tc, 3 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
+    half = 2 * HIDDEN * PLANE_TILE * 4                            # bytes from row 0 to row 512 of a tile of a_t
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.check(lib.diinn_backward_data_qonly(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
+                      "diinn_backward_data_qonly")
+        for i in (3, 2, 1):
+            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, HIDDEN, ptr(q[i - 1]), HIDDEN, 0,
+                                                  ptr(part[i - 1]), HIDDEN, HIDDEN, n, ksplit, 1),
+                          "diinn_plane_gemm_nt")
+        # layer 0: only g_s,0 (rows 256..511 of G_0) meets (rel_h, rel_w, ratio, 1); dbK_0 comes from the chain below
+        _native.check(lib.diinn_plane_rowdot(stream, C.c_void_p(g[0].data_ptr() + HIDDEN * PLANE_TILE * 4), 2 * HIDDEN, ptr(syn_t), ptr(part0),
+                                             HIDDEN, n, rsplit), "diinn_plane_rowdot")
+        _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(gout_t), ptr(partl), HIDDEN, n, rsplit),
+                      "diinn_plane_rowdot")
+        _native.check(lib.diinn_backward_cell_sum(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t), b, h, w, hu, wu),
+                      "diinn_backward_cell_sum")
+        _native.check(lib.diinn_cell_chain_bwd(stream, ptr(a_t), ptr(chain), ptr(packed), ptr(dp), ptr(a_t), ptr(k_t), b, h, w),
+                      "diinn_cell_chain_bwd")
+        for i in (3, 2, 1):
+            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(a_t), 4 * HIDDEN, i * HIDDEN, ptr(k_t), 3 * HIDDEN, (i - 1) * HIDDEN,
+                                                  ptr(partk[i - 1]), HIDDEN, HIDDEN, cells, kcsplit, 0),
+                          "diinn_plane_gemm_nt")
+        for hf in (0, 1):                                        # rows 0..511 and 512..1023 of dP against ones
+            _native.check(lib.diinn_plane_rowdot(stream, C.c_void_p(a_t.data_ptr() + hf * half), 4 * HIDDEN, ptr(ones_t), ptr(partb[hf]),
+                                                 2 * HIDDEN, cells, rcsplit), "diinn_plane_rowdot")
+    grads: Dict[str, torch.Tensor] = {}
+    dl = _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: q_3 . (g_out ; 0)^T
+    grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
+    grads["last_layer.bias"] = gp.sum(1)
+    dws = _sum_parts(part.view(3, ksplit, -1)).view(3, HIDDEN, HIDDEN + 1)        # [3, 256, 257]: [dQw_i | dbQ_i]
+    dks = _sum_parts(partk.view(3, kcsplit, -1)).view(3, HIDDEN, HIDDEN)          # [3, 256, 256]: dKk_i
+    d_bk = _sum_parts(partb.view(2, rcsplit, -1)).view(4, HIDDEN, 4)[:, :, 0]     # [4, 256]: sum of dP_i over the cells
+    d_kk: List[Optional[torch.Tensor]] = [None] * 4
+    for i in (3, 2, 1):
+        d_kk[i] = dks[i - 1]
+        grads[f"Q.{i}.0.weight"] = dws[i - 1][:, :HIDDEN].reshape(HIDDEN, HIDDEN, 1, 1)
+        grads[f"Q.{i}.0.bias"] = dws[i - 1][:, HIDDEN]
+    d0 = _sum_parts(part0.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: g_s,0 . (rel_h, rel_w, ratio, 1)^T
+    grads["Q.0.0.weight"] = d0[:, :3].reshape(HIDDEN, 3, 1, 1)
+    grads["Q.0.0.bias"] = d0[:, 3]
+    kw = tuple(p[f"K.{i}.0.weight"] for i in range(4))
+    wx = _hoisted_conv_weight(p, mode)
+    d_wx, d_feat = _conv_grads_native(feat, wx, dp, need_feat_grad, wkey=(mode, *((x.data_ptr(), x._version) for x in kw)),
+                                      wpins=kw, a_t=a_t, rows=wx.shape[0])
+    _assemble_k_grads_modes12(grads, d_wx, d_kk, d_bk, mode)
+    return d_feat, [grads[name] for name in PARAM_NAMES]
+
+
+# ---------------------------------------------------------------------------
 # autograd function
 # ---------------------------------------------------------------------------
 class DecodeMode3Function(torch.autograd.Function):
@@ -540,9 +798,69 @@ class DecodeMode3Function(torch.autograd.Function):
         return (d_feat, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
 
 
+def train_forward_modes12(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int, mode: int):
+    """The modes-1/2 training forward on a contiguous fp32 CUDA ``feat_c``: the hoisted conv (diinn_precompute_P_wpu), the per-cell
+    chain (diinn_cell_chain), decode_kernel<SIN, KPART=false, SAVE> (diinn_decode_train_fwd_qonly).
+    Returns (out, acts [4,T,512,32], chain workspace [B,H,W,1024], packed image)."""
+    lib = _native.load()
+    b, c, h, w = feat_c.shape
+    n = b * hu * wu
+    dev = feat_c.device
+    packed = pack_on_device(params, mode)
+    chain = torch.empty((b, h, w, 4 * HIDDEN), dtype=torch.float32, device=dev)
+    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
+    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.check(lib.diinn_precompute_P_wpu(stream, ptr(feat_c), ptr(packed), ptr(chain), b, h, w, 0, h), "diinn_precompute_P_wpu")
+        _native.check(lib.diinn_cell_chain(stream, ptr(chain), ptr(packed), b, h, w, 0, h), "diinn_cell_chain")
+        _native.check(lib.diinn_decode_train_fwd_qonly(stream, ptr(chain), ptr(packed), ptr(out), ptr(acts), b, h, w, hu, wu,
+                                                       int(sin_mode)), "diinn_decode_train_fwd_qonly")
+    return out, acts, chain, packed
+
+
+class DecodeModes12Function(torch.autograd.Function):
+    """out = decoder(feat) for decoder modes 1 and 2 on the HIP kernels, differentiable in feat and the 18 parameter tensors.
+    Besides the planes the forward keeps the chain workspace (B*H*W*1024 floats): the masks and k_{i-1} of the chain's backward."""
+
+    @staticmethod
+    def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, mode: int, *params: torch.Tensor) -> torch.Tensor:
+        lib = _native.load()
+        if not feat.is_cuda:
+            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
+        if len(params) != len(PARAM_NAMES):
+            raise ValueError(f"expected {len(PARAM_NAMES)} parameter tensors in PARAM_NAMES order")
+        shapes = param_shapes(mode)
+        for name, p_ in zip(PARAM_NAMES, params):
+            if tuple(p_.shape) != shapes[name]:
+                raise ValueError(f"{name}: expected shape {shapes[name]} for decoder mode {mode}, got {tuple(p_.shape)}")
+        feat_c = feat.detach().contiguous().to(torch.float32)
+        if feat_c.dim() != 4 or feat_c.shape[1] != IN_CHANNELS:
+            raise ValueError(f"feat must be [B,{IN_CHANNELS},H,W]")
+        n = feat_c.shape[0] * hu * wu
+        if lib.diinn_training_plane_floats(n, 2 * HIDDEN) < 0:
+            raise RuntimeError(f"diinn_amd: B*Hu*Wu = {n} HR pixels in one training forward exceeds the limit; split the batch")
+        out, acts, chain, packed = train_forward_modes12(feat_c, params, hu, wu, sin_mode, mode)
+        ctx.save_for_backward(feat_c, acts, chain, packed, *[p_.detach() for p_ in params])
+        ctx.size = (hu, wu)
+        ctx.mode = mode
+        return out
+
+    @staticmethod
+    def backward(ctx, gout: torch.Tensor):
+        feat, acts, chain, packed, *params = ctx.saved_tensors
+        d_feat, d_params = backward_fused_modes12(gout.contiguous(), feat, acts, chain, params, packed, ctx.size, ctx.mode,
+                                                  need_feat_grad=ctx.needs_input_grad[0])
+        need = ctx.needs_input_grad[5:]
+        return (d_feat, None, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+
+
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
-    """``ImplicitDecoder.forward(x, size, None)`` under autograd (mode 3)."""
+    """``ImplicitDecoder.forward(x, size, None)`` under autograd (modes 1, 2 and 3)."""
     named = dict(decoder.named_parameters())
     params = [named[name] for name in PARAM_NAMES]
     hu, wu = size
+    if decoder.mode in (1, 2):
+        return DecodeModes12Function.apply(feat, int(hu), int(wu), int(decoder.sin_mode), int(decoder.mode), *params)
     return DecodeMode3Function.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *params)

@@ -302,6 +302,15 @@ long long diinn_training_plane_floats(long long npix, int rows);
 int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
                            float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode);
 
+/* Training forward of decoder modes 1 and 2.  Replaces: ImplicitDecoder.step() of those modes under autograd (diinn.py:116-131
+ * through forward(x, size, None), :170-171; sr_module.py:127-129).  chain_dev is the [B,H,W,1024] workspace after
+ * diinn_precompute_P_wpu (or diinn_precompute_P) AND diinn_cell_chain over all rows: slot 0 = P_0, slots 1..3 = k_i per LR cell.
+ * The per-pixel network is the synthesis branch alone (DIINN_COMPUTE_F32_QONLY's kernel with the sine branch in radians); acts_dev
+ * has diinn_decode_train_fwd's layout, rows 0..255 of group i holding k_i of the pixel's cell (replicated per pixel), so the
+ * cell sums, the plane GEMM and the rowdot serve both.  The backward pass also needs chain_dev: keep it.  One kernel. */
+int diinn_decode_train_fwd_qonly(void* stream, const float* chain_dev, const float* packed_dev, float* out_dev,
+                                 float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode);
+
 /* Backward pass of the per-pixel layers.  Replaces: autograd's backward through step()
  * (diinn.py:132-139), the part that runs per HR pixel.
  * Inputs: gout_planes_dev = d loss / d out as PLAIN planes [3][npix]; acts_dev from
@@ -316,6 +325,14 @@ int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed
  * synchronisation. */
 int diinn_backward_data(void* stream, const float* gout_planes_dev, const float* acts_dev,
                         const float* packed_dev, float* G_dev, float* Q_dev, long long npix);
+
+/* The same for decoder modes 1 and 2 (autograd's backward through diinn.py:116-131, the per-pixel part): the modulation branch
+ * does not see q there, so g_q,i-1 = Qw_i^T g_s,i alone (half the MFMAs and half the weight stream of diinn_backward_data).
+ * Same buffers and layouts; acts_dev from diinn_decode_train_fwd_qonly.  Rows 0..255 of G_i hold g_q,i sin(s_i) [k_i > 0], the
+ * gradient at the modulation pre-activation BEFORE the per-cell chain: its per-cell sums S_i (diinn_backward_cell_sum) go through
+ * diinn_cell_chain_bwd.  dQw_i = g_s,i q_{i-1}^T is diinn_plane_gemm_nt on rows 256..511 of G_i.  3 kernels. */
+int diinn_backward_data_qonly(void* stream, const float* gout_planes_dev, const float* acts_dev,
+                              const float* packed_dev, float* G_dev, float* Q_dev, long long npix);
 
 /* Weight-gradient GEMM over the pixel axis: C[M x Nc] = A . B^T where A = rows [a_row0, a_row0+M) of a tiled
  * group with a_rows rows per tile and B = rows [b_row0, b_row0+Nc) of a tiled group with b_rows rows;
@@ -348,6 +365,18 @@ int diinn_sum_parts(void* stream, const float* part_dev, float* out_dev, int gro
 int diinn_backward_cell_sum(void* stream, const float* G_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
                             float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu);
 int diinn_unfold_tiled(void* stream, const float* feat_dev, float* out_tiled_dev, int rows, int B, int H, int W);
+
+/* Modes 1 and 2: backward of the per-cell modulation chain k_0 = relu(P_0), k_i = relu(Kk_i k_{i-1} + P_i), Kk_i = K.i.weight[:, :256]
+ * (autograd's backward through the K layers of diinn.py:118-121,126-129, which run on the replicated map in the reference):
+ *     g_a,3 = S_3,    g_a,i-1 = [k_{i-1} > 0] (Kk_i^T g_a,i) + S_{i-1},    dP_i = g_a,i
+ * S_tiled_dev: the per-cell sums as diinn_backward_cell_sum's tiled output, [ceil(B H W / 32)][1024][32] (rows 256 i + ch).
+ * chain_dev: the workspace diinn_decode_train_fwd_qonly read (slots 1..3 = k_i, slot 0 = P_0, whose sign is the mask of layer 0).
+ * Outputs: dP_dev NCHW [B][1024][H][W] and dP_tiled_dev in S's layout -- dP_tiled_dev may equal S_tiled_dev (in place); the
+ * padding of a ragged last tile is neither read as data nor written.  k_tiled_dev (may be NULL): k_0, k_1, k_2 (rectified) as a
+ * tiled group [ceil(B H W / 32)][768][32] over the cells, the B operand of dKk_i = g_a,i k_{i-1}^T on diinn_plane_gemm_nt;
+ * dbK_i is the sum of dP_i over the cells.  Reads section 8 of the packed image.  One kernel; no allocation, no synchronisation. */
+int diinn_cell_chain_bwd(void* stream, const float* S_tiled_dev, const float* chain_dev, const float* packed_dev,
+                         float* dP_dev, float* dP_tiled_dev, float* k_tiled_dev, int B, int H, int W);
 
 /* ---- LIIF comparison decoder ------------------------
  * Replaces: LIIF.query_rgb + batched_predict + reshape_pred (liif.py:59-127,129-146), constructor

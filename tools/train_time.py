@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Decoder training step (forward + backward) timing on one GPU.
 
-  ours   : DecodeMode3Function (HIP forward with saved planes + library-GEMM backward)
+  ours   : the decoder under autograd on the HIP path (training.DecodeMode3Function, or DecodeModes12Function with --mode 1|2:
+           HIP forward with saved planes + library-GEMM backward)
   eager  : the reference's op sequence in PyTorch-ROCm eager mode (unfold -> nearest-exact gather ->
            9 conv1x1 + 3 cat + 4 sin under autograd), restated inline (the reference itself does not
            travel to the GPU box)
 
-usage: train_time.py [B] [LR] [SCALE] [--only-ours]     (default 16 48 4: the reference's training patch geometry,
+usage: train_time.py [B] [LR] [SCALE] [--only-ours] [--mode=1|2|3]     (default 16 48 4: the reference's training patch geometry,
        configs/default.yaml: batch 16, 48x48 LR patches, scales 2-4)
 """
 import os
@@ -24,12 +25,13 @@ import diinn_amd.training as T  # noqa: E402
 
 
 def eager_forward(dec, feat, size, idx_h, idx_w, syn):
+    """step() of the decoder's mode (diinn.py:116-139): K[i] sees k (mode 1), [k; x] (mode 2) or [q; x] (mode 3)."""
     u = F.unfold(feat, 3, padding=1).view(feat.shape[0], 576, feat.shape[2], feat.shape[3])
     x = u[:, :, idx_h][:, :, :, idx_w]
     k = dec.K[0](x)
     q = k * dec.Q[0](syn)
     for i in range(1, 4):
-        k = dec.K[i](torch.cat([q, x], dim=1))
+        k = dec.K[i](k if dec.mode == 1 else torch.cat([k if dec.mode == 2 else q, x], dim=1))
         q = k * dec.Q[i](q)
     return dec.last_layer(q)
 
@@ -94,14 +96,15 @@ def main():
     only_ours = "--only-ours" in sys.argv          # for profiling: skip the eager comparison
     if "--e2e" in sys.argv:
         return e2e()
+    mode = next((int(a.split("=")[1]) for a in sys.argv if a.startswith("--mode=")), 3)
     argv = [a for a in sys.argv if not a.startswith("--")]
     b = int(argv[1]) if len(argv) > 1 else 16
     lr = int(argv[2]) if len(argv) > 2 else 48
     sc = int(argv[3]) if len(argv) > 3 else 4
     dev = torch.device("cuda:0")
     hu = wu = lr * sc
-    dec = D.ImplicitDecoder(mode=3, init_q=False)
-    dec.load_state_dict({k: torch.from_numpy(v) for k, v in synth.decoder_state_dict(123).items()})
+    dec = D.ImplicitDecoder(mode=mode, init_q=False)
+    dec.load_state_dict({k: torch.from_numpy(v) for k, v in synth.decoder_state_dict(123, mode=mode).items()})
     dec = dec.to(dev).train()
     feat = torch.from_numpy(synth.encoder_features(123, b, lr, lr)).to(dev).requires_grad_(True)
     r = torch.randn(b, 3, hu, wu, device=dev)
@@ -129,7 +132,7 @@ def main():
         (eager_forward(dec, feat, (hu, wu), idx_h, idx_w, syn) * r).sum().backward()
 
     n = b * hu * wu
-    print(f"B={b} LR={lr}x{lr} x{sc} -> {hu}x{wu}: {n} HR pixels")
+    print(f"mode {mode}  B={b} LR={lr}x{lr} x{sc} -> {hu}x{wu}: {n} HR pixels")
     print(f"  inference forward (no grad)        {timeit(ours_fwd):8.2f} ms")
     print(f"  training forward (saves planes)    {timeit(ours_train_fwd):8.2f} ms")
     t_ours = timeit(ours_step)
