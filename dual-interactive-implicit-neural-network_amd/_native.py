@@ -155,6 +155,10 @@ SIGNATURES = {
                                             C.c_longlong]),
     "diinn_cell_chain_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int]),
+    "diinn_relu_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                  C.c_int, C.c_int, C.c_int]),
+    "diinn_conv_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@
 //                              decode_bf16_coop8_kernel (8 waves), decode_bf16_coop8p_kernel (8 waves, persistent)
 //   diinn_bf16x3.hip           decode_bf16x3h_kernel (persistent, hi weight pieces through LDS), decode_bf16x3_kernel: split bf16
 //   diinn_training.hip         backward pass: bwd_head / bwd_layer (<KPART=false>: modes 1/2), cell_chain_bwd (modes 1/2), plane_gemm, plane_rowdot, cell_sum
+//   diinn_enc_training.hip     the encoder's dense blocks under autograd: conv_wgrad (weight-gradient GEMM over the pixel axis), relu_gate
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))

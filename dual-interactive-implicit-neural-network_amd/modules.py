@@ -47,10 +47,21 @@ class RDB(nn.Module):
         self.convs = nn.Sequential(*[RDB_Conv(growRate0 + c * growRate, growRate, kSize) for c in range(nConvLayers)])
         self.LFF = nn.Conv2d(growRate0 + nConvLayers * growRate, growRate0, 1)
 
-    def forward(self, x):
+    def forward(self, x, hip_autograd: bool = False, max_pixels: Optional[int] = None):
         if not torch.is_grad_enabled():
             return self._forward_dense_buffer(x)
+        if hip_autograd and self._hip_autograd_applies(x, max_pixels):
+            from .encoder_training import RDBFunction, block_params
+            return RDBFunction.apply(x, *block_params(self))
         return self.LFF(self.convs(x)) + x
+
+    def _hip_autograd_applies(self, x, max_pixels) -> bool:
+        """``RDN.hip_autograd``'s conditions for this block and input: CUDA fp32, the config-'B' block shape, and a map within
+        the encoder's ``hip_trunk_max_pixels``; anything else trains through the framework as before."""
+        from .encoder_training import block_applies
+        return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and max_pixels is not None
+                and x.shape[0] * x.shape[-2] * x.shape[-1] <= max_pixels and self.LFF.weight.dtype == torch.float32
+                and block_applies(self))
 
     def _forward_dense_buffer(self, x):
         """Inference form of the dense block: one [B, G0 + C*G, H, W] buffer, every conv reads the
@@ -167,6 +178,10 @@ class RDN(nn.Module):
     # ~3e-6 of max|feat| and the decoded image by ~3e-8.  Measured per trunk: 192x192 9.4 -> 6.7 ms,
     # 256x256 11.85 -> 7.9 ms, 384x384 28.1 -> 20.1 ms, 512x512 46.6 -> 31.4 ms; below ~180x180 the Winograd kernels stay faster and are used.
     hip_split_bf16: bool = False
+    # opt-in: under autograd the 16 residual dense blocks run on the library's kernels (encoder_training.RDBFunction, DESIGN.md
+    # section 3.8: forward and input gradients on the trunk's convolution kernels, weight gradients on conv_wgrad_kernel), fp32 CUDA
+    # maps of up to hip_trunk_max_pixels; SFENet1, SFENet2 and GFF stay on the framework.  False: autograd through the framework.
+    hip_autograd: bool = False
 
     def __init__(self, G0: int = 64, RDNkSize: int = 3, RDNconfig: str = "B", n_colors: int = 3):
         super().__init__()
@@ -333,8 +348,9 @@ class RDN(nn.Module):
         shallow = self.SFENet1(x)
         x = self.SFENet2(shallow)
         blocks = []
+        hip_autograd = self.hip_autograd and self._hip_ok and torch.is_grad_enabled()
         for rdb in self.RDBs:
-            x = rdb(x)
+            x = rdb(x, True, self.hip_trunk_max_pixels) if hip_autograd else rdb(x)
             blocks.append(x)
         return self.GFF(torch.cat(blocks, 1)) + shallow
 

@@ -378,6 +378,26 @@ int diinn_unfold_tiled(void* stream, const float* feat_dev, float* out_tiled_dev
 int diinn_cell_chain_bwd(void* stream, const float* S_tiled_dev, const float* chain_dev, const float* packed_dev,
                          float* dP_dev, float* dP_tiled_dev, float* k_tiled_dev, int B, int H, int W);
 
+/* ---- RDN dense blocks under autograd (encoder_training.py: RDBFunction) ------------------------
+ * Replaces: what autograd records and runs backward for RDB_Conv.forward (rdn.py:15-17: conv, ReLU, torch.cat) and RDB.forward
+ * (rdn.py:34-35: LFF(convs(x)) + x) when RDN.hip_autograd is set.  The forward and every input gradient of a block run on
+ * diinn_conv_ksplit / diinn_conv_wino / diinn_conv_wino4_ws; these two are the rest.  Both validate every argument before
+ * the launch, enqueue one kernel on `stream`, allocate nothing and do not synchronise.
+ * diinn_relu_gate: g[b][c][y][x] = y[b][c][y][x] > 0 ? d[b][c][y][x] : 0 over 64 planes per image, each tensor addressed as
+ *   base + b * batch_stride (floats; >= 64 * H * W for B > 1) + c * H * W.  A zero of either sign and a NaN in y close the gate.
+ * diinn_conv_wgrad: the weight gradient of a 64-output convolution,
+ *       dW[co][ci][tap] = sum over (b, y, x) of g[b][co][y][x] * x[b][ci][y + ky - 1][x + kx - 1],   tap = 3 ky + kx,
+ *   taps = 9 (3x3, zero padding) or 1 (1x1: tap shift 0); Cin % 64 == 0, Cin <= 576; g_dev / x_dev addressed by batch stride like
+ *   the convolution entry points.  A GEMM over the pixel axis on the fp32 MFMA; the unfolded input is gathered from x_dev on the
+ *   fly, never written.  The pixel axis is cut into `nsplit` slices of whole 32-pixel tiles: part_dev is
+ *   [nsplit][64][Cin * taps + 1], slice ks holding its share of dW in the weight's own [co][ci][tap] order and, in the last
+ *   column, the row sums of g (the bias gradient).  A slice that receives no tile writes zeros.  The caller adds the slices in
+ *   order (diinn_sum_parts; 64 * (Cin * taps + 1) is a multiple of 4): no atomics, deterministic. */
+int diinn_relu_gate(void* stream, const float* d_dev, long long d_batch_stride, const float* y_dev, long long y_batch_stride,
+                    float* g_dev, long long g_batch_stride, int B, int H, int W);
+int diinn_conv_wgrad(void* stream, const float* g_dev, long long g_batch_stride, const float* x_dev, long long x_batch_stride,
+                     int Cin, int taps, float* part_dev, int nsplit, int B, int H, int W);
+
 /* ---- LIIF comparison decoder ------------------------
  * Replaces: LIIF.query_rgb + batched_predict + reshape_pred (liif.py:59-127,129-146), constructor
  * defaults (local_ensemble, feat_unfold, cell_decode): for every HR pixel the 580->256->256->256->256->3

@@ -9,6 +9,8 @@
 
 usage: train_time.py [B] [LR] [SCALE] [--only-ours] [--mode=1|2|3]     (default 16 48 4: the reference's training patch geometry,
        configs/default.yaml: batch 16, 48x48 LR patches, scales 2-4)
+       train_time.py [B] [LR] [SCALE] --encoder-hip[=on|off]   the WHOLE step (SRLitModule.step + backward + Adam) with the encoder's
+       dense blocks under autograd on the HIP kernels (net.encoder.hip_autograd) and on the framework, 5 repetitions each
 """
 import os
 import sys
@@ -92,10 +94,47 @@ def e2e():
     print(f"  peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
 
+def encoder_hip(b, lr, sc, mode, reps=5, only=None):
+    """The whole training step (SRLitModule.step + backward, one scale) with the encoder's dense blocks on the HIP path
+    (net.encoder.hip_autograd) and off it: ``reps`` repetitions each after a warm-up, every one followed by an Adam step so
+    that the flag-on time includes the weight repacks an optimiser step forces.  ``only``: "on" / "off" (profiling)."""
+    import diinn_amd.modules as M
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    net = M.SRLitModule(arch="diinn", mode=mode, init_q=False).to(dev).train()
+    opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+    x = torch.rand(b, 3, lr, lr, device=dev)
+    batch = {sc: (x, torch.rand(b, 3, lr * sc, lr * sc, device=dev), None)}
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss, _ = net.step(batch)
+        loss.backward()
+        opt.step()
+
+    print(f"whole training step (encoder + decoder mode {mode} + Adam)  B={b} LR={lr}x{lr} x{sc}")
+    for flag in (False, True):
+        if only is not None and flag != (only == "on"):
+            continue
+        net.net.encoder.hip_autograd = flag
+        torch.cuda.reset_peak_memory_stats()
+        for _ in range(3):
+            step()
+        times = [timeit(step, n=3, warm=0) for _ in range(reps)]
+        print(f"  encoder.hip_autograd = {flag!s:5}  " + " ".join(f"{t:7.2f}" for t in times) +
+              f" ms   median {sorted(times)[len(times) // 2]:7.2f}   peak memory {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB")
+
+
 def main():
     only_ours = "--only-ours" in sys.argv          # for profiling: skip the eager comparison
     if "--e2e" in sys.argv:
         return e2e()
+    if "--encoder-hip" in sys.argv or any(a.startswith("--encoder-hip=") for a in sys.argv):
+        argv = [a for a in sys.argv if not a.startswith("--")]
+        mode = next((int(a.split("=")[1]) for a in sys.argv if a.startswith("--mode=")), 3)
+        only = next((a.split("=")[1] for a in sys.argv if a.startswith("--encoder-hip=")), None)
+        return encoder_hip(int(argv[1]) if len(argv) > 1 else 16, int(argv[2]) if len(argv) > 2 else 48,
+                           int(argv[3]) if len(argv) > 3 else 4, mode, only=only)
     mode = next((int(a.split("=")[1]) for a in sys.argv if a.startswith("--mode=")), 3)
     argv = [a for a in sys.argv if not a.startswith("--")]
     b = int(argv[1]) if len(argv) > 1 else 16
