@@ -41,9 +41,22 @@ struct TagCoopT { static constexpr bool value = true; };
 // order; they go to the TAP BUFFER p.out = [B][p.Orows rows from p.Orow0][Wu][TAP_STRIDE] (k major, c minor, one pad float: seven
 // 16-byte stores per pixel).  The head table (27 x 256 floats, natural channel order) sits in LDS behind the Q0 rows of `tab`.
 // (TAPS, TAP_STRIDE and the head image's layout: diinn_layout.h)
-template <int SIN_MODE, bool KPART = true, bool SAVE = false, bool HEAD3 = false>
+//
+// INITQ = true (decoder init_q=True, mode 3: diinn.py:48-51,113-115): the unfolded features are multiplied by a per-pixel sine
+// embedding before any layer sees them, so there is no per-cell P.  initq_planes_kernel (diinn_initq.hip) leaves, per HR PIXEL,
+// PIX_CH = 1280 floats in p.P = [B][p.Prows HR rows from p.Prow0][Wu][1280]: channels 0..1023 are what P[cell] holds otherwise,
+// channels 1024..1279 layer 0's sine argument (Q0 . E + bQ0, in revolutions).  Pc points at the pixel's own record, layer 0 reads
+// its sine argument there and not from the Q0 table (whose rows the preamble skips); everything else is the code below as it is.
+// INITQ rides in the first template argument, SIN_X = sine mode | DECODE_INITQ: the kernel keeps its four parameters, so every
+// instantiation that existed before keeps its symbol name (and its instructions); the new ones are decode_kernel<SIN | DECODE_INITQ>.
+constexpr int DECODE_INITQ = 4;
+template <int SIN_X, bool KPART = true, bool SAVE = false, bool HEAD3 = false>
 __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
+    constexpr int SIN_MODE = SIN_X & (DECODE_INITQ - 1);
+    constexpr bool INITQ = (SIN_X & DECODE_INITQ) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * DECODE_INITQ && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | DECODE_INITQ");
     static_assert(!(HEAD3 && SAVE), "mode 4 is inference only");
+    static_assert(!INITQ || (KPART && !SAVE && !HEAD3), "init_q: mode 3, inference");
     // The small tables of layer 0 and of the head go through LDS: a vector-memory instruction blocks its wave for
     // ~60 cycles (stamps), and a wave reading them straight from the packed image issued 128 + 96
     // of those per tile.  Rows: Q0h, Q0w, t = fma(Q0r, ratio, bQ0) (the pixel-independent part of the sine
@@ -61,14 +74,18 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
         const int i = threadIdx.x & 63, part = threadIdx.x >> 6;
         const float* __restrict__ Q0s = p.Wt + S_Q0 + 4 * i;
         if (part == 0) {
-            *(f32x4*)(tab + 0 * HID + 4 * i) = *(const f32x4*)(Q0s + 0 * HID);
-            *(f32x4*)(tab + 1 * HID + 4 * i) = *(const f32x4*)(Q0s + 1 * HID);
+            if constexpr (!INITQ) {
+                *(f32x4*)(tab + 0 * HID + 4 * i) = *(const f32x4*)(Q0s + 0 * HID);
+                *(f32x4*)(tab + 1 * HID + 4 * i) = *(const f32x4*)(Q0s + 1 * HID);
+            }
         } else if (part == 1) {
-            const f32x4 wr = *(const f32x4*)(Q0s + 2 * HID), bq = *(const f32x4*)(Q0s + 3 * HID);
-            f32x4 t;
+            if constexpr (!INITQ) {
+                const f32x4 wr = *(const f32x4*)(Q0s + 2 * HID), bq = *(const f32x4*)(Q0s + 3 * HID);
+                f32x4 t;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
-            *(f32x4*)(tab + 2 * HID + 4 * i) = t;
+                for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
+                *(f32x4*)(tab + 2 * HID + 4 * i) = t;
+            }
         } else if constexpr (HEAD3) {
             // (the 27 head rows are loaded by all four waves below; mode 4's bias and both validity words belong to the gather)
         } else if (part == 2) {
@@ -131,7 +148,8 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
 #endif
     STAMP(0);
     const float* __restrict__ Wt = p.Wt;
-    const float* __restrict__ Pc = p.P + (((size_t)b * p.Prows + (iy - p.Prow0)) * p.W + ix) * PCH + 4 * h;
+    const float* __restrict__ Pc = INITQ ? p.P + (((size_t)b * p.Prows + (yc - p.Prow0)) * p.Wu + xc) * PIX_CH + 4 * h
+                                         : p.P + (((size_t)b * p.Prows + (iy - p.Prow0)) * p.W + ix) * PCH + 4 * h;
 
     // saved-activation planes (SAVE): one buffer descriptor per layer covering this wave's plane tile
     // (512 rows x 32 pixels); a lane's offset is its pixel inside the row of channel 4h, the channel
@@ -154,14 +172,21 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
             for (int g = 0; g < 4; ++g) {
                 const int c0 = 32 * m + 8 * g;
                 const f32x4 pv = *(const f32x4*)(Pc + c0);
-                const f32x4 wh = *(const f32x4*)(Q0 + 0 * HID + c0);
-                const f32x4 ww = *(const f32x4*)(Q0 + 1 * HID + c0);
-                const f32x4 tq = *(const f32x4*)(Q0 + 2 * HID + c0);
+                f32x4 wh, ww, tq;
+                if constexpr (INITQ) {
+                    tq = *(const f32x4*)(Pc + PCH + c0);         // the pixel's own sine argument
+                } else {
+                    wh = *(const f32x4*)(Q0 + 0 * HID + c0);
+                    ww = *(const f32x4*)(Q0 + 1 * HID + c0);
+                    tq = *(const f32x4*)(Q0 + 2 * HID + c0);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float a = tq[e];
-                    a = __builtin_fmaf(ww[e], relw, a);
-                    a = __builtin_fmaf(wh[e], relh, a);
+                    if constexpr (!INITQ) {
+                        a = __builtin_fmaf(ww[e], relw, a);
+                        a = __builtin_fmaf(wh[e], relh, a);
+                    }
                     const float kv = relu0(pv[e]);
                     q[16 * m + 4 * g + e] = kv * sine(a);
                     if constexpr (SAVE) {
@@ -882,7 +907,58 @@ static int decode_mode4_band_impl(void* stream, const float* P_dev, const float*
     return hip_status(hipGetLastError());
 }
 
+// init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
+// The throughput kernel only (no 16-pixel latency twin).
+static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!pix_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
+    const int gy = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
+    if (gy > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
+    const OutView ov = contig(RowWin{0, Hu}, Wu);
+    DecodeParams p;
+    p.P = pix_dev; p.Wt = packed_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = y0; p.y1 = y1;
+    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
+    p.Prow0 = y0; p.Prows = y1 - y0; p.Orow0 = ov.row0; p.Orows = ov.rows;          // P = the pixel planes: HR rows
+    p.x0 = 0; p.x1 = Wu; p.Ocol0 = ov.col0; p.o_bs = ov.bs; p.o_ps = ov.ps; p.o_rs = ov.rs;
+    p.acts = nullptr; p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;
+    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
+#ifdef DIINN_STAMPS
+    p.stamps = nullptr;
+#endif
+    const int small = diinn_uses_small_output_kernel(Hu, Wu);
+    p.ah = make_axis(H, Hu, small);
+    p.aw = make_axis(W, Wu, small);
+    const dim3 grid(gx, gy, B);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
 extern "C" {
+
+int diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                            int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
+
+int diinn_decode_initq(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                       float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!out_dev) return DIINN_ERR_INVALID_ARG;
+    const int st = diinn_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
 
 int diinn_decode_mode4_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
                             float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,

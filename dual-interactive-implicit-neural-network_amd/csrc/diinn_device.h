@@ -5,6 +5,7 @@
 // Translation units (all built with hipcc --offload-arch=gfx950 -O3 -ffp-contract=off; build.py: HIP_SOURCES + HOST_SOURCES):
 //   diinn_decode.hip           decode_kernel (+ modes 1/2 chain, training forward, mode 4's tap form), decode_coop16_kernel (latency
 //                              form), head3x3_reflect_kernel (mode 4's 9-point gather) and the decode entry points of the C ABI
+//   diinn_initq.hip            initq_planes_kernel (decoder init_q=True: the per-pixel sine embedding and its two per-pixel GEMMs; decode_kernel<SIN | DECODE_INITQ> reads its planes)
 //   diinn_precompute.hip       precompute_P_kernel (direct fp32), precompute_P_bf16_kernel / _bf16_wide_kernel, launch_P
 //   diinn_precompute_wino.hip  precompute_P_wino_kernel (the fp32 hoisted conv in Winograd F(2x2,3x3) form: inference)
 //   diinn_precompute_x3.hip    precompute_P_x3_kernel (the hoisted conv in split-bf16 arithmetic: DIINN_COMPUTE_BF16X3, large maps)

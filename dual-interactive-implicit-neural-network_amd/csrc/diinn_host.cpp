@@ -442,6 +442,44 @@ size_t diinn_mode4_taps_bytes(int B, int Hu, int Wu, int y0, int y1) {
     return (size_t)B * (size_t)(b - a) * (size_t)Wu * TAP_STRIDE * sizeof(float);
 }
 
+// ---- decoder init_q=True (mode 3): the first-layer / Q.0 image (diinn_layout.h "decoder init_q=True") -----------
+size_t diinn_initq_packed_floats(void) { return IQ_FLOATS; }
+
+int diinn_pack_initq(const float* Fw, const float* Fb, const float* Q0w, const float* Q0b, float* packed) {
+    if (!Fw || !Fb || !Q0w || !Q0b || !packed) return DIINN_ERR_INVALID_ARG;
+    float* f = packed + IQ_OFF_F;
+    for (int n = 0; n < UNF; ++n) {                             // Fw is [576][3]: columns rel_h, rel_w, ratio
+        f[0 * UNF + n] = Fw[n * 3 + 0] * INV_2PI;
+        f[1 * UNF + n] = Fw[n * 3 + 1] * INV_2PI;
+        f[2 * UNF + n] = Fw[n * 3 + 2] * INV_2PI;
+        f[3 * UNF + n] = Fb[n] * INV_2PI;
+    }
+    for (int mo = 0; mo < 8; ++mo)                              // Q0w is [256][576]: WP's piece order
+        for (int kg = 0; kg < WP_KG; ++kg) {
+            float* dst = packed + IQ_OFF_Q0W + ((((size_t)(mo >> 1) * WP_KG + kg) * 2) + (mo & 1)) * WL_PIECE;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int o = 32 * mo + (lane & 31);
+                const int h = lane >> 5;
+                for (int e = 0; e < 4; ++e) {
+                    const int kk = 4 * kg + e;
+                    const int t = kk >> 5;
+                    const int c = 2 * (kk & 31) + h;
+                    dst[lane * 4 + e] = Q0w[(size_t)o * UNF + (size_t)c * 9 + t] * INV_2PI;
+                }
+            }
+        }
+    for (int ch = 0; ch < HID; ++ch) packed[IQ_OFF_BQ0 + ch] = Q0b[ch] * INV_2PI;
+    const uint32_t magic = DIINN_INITQ_MAGIC;
+    std::memcpy(packed + IQ_OFF_BQ0 + HID, &magic, 4);
+    for (int i = 1; i < 4; ++i) packed[IQ_OFF_BQ0 + HID + i] = 0.0f;
+    return DIINN_OK;
+}
+
+size_t diinn_initq_pix_bytes(int B, int Wu, int rows) {
+    if (B <= 0 || Wu <= 0 || rows <= 0) return 0;
+    return (size_t)B * (size_t)rows * (size_t)Wu * PIX_CH * sizeof(float);
+}
+
 int diinn_window_rows(int H, int Hu, int Wu, int y0, int y1,
                       int* feat_row0, int* feat_rows, int* p_row0, int* p_rows) {
     int r0, r1;

@@ -124,6 +124,24 @@ constexpr int    TAP_STRIDE   = 28;
 constexpr size_t HEAD3_BIAS   = (size_t)TAPS * HID;
 constexpr size_t HEAD3_FLOATS = HEAD3_BIAS + 4;                // 6,916
 
+// ---- decoder init_q=True, mode 3 (diinn.py:48-51,113-115: E = sin(first_layer . (rel_h, rel_w, ratio) + bF), x' = E * X[cell],
+// Q.0 is 256 x 576 and reads E) ----
+// The first layer and Q.0 are a SEPARATE small image (diinn_pack_initq; the body image is the mode-3 image of the K.* / Q.1..3 / head
+// tensors with a zero Q0 table, which the init_q instantiation of decode_kernel never reads).  Everything in it feeds a sine and is
+// stored divided by 2 pi (inference runs in revolutions, like the *R sections of the body image):
+//   F   [4][576]  rows Fh, Fw, Fr (columns rel_h, rel_w, ratio of first_layer.0.weight) and bF, natural unfolded order n = c*9 + tap
+//   Q0W [mp 4][kg 72][t 2][lane 64][e 4]  A operands of v_mfma_f32_32x32x2_f32 in WP's k order, M-tile mo = 2mp+t:
+//       k-step kk = 4kg+e: tap = kk/32, channel c = 2*(kk%32) + (lane>>5);  value = Q0w[ o = 32mo + (lane&31) ][ c*9 + tap ] / (2 pi)
+//   BQ0 [256], then the image's own validity word DIINN_INITQ_MAGIC.
+// initq_planes_kernel writes, per HR pixel, PIX[b][row - y0][x][PIX_CH]: channels 0..1023 = Wx . (E * X[cell]) + bK (what P holds per
+// cell when init_q is off), channels 1024..1279 = Q0 . E + bQ0 in revolutions (layer 0's sine argument).
+constexpr int    PIX_CH       = PCH + HID;                      // 1280 floats per HR pixel
+constexpr size_t IQ_OFF_F     = 0;
+constexpr size_t IQ_OFF_Q0W   = IQ_OFF_F + 4 * (size_t)UNF;     // 2,304
+constexpr size_t IQ_SZ_Q0W    = (size_t)8 * WP_KG * WL_PIECE;   // 147,456 floats
+constexpr size_t IQ_OFF_BQ0   = IQ_OFF_Q0W + IQ_SZ_Q0W;         // 149,760
+constexpr size_t IQ_FLOATS    = IQ_OFF_BQ0 + HID + 4;           // 150,020 (validity word at IQ_OFF_BQ0 + HID)
+
 // channel held by activation register (m, r) of lane-half h
 DIINN_HD int chan_of(int kk /* = 16*m + r */, int h) {
     const int m = kk >> 4, r = kk & 15;

@@ -104,6 +104,93 @@ def pack_head3x3(sd, prefix: str = "") -> torch.Tensor:
     return torch.from_numpy(packed)
 
 
+def pack_initq(sd, prefix: str = "") -> torch.Tensor:
+    """``init_q=True``: ``first_layer.0.weight`` [576,3,1,1], ``first_layer.0.bias`` [576], ``Q.0.0.weight`` [256,576,1,1] and
+    ``Q.0.0.bias`` [256] (diinn.py:48-51,61-62) -> the init_q host image (1-D fp32 CPU tensor; C ABI ``diinn_pack_initq``:
+    the first layer as [4][576], Q.0 as MFMA A operands in the piece order of the hoisted conv, its bias, a validity word;
+    everything divided by 2 pi).  The body image of such a decoder is ``pack_state_dict`` of the same tensors with a zero
+    [256,3] in place of ``Q.0.0.weight`` (``initq_body_state_dict``)."""
+    lib = _native.load()
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
+        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
+
+    fw, fb = get("first_layer.0.weight", (576, 3)), get("first_layer.0.bias", (576,))
+    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 576)), get("Q.0.0.bias", (HIDDEN,))
+    packed = np.empty(lib.diinn_initq_packed_floats(), dtype=np.float32)
+    _native.check(lib.diinn_pack_initq(_native.fptr(fw), _native.fptr(fb), _native.fptr(q0w), _native.fptr(q0b),
+                                       _native.fptr(packed)), "diinn_pack_initq")
+    return torch.from_numpy(packed)
+
+
+def initq_body_state_dict(sd, prefix: str = ""):
+    """The tensors ``pack_state_dict(..., mode=3)`` takes for an ``init_q=True`` decoder: the same dict with a zero [256,3]
+    in place of the 576-wide ``Q.0.0.weight`` (the init_q kernels never read the body image's Q0 rows)."""
+    body = dict(sd)
+    body[prefix + "Q.0.0.weight"] = np.zeros((HIDDEN, 3), np.float32)
+    return body
+
+
+def initq_chunk_rows(b: int, wu: int, cap_bytes: int) -> int:
+    """HR rows per chunk of the init_q decode: the largest multiple of 8 (``decode_kernel``'s block rows) whose pixel planes,
+    ``b * rows * wu * 5120`` bytes, stay within ``cap_bytes``; at least 8."""
+    per_row = int(b) * int(wu) * (P_CHANNELS + HIDDEN) * 4
+    return max(8, (int(cap_bytes) // per_row) // 8 * 8)
+
+
+def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "") -> torch.Tensor:
+    """The formula sheet of the ``init_q=True``, mode-3 path in tensor algebra, in the RESTRUCTURED form the kernels run
+    (any device, any float dtype; the tests' one restatement, as ``encoder_training.rdb_backward_reference`` is for its path).
+
+    Reference (diinn.py:113-115,132-139,163-173), per HR pixel with LR cell (iy, ix)::
+
+        E  = sin(Fw . (rel_h, rel_w, ratio) + Fb)                576 values      first_layer
+        x' = E * X[:, iy, ix]                                     X = unfold3x3(feat), index c * 9 + 3 ky + kx, zero padded
+        k0 = relu(K0 . x' + bK0);            q0 = k0 * sin(Q0 . E + bQ0)
+        k_i = relu(K_i . [q_{i-1}; x'] + bK_i);  q_i = k_i * sin(Q_i . q_{i-1} + bQ_i),  i = 1..3;   out = L . q3 + bL
+
+    Restructured: the feature columns of K_0..3 are stacked into Wx [1024,576], so ``PIX[0:1024] = Wx . x' + bK`` and
+    ``PIX[1024:1280] = Q0 . E + bQ0`` are two GEMMs per pixel (``initq_planes_kernel``), and the layers read their seeds
+    there: ``k_i = relu(K_i[:, :256] . q_{i-1} + PIX[256 i : 256 i + 256])`` (``decode_kernel<SIN | DECODE_INITQ>``).  E depends on the
+    pixel only, not on the batch item.  Coordinates: the fp32 tables of ``axis_tables`` (the reference computes them in fp32
+    whatever the module's dtype); ``ratio`` is the Python double rounded to ``dtype``, as ``x.new_tensor`` does."""
+    def get(name, shape):
+        t = sd[prefix + name]
+        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
+        return t.to(device=feat.device, dtype=dtype).reshape(shape)
+
+    hu, wu = int(size[0]), int(size[1])
+    x = feat.to(dtype)
+    b, c, h, w = x.shape
+    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
+    iy, rel_h = axis_tables(h, hu, small)
+    ix, rel_w = axis_tables(w, wu, small)
+    dev = feat.device
+    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
+    syn = torch.empty((3, hu, wu), dtype=dtype, device=dev)
+    syn[0] = torch.from_numpy(rel_h).to(dev, dtype)[:, None]
+    syn[1] = torch.from_numpy(rel_w).to(dev, dtype)[None, :]
+    syn[2] = torch.tensor((h * w) / (hu * wu), dtype=dtype, device=dev)
+    n = hu * wu
+    e = torch.sin(get("first_layer.0.weight", (576, 3)) @ syn.reshape(3, n) + get("first_layer.0.bias", (576, 1)))   # [576, n]
+    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
+    xc = unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)
+    xp = e[None] * xc                                                                                              # [b, 576, n]
+    wx = torch.cat([get("K.0.0.weight", (HIDDEN, 576))] +
+                   [get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, HIDDEN:] for i in (1, 2, 3)], 0)          # [1024, 576]
+    bk = torch.cat([get(f"K.{i}.0.bias", (HIDDEN,)) for i in range(4)])[None, :, None]
+    pix = wx @ xp + bk                                                                                             # [b, 1024, n]
+    a0 = get("Q.0.0.weight", (HIDDEN, 576)) @ e + get("Q.0.0.bias", (HIDDEN, 1))                                   # [256, n]
+    q = torch.relu(pix[:, :HIDDEN]) * torch.sin(a0)[None]
+    for i in (1, 2, 3):
+        k = torch.relu(get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, :HIDDEN] @ q + pix[:, HIDDEN * i:HIDDEN * (i + 1)])
+        q = k * torch.sin(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1)))
+    out = get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))
+    return out.reshape(b, 3, hu, wu)
+
+
 def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     """((ty0, ty1), (r0, r1)): the HR rows whose tap values mode 4 needs for output rows [y0,y1) (one more row each way,
     clipped to the image) and the LR rows those read (C ABI ``diinn_mode4_rows``)."""
@@ -148,7 +235,8 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
                     out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     rows: Optional[Tuple[int, int]] = None, sin_mode: int = _native.SIN_DEFAULT,
                     compute: str = "f32", mode: int = 3, head: Optional[torch.Tensor] = None,
-                    taps: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    taps: Optional[torch.Tensor] = None, initq: Optional[torch.Tensor] = None,
+                    pix: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode encoder features ``feat`` [B,64,H,W] to RGB [B,3,Hu,Wu].
 
     ``rows=(y0,y1)`` computes only that HR row band (tile sharding across GPUs);
@@ -160,9 +248,18 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
     only.  Mode 4 (fp32 only) takes the body image as ``packed`` (``pack_state_dict(..., mode=4)``) and the 3x3 head
     image as ``head`` (``pack_head3x3``); ``taps`` is its second workspace, ``diinn_mode4_taps_bytes`` bytes for the
     rows decoded (allocated if None).  A row band of mode 4 is bit-identical to the same rows of a whole-image decode.
+    ``initq`` (mode 3, fp32 only): the init_q image (``pack_initq``) of an ``init_q=True`` decoder, with ``packed`` the body image
+    of ``initq_body_state_dict``; ``pix`` is its workspace, the pixel planes of the rows decoded (``diinn_initq_pix_bytes``,
+    5,120 bytes per HR pixel; allocated if None; ``workspace`` is not used).  A row band is bit-identical to the same rows of a
+    whole-image decode.
     Enqueues two kernels (three for modes 1/2: + the per-cell modulation chain; three for mode 4: + the 9-point
     gather) on the current stream; never synchronises."""
     lib = _native.load()
+    if initq is not None:
+        if mode != 3:
+            raise NotImplementedError(f"init_q=True is covered for mode 3 only (got mode {mode})")
+        if compute != "f32":
+            raise ValueError("init_q=True runs in fp32 only")
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
     if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
@@ -178,6 +275,23 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
         if out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
                 or out.device != feat.device:
             raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
+    if initq is not None:
+        _require_cuda(initq, "init_q image")
+        pneed = lib.diinn_initq_pix_bytes(b, wu, y1 - y0)
+        if pneed == 0 or y0 < 0 or y1 > hu:
+            raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
+        if pix is None:
+            pix = torch.empty(pneed // 4, dtype=torch.float32, device=feat.device)
+        elif pix.numel() * pix.element_size() < pneed or pix.dtype != torch.float32 or not pix.is_contiguous() \
+                or pix.device != feat.device:
+            raise ValueError(f"pix must be a contiguous fp32 buffer of >= {pneed} bytes on feat's device")
+        with torch.cuda.device(feat.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            st = lib.diinn_decode_initq(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                        C.c_void_p(initq.data_ptr()), C.c_void_p(pix.data_ptr()), C.c_void_p(out.data_ptr()),
+                                        b, h, w, hu, wu, y0, y1, int(sin_mode))
+        _native.check(st, "diinn_decode_initq")
+        return out
     need = lib.diinn_workspace_bytes(b, h, w)
     if workspace is None:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
@@ -453,7 +567,8 @@ class ImplicitDecoder(nn.Module):
     loads); the MI355X kernels implement the paper's final variant, ``mode=3,
     init_q=False`` (README.md:111-112 of the reference), the ablation modes 1 and 2, whose
     modulation branch depends on the LR cell only, and mode 4, mode 3 with a 3x3 reflect-padded
-    head (inference, fp32).  ``init_q=True`` raises ``NotImplementedError`` in ``forward``."""
+    head (inference, fp32).  ``init_q=True`` (the per-pixel sine embedding ``first_layer``, diinn.py:48-51,113-115) runs
+    for mode 3, inference, fp32; with modes 1, 2, 4 or under autograd ``forward`` raises ``NotImplementedError``."""
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32"):
@@ -488,8 +603,14 @@ class ImplicitDecoder(nn.Module):
         # mode 4: the head image (cached with the body image) and the tap workspaces, kept like the P workspaces
         self._packed_head: Optional[torch.Tensor] = None
         self._tap_workspaces: "Dict[tuple, torch.Tensor]" = {}
+        # init_q (mode 3): the first-layer / Q.0 image (cached with the body image) and the pixel-plane workspaces
+        self._packed_initq: Optional[torch.Tensor] = None
+        self._pix_workspaces: "Dict[tuple, torch.Tensor]" = {}
 
     _MAX_WORKSPACES = 4
+    # init_q decodes in chunks of HR rows whose pixel planes (5,120 bytes per pixel) stay within this many bytes: a memory cap
+    # (a 1024 x 1024 output would need 5 GiB at once), not a tuned number
+    INITQ_CHUNK_BYTES = 256 * 1024 * 1024
     # mode 4 decodes at most this many HR rows per call, which caps the tap buffer at B x 256 x Wu x 112 bytes.  254, not 256: a
     # middle chunk needs the tap values of one more row each way, and 256 tap rows are a whole number of decode_kernel's 8-row
     # blocks (258 rows start a 33rd block row: at 1024 x 1024 a ninth round of workgroups per chunk, 7.40 against 6.47 ms measured)
@@ -503,8 +624,9 @@ class ImplicitDecoder(nn.Module):
         key = self._weights_key(device)
         if self._packed is None or self._packed_key != key:
             sd = self.state_dict()
-            self._packed = pack_state_dict(sd, mode=self.mode).to(device)
+            self._packed = pack_state_dict(initq_body_state_dict(sd) if self.init_q else sd, mode=self.mode).to(device)
             self._packed_head = pack_head3x3(sd).to(device) if self.mode == 4 else None
+            self._packed_initq = pack_initq(sd).to(device) if self.init_q else None
             self._packed_key = key
         return self._packed
 
@@ -515,11 +637,18 @@ class ImplicitDecoder(nn.Module):
         self.packed_weights(device)
         return self._packed_head
 
+    def packed_initq(self, device) -> torch.Tensor:
+        """``init_q=True``: the first-layer / Q.0 image on ``device`` (packed and cached together with the body image)."""
+        if not self.init_q:
+            raise ValueError("only init_q=True has an init_q image")
+        self.packed_weights(device)
+        return self._packed_initq
+
     def _check_supported(self):
-        if self.mode not in (1, 2, 3, 4) or self.init_q:
+        if self.mode not in (1, 2, 3, 4) or (self.init_q and self.mode != 3):
             raise NotImplementedError(
                 f"diinn_amd HIP decode path implements modes 1-4 with init_q=False (mode 3 is the reference's "
-                f"final model; init_q=True is not covered); got mode={self.mode}, init_q={self.init_q}")
+                f"final model) and init_q=True for mode 3, which is covered; got mode={self.mode}, init_q={self.init_q}")
         if self.in_channels != IN_CHANNELS or self.hidden_dims != [HIDDEN] * 4:
             raise NotImplementedError("diinn_amd HIP decode path is built for in_channels=64, hidden_dims=[256]*4")
 
@@ -534,16 +663,23 @@ class ImplicitDecoder(nn.Module):
         Mode 4: the reference's ``batched_step`` applies the head's reflect padding at every column-strip edge, so
         the reference's own result depends on ``bsize`` there.  This path reproduces ``bsize=None``, the whole-image
         convolution, for any ``bsize``.  Inference only (``torch.no_grad()``), fp32; the image is decoded in chunks
-        of at most ``MODE4_CHUNK_ROWS`` HR rows, which bounds the tap workspace and changes no bit of the result."""
+        of at most ``MODE4_CHUNK_ROWS`` HR rows, which bounds the tap workspace and changes no bit of the result.
+
+        ``init_q=True`` (mode 3, fp32, inference only): the per-pixel planes the two kernels hand over take 5,120 bytes per
+        HR pixel, so the image is decoded in chunks of ``initq_chunk_rows(B, W_up, INITQ_CHUNK_BYTES)`` HR rows; chunking
+        changes no bit of the result either.  ``bsize=30000`` and ``bsize=None`` give the same bits, as in the reference."""
         self._check_supported()
         wants_grad = bsize is None and torch.is_grad_enabled() and (
             x.requires_grad or any(p.requires_grad for p in self.parameters()))
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
-        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32"):
+        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or self.init_q):
             raise NotImplementedError(
-                "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 (mode 3 is the reference's "
-                "final model, modes 1/2 its ablations); call mode 4 or the bf16 path under torch.no_grad()")
+                "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
+                "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
+                "torch.no_grad()")
+        if self.init_q and self.compute != "f32":
+            raise ValueError("init_q=True runs in fp32 only")
         _require_cuda(x, "x")
         if wants_grad:
             from .training import decode_with_grad
@@ -567,6 +703,18 @@ class ImplicitDecoder(nn.Module):
                 ws = cache[key] = torch.empty(numel, dtype=torch.float32, device=x.device)
             return ws
 
+        if self.init_q:
+            hu, wu = size
+            hu, wu = int(hu), int(wu)
+            chunk = initq_chunk_rows(b, wu, self.INITQ_CHUNK_BYTES)
+            pix = cached(self._pix_workspaces, b * min(chunk, hu) * wu * (P_CHANNELS + HIDDEN))
+            with torch.no_grad():
+                packed = self.packed_weights(x.device)
+                out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
+                for y0 in range(0, hu, chunk):
+                    decode_features(x, packed, (hu, wu), out=out, rows=(y0, min(hu, y0 + chunk)), sin_mode=self.sin_mode,
+                                    initq=self._packed_initq, pix=pix)
+                return out
         workspace = cached(self._workspaces, need)
         with torch.no_grad():
             packed = self.packed_weights(x.device)

@@ -426,6 +426,9 @@ class DIINN(nn.Module, _GraphReplay):
     def __init__(self, mode, init_q, graphs: bool = False):
         super().__init__()
         self.encoder = make_rdn()
+        if graphs and init_q:
+            raise NotImplementedError("DIINN(init_q=True, graphs=True): graph replay of the init_q decoder's chunk loop is not "
+                                      "covered; construct with graphs=False")
         self.decoder = ImplicitDecoder(mode=mode, init_q=init_q)
         self._init_graphs(graphs)
 

@@ -76,15 +76,19 @@ def normalish(seed: int, name: str, shape) -> np.ndarray:
     return acc.astype(np.float32).reshape(shape)
 
 
-def decoder_param_shapes(mode: int = 3) -> "OrderedDict[str, tuple]":
-    """Reference ``ImplicitDecoder(mode=mode, init_q=False).state_dict()`` layout
+def decoder_param_shapes(mode: int = 3, init_q: bool = False) -> "OrderedDict[str, tuple]":
+    """Reference ``ImplicitDecoder(mode=mode, init_q=init_q).state_dict()`` layout
     (diinn.py:53-92).  Mode 1 chains k -> K[i] (256 inputs); modes 2-4 feed
     [k or q ; unfolded features] (832 inputs).  Mode 4's head is the 3x3 conv of diinn.py:89-90; tensors are drawn by
-    name, so every other tensor (and every tensor of modes 1-3) keeps its bits."""
+    name, so every other tensor (and every tensor of modes 1-3) keeps its bits.  ``init_q`` (diinn.py:48-51) adds ``first_layer.0``
+    (Conv2d(3, 576, 1)) and widens ``Q.0.0.weight`` to 576 inputs."""
     shapes: "OrderedDict[str, tuple]" = OrderedDict()
+    if init_q:
+        shapes["first_layer.0.weight"] = (UNFOLD, 3, 1, 1)
+        shapes["first_layer.0.bias"] = (UNFOLD,)
     for i in range(N_LAYERS):
         kin = UNFOLD if i == 0 else (HIDDEN if mode == 1 else HIDDEN + UNFOLD)
-        qin = 3 if i == 0 else HIDDEN
+        qin = (UNFOLD if init_q else 3) if i == 0 else HIDDEN
         shapes[f"K.{i}.0.weight"] = (HIDDEN, kin, 1, 1)
         shapes[f"K.{i}.0.bias"] = (HIDDEN,)
         shapes[f"Q.{i}.0.weight"] = (HIDDEN, qin, 1, 1)
@@ -98,22 +102,27 @@ SIREN_Q_GAIN = (30.0, math.sqrt(6.0))
 
 
 def decoder_state_dict(seed: int = 123, gain: float = 1.0, mode: int = 3,
-                       q_gain=None) -> "OrderedDict[str, np.ndarray]":
+                       q_gain=None, init_q: bool = False) -> "OrderedDict[str, np.ndarray]":
     """Synthetic decoder weights in the reference's state_dict naming.
 
     ``gain`` scales every tensor (gain=3 is the SURVEY §8(d2) stress set:
     larger sine arguments and output magnitude).  ``q_gain = (first, hidden)`` additionally scales the
     synthesis branch's WEIGHTS (``Q.0.0.weight`` by ``first``, ``Q.1..3.0.weight`` by ``hidden``; biases and
     every other tensor untouched): ``SIREN_Q_GAIN`` = (30, sqrt 6) is the trained-SIREN range -- layer-0 sine
-    arguments of tens of radians on the raw coordinates (reference diinn.py:61-62,134) with |out| still O(1)."""
+    arguments of tens of radians on the raw coordinates (reference diinn.py:61-62,134) with |out| still O(1).
+
+    ``init_q=True`` adds ``first_layer.0.weight`` [576,3,1,1] / ``.bias`` (bound 1/sqrt 3) and draws ``Q.0.0.weight`` as
+    [256,576,1,1] (bound 1/sqrt 576, which is also ``Q.0.0.bias``'s bound then) under a generator name of its own; tensors
+    are drawn by name, so every tensor of the ``init_q=False`` calls keeps its bits."""
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
-    shapes = decoder_param_shapes(mode)
+    shapes = decoder_param_shapes(mode, init_q)
     for name, shape in shapes.items():
         layer = name.rsplit(".", 1)[0] + ".weight"
         wshape = shapes[layer]
         fan_in = wshape[1] * wshape[2] * wshape[3]
         bound = 1.0 / math.sqrt(fan_in)
-        sd[name] = (uniform(seed, name, shape, bound) * np.float32(gain)).astype(np.float32)
+        draw = name + ":init_q" if init_q and name.startswith("Q.0.0.") else name
+        sd[name] = (uniform(seed, draw, shape, bound) * np.float32(gain)).astype(np.float32)
         if q_gain is not None and name.startswith("Q.") and name.endswith(".weight"):
             sd[name] = (sd[name] * np.float32(q_gain[0] if name.startswith("Q.0.") else q_gain[1])).astype(np.float32)
     return sd

@@ -284,6 +284,45 @@ int    diinn_decode_mode4(void* stream, const float* feat_dev, const float* pack
                           float* workspace_dev, float* taps_dev, float* out_dev,
                           int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
 
+/* ---- decoder init_q=True, mode 3: the per-pixel sine embedding (diinn.py:48-51,113-115) -----------------------
+ * With init_q the synthesis input (rel_h, rel_w, ratio) first goes through first_layer = Conv2d(3, 576, 1) + sin, the
+ * result multiplies the unfolded features of the pixel's LR cell, and Q.0 is 256 x 576 and reads the embedding:
+ *     E  = sin(Fw . (rel_h, rel_w, ratio) + Fb)                     576 values per HR pixel
+ *     x' = E * X[cell]                                               X = unfold3x3(feat) of the pixel's cell
+ *     k0 = relu(K0 . x' + bK0);  q0 = k0 * sin(Q0 . E + bQ0)
+ *     k_i = relu(K_i . [q_{i-1}; x'] + bK_i),  q_i = k_i * sin(Q_i . q_{i-1} + bQ_i),  i = 1..3;   out = L . q3 + bL
+ * x' depends on the HR pixel, so the hoisted conv per LR cell is gone: Wx . x' (1024 x 576) and Q0 . E (256 x 576) are
+ * per-pixel GEMMs (initq_planes_kernel, fp32 MFMA) whose result, the PIXEL PLANES, feeds the register-resident decode
+ * kernel in place of P.  fp32 only; inference only; every sine_mode.
+ *
+ * IMAGES.  The body image is diinn_pack_weights of the K / Q.1..3 / head tensors with a ZERO [256][3] in place of Q0w (and
+ * any Q0b): its Q0 rows are never read.  The second image, diinn_pack_initq(Fw [576][3], Fb [576], Q0w [256][576],
+ * Q0b [256]), writes diinn_initq_packed_floats() floats, everything divided by 2 pi (sines run in revolutions):
+ *     [4][576]   Fw[:, 0], Fw[:, 1], Fw[:, 2], Fb        (unfolded order n = c * 9 + 3 ky + kx)
+ *     [mp 4][kg 72][t 2][lane 64][e 4]   Q0w[ 32 (2 mp + t) + (lane & 31) ][ c * 9 + tap ],  k-step kk = 4 kg + e:
+ *                tap = kk / 32, c = 2 (kk % 32) + (lane >> 5)        (the piece order of section 1, WP)
+ *     [256]      Q0b,  then the image's validity word DIINN_INITQ_MAGIC (without it every output is NaN).
+ *
+ * PIXEL PLANES.  pix_dev is [B][y1 - y0][Wu][1280] floats for the HR rows [y0,y1) of one call, diinn_initq_pix_bytes(B,
+ * Wu, y1 - y0) bytes (0 for invalid arguments): channels 0..1023 = Wx . x' + bK (layer i at 256 i), channels 1024..1279 =
+ * (Q0 . E + bQ0) / (2 pi).
+ *
+ * diinn_initq_planes:      feat_dev [B,64,H,W] -> pix_dev for rows [y0,y1).
+ * diinn_decode_initq_band: pix_dev of rows [y0,y1) -> out_dev[b, :, y0:y1, :] of a contiguous [B,3,Hu,Wu] tensor.
+ * diinn_decode_initq:      both in order.  A band is BIT-IDENTICAL to the same rows of a whole-image decode (no pixel's
+ *   arithmetic depends on the band).  Invalid arguments return DIINN_ERR_INVALID_ARG; none allocates or synchronises. */
+#define DIINN_INITQ_MAGIC 0x44494951u   /* "DIIQ" */
+size_t diinn_initq_packed_floats(void);
+int    diinn_pack_initq(const float* Fw, const float* Fb, const float* Q0w, const float* Q0b, float* packed);
+size_t diinn_initq_pix_bytes(int B, int Wu, int rows);
+int    diinn_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                          float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                               int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                          float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                          int sin_mode);
+
 /* ---- training ------------------------------------
  * TILED PLANES.  Every per-pixel training buffer is a group of C channel rows over npix = B*Hu*Wu
  * pixels (pixel index (b*Hu + y)*Wu + x), stored as [ceil(npix/32) tiles][C rows][32 pixels] fp32:
