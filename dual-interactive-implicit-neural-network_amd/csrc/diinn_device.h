@@ -15,6 +15,7 @@
 //   diinn_training.hip         backward pass: bwd_head / bwd_layer (<KPART=false>: modes 1/2), cell_chain_bwd (modes 1/2), plane_gemm, plane_rowdot, cell_sum
 //   diinn_enc_training.hip     the encoder's dense blocks under autograd: conv_wgrad (weight-gradient GEMM over the pixel axis), relu_gate
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
+//   diinn_metasr_training.hip  metasr_bwd_cells_kernel (MetaSR under autograd: the per-cell backward pass)
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))
 //   diinn_conv_x3.hip          RDN trunk, optional split-bf16 arithmetic: conv3x3_x3m_kernel / conv3x3_x3_kernel (3x3 layers), conv1x1_x3_kernel (fusion)

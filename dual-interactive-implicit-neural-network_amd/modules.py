@@ -547,7 +547,10 @@ class LIIF(nn.Module, _GraphReplay):
 class MetaSR(nn.Module, _GraphReplay):
     """The MetaSR comparison model (reference metasr.py:22-135; Hu et al. 2019 as re-implemented by LIIF)
     behind ``forward(inp, size, bsize=None)``: RDN encoder (PyTorch-ROCm) + the meta-upscale decoder on the
-    HIP path (``metasr_kernel``).  Inference only; ``bsize`` accepted and ignored."""
+    HIP path (``metasr_kernel``).  Under autograd with ``bsize=None`` -- the reference's training call, sr_module.py:127-129 --
+    the decoder runs through ``metasr_training.MetaSRFunction`` (the same forward kernels, the per-cell backward on the HIP
+    kernels; ROCm GPU only).  With ``bsize`` given the reference decodes under no_grad (``batched_predict``, metasr.py:106-117):
+    the output carries no graph, and ``bsize`` itself, a memory knob, is ignored.  Graph replay is inference-only."""
 
     def __init__(self, graphs: bool = False):
         super().__init__()
@@ -574,9 +577,18 @@ class MetaSR(nn.Module, _GraphReplay):
         feat = self.gen_feat(inp)
         return metasr_decode_features(feat, self._packed_weights(feat.device), size)
 
+    def _forward_train(self, inp, size):
+        from .metasr_training import decode_with_grad
+        if not inp.is_cuda:
+            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
+        return decode_with_grad(self.imnet, self.gen_feat(inp), size)
+
     def forward(self, inp, size, bsize=None):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("diinn_amd: MetaSR runs on the HIP path for inference only; call under torch.no_grad()")
+        if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if bsize is None:
+                return self._forward_train(inp, size)
+            with torch.no_grad():                                # batched_predict is no_grad in the reference: no graph
+                return self._forward_eager(inp, size, bsize)
         if self._use_graph(inp):
             return self._forward_graphed(inp, size, bsize)
         return self._forward_eager(inp, size, bsize)

@@ -170,6 +170,12 @@ def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor], mode: int = 
     w = _hoisted_conv_weight({name: t.detach() for name, t in zip(PARAM_NAMES, params)}, mode).to(torch.float64)
     if mode == 1:                                                # layers 1..3 of the conv are zero (the host packer's widened K.i)
         w = torch.cat([w, w.new_zeros((3 * HIDDEN, IN_CHANNELS, 3, 3))], 0)
+    _fill_wpu_weight(packed, w)
+
+
+def _fill_wpu_weight(packed: torch.Tensor, w: torch.Tensor) -> None:
+    """``_fill_wpu`` for any 1024-output 3x3 weight ``w`` [1024,64,3,3] (the MetaSR training image brings its own: metasr_training.py)."""
+    w = w.detach().to(torch.float64)
     g = torch.tensor(_WPU_G, dtype=torch.float64, device=w.device)
     gi = [g[:, a].view(1, 1, 4, 1) for a in range(3)]
     t = gi[0] * w[:, :, 0:1, :] + gi[1] * w[:, :, 1:2, :] + gi[2] * w[:, :, 2:3, :]          # [O, C, i 4, b 3]
@@ -304,7 +310,10 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
       input :  d_feat = conv3x3(dP; Wx transposed and flipped) -- a 64-output 3x3 convolution over 1024 planes, i.e. the
                encoder's convolution kernels (Winograd F(4x4) / F(2x2) / split-K by the same rule as the trunk).
     ``rows`` < 1024 (decoder mode 1: 256, only P_0 is a convolution of the features): the conv is Wx[:rows], i.e. the first
-    ``rows`` planes of ``dp`` [B,1024,H,W] / rows of ``a_t`` are used and ``wx`` is [rows,64,3,3]."""
+    ``rows`` planes of ``dp`` [B,1024,H,W] / rows of ``a_t`` are used and ``wx`` is [rows,64,3,3].
+    The weight and its cache key are the caller's: ``wx`` (a tensor, or a callable returning it, evaluated only when the
+    transposed weight has to be repacked), ``wkey`` (what identifies its values: the DIINN callers pass their K weights'
+    (address, version) pairs, MetaSR its own tagged tuple) and ``wpins`` (the tensors the key describes)."""
     from . import modules as M                                   # (pack functions; imported late: modules imports the decoder)
     lib = _native.load()
     b, c, h, w = feat.shape
@@ -348,6 +357,8 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
             key = (str(dev), wkey, rows)
             ent = _dgrad_pack.get((form, str(dev)))
             if wkey is None or ent is None or ent[0] != key:
+                if callable(wx):                                 # (a caller whose weight is itself derived builds it only for a repack)
+                    wx = wx()
                 wt = wx.flip(2, 3).permute(1, 0, 2, 3).contiguous()      # [64, 1024, 3, 3]
                 pk = (M.pack_conv_wino4(wt) if form == "wino4" else M.pack_conv_wino(wt) if form == "wino" else M.pack_conv_ksplit(wt))
                 ent = (key, pk, tuple(t.detach() for t in (wpins or ())))

@@ -465,6 +465,22 @@ size_t diinn_metasr_workspace_bytes(int B, int H, int W);
 int    diinn_metasr_decode(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
                            float* out_dev, int B, int H, int W, int Hu, int Wu);
 int    diinn_metasr_make_axis_tables(int n_in, int n_out, int32_t* idx, float* rel, float* r_rev);
+/* MetaSR under autograd (added under ABI 11, backward compatible): the per-cell half of the backward pass.  With
+ * W2r[n, comp, j] = W2[3n + comp, j] the decoder is out[comp] = sum_j h_j M[c][comp][j] + B0[c][comp] per HR pixel of LR cell c,
+ * h = relu(W1 (rel_h, rel_w, r_rev) + b1), where [M; B0] is a 3x3 convolution of the features with 771 outputs.  Given
+ *   gout_dev [B,3,Hu,Wu] = d loss / d out,  M_dev [B,H,W,1024] (row 256 comp + j; rows 768.. are not read: the layout
+ *   diinn_precompute_P_wpu writes),  packed_dev the MetaSR packed image (its W1 / b1 rows are read),  seg_h_dev [H+1] /
+ *   seg_w_dev [W+1] the first HR row / column of every LR row / column of diinn_metasr_make_axis_tables' index (last entry
+ *   Hu / Wu; the table is monotone, so a cell's pixels form a rectangle),
+ * it writes the gradient at that convolution's output, dM[c][comp][j] = sum over the cell's pixels of g[comp] h_j in rows
+ * 256 comp + j, dB0[c][comp] = sum of g[comp] in rows 768 + comp, zeros in rows 771..1023, in both layouts of
+ * diinn_backward_cell_sum: dM_dev NCHW [B][1024][H][W] and dM_tiled_dev [ceil(B H W / 32)][1024][32] (whole tiles are
+ * written, the padding of a ragged last tile as zeros); and part0_dev [2 ceil(B H W / 32)][256][4] (16-byte aligned), whose
+ * sum over the first axis (diinn_sum_parts) is [dW1 | db1].  A cell that owns no pixel gets zeros.  Fixed summation order,
+ * no atomics: deterministic.  One kernel; validates every argument first, allocates nothing, does not synchronise. */
+int    diinn_metasr_backward_cells(void* stream, const float* gout_dev, const float* M_dev, const float* packed_dev,
+                                   const int32_t* seg_h_dev, const int32_t* seg_w_dev, float* dM_dev, float* dM_tiled_dev,
+                                   float* part0_dev, int B, int H, int W, int Hu, int Wu);
 
 /* ---- RDN encoder trunk ------------------------------------
  * Replaces: RDN.forward after SFENet1 (rdn.py:95-105), config 'B' (16 RDBs x 8 dense 3x3 convs, growth 64,
