@@ -40,6 +40,13 @@ class SineAct(nn.Module):
 # ---------------------------------------------------------------------------
 # packed weights
 # ---------------------------------------------------------------------------
+def _host_array(sd, prefix: str, name: str, shape) -> np.ndarray:
+    """``sd[prefix + name]`` (a tensor or an array) as a contiguous fp32 host array of ``shape``."""
+    t = sd[prefix + name]
+    a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
+    return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
+
+
 def pack_state_dict(sd, prefix: str = "", mode: int = 3) -> torch.Tensor:
     """Reference-named decoder tensors -> packed host image (1-D fp32 CPU tensor).
 
@@ -51,29 +58,23 @@ def pack_state_dict(sd, prefix: str = "", mode: int = 3) -> torch.Tensor:
     second image (``pack_head3x3``).  Calls the C ABI ``diinn_pack_weights`` (include/diinn_hip.h)."""
     lib = _native.load()
 
-    def get(name, shape):
-        t = sd[prefix + name]
-        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
-        a = np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
-        return a
-
-    k0w = get("K.0.0.weight", (HIDDEN, 576)); k0b = get("K.0.0.bias", (HIDDEN,))
+    k0w = _host_array(sd, prefix, "K.0.0.weight", (HIDDEN, 576)); k0b = _host_array(sd, prefix, "K.0.0.bias", (HIDDEN,))
     if mode == 1:
         kw = []
         for i in (1, 2, 3):
             wide = np.zeros((HIDDEN, HIDDEN + 576), np.float32)
-            wide[:, :HIDDEN] = get(f"K.{i}.0.weight", (HIDDEN, HIDDEN))
+            wide[:, :HIDDEN] = _host_array(sd, prefix, f"K.{i}.0.weight", (HIDDEN, HIDDEN))
             kw.append(wide)
     else:
-        kw = [get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576)) for i in (1, 2, 3)]
-    kb = [get(f"K.{i}.0.bias", (HIDDEN,)) for i in (1, 2, 3)]
-    q0w = get("Q.0.0.weight", (HIDDEN, 3)); q0b = get("Q.0.0.bias", (HIDDEN,))
-    qw = [get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) for i in (1, 2, 3)]
-    qb = [get(f"Q.{i}.0.bias", (HIDDEN,)) for i in (1, 2, 3)]
+        kw = [_host_array(sd, prefix, f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576)) for i in (1, 2, 3)]
+    kb = [_host_array(sd, prefix, f"K.{i}.0.bias", (HIDDEN,)) for i in (1, 2, 3)]
+    q0w = _host_array(sd, prefix, "Q.0.0.weight", (HIDDEN, 3)); q0b = _host_array(sd, prefix, "Q.0.0.bias", (HIDDEN,))
+    qw = [_host_array(sd, prefix, f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) for i in (1, 2, 3)]
+    qb = [_host_array(sd, prefix, f"Q.{i}.0.bias", (HIDDEN,)) for i in (1, 2, 3)]
     if mode == 4:
         lw = np.zeros((3, HIDDEN), np.float32); lb = np.zeros((3,), np.float32)
     else:
-        lw = get("last_layer.weight", (3, HIDDEN)); lb = get("last_layer.bias", (3,))
+        lw = _host_array(sd, prefix, "last_layer.weight", (3, HIDDEN)); lb = _host_array(sd, prefix, "last_layer.bias", (3,))
 
     packed = np.empty(lib.diinn_packed_weight_floats(), dtype=np.float32)
     f3 = _native._f3
@@ -93,12 +94,7 @@ def pack_head3x3(sd, prefix: str = "") -> torch.Tensor:
     word)."""
     lib = _native.load()
 
-    def get(name, shape):
-        t = sd[prefix + name]
-        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
-        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
-
-    lw = get("last_layer.weight", (3, HIDDEN, 3, 3)); lb = get("last_layer.bias", (3,))
+    lw = _host_array(sd, prefix, "last_layer.weight", (3, HIDDEN, 3, 3)); lb = _host_array(sd, prefix, "last_layer.bias", (3,))
     packed = np.empty(lib.diinn_head3x3_packed_floats(), dtype=np.float32)
     _native.check(lib.diinn_pack_head3x3(_native.fptr(lw), _native.fptr(lb), _native.fptr(packed)), "diinn_pack_head3x3")
     return torch.from_numpy(packed)
@@ -112,13 +108,8 @@ def pack_initq(sd, prefix: str = "") -> torch.Tensor:
     [256,3] in place of ``Q.0.0.weight`` (``initq_body_state_dict``)."""
     lib = _native.load()
 
-    def get(name, shape):
-        t = sd[prefix + name]
-        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
-        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
-
-    fw, fb = get("first_layer.0.weight", (576, 3)), get("first_layer.0.bias", (576,))
-    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 576)), get("Q.0.0.bias", (HIDDEN,))
+    fw, fb = _host_array(sd, prefix, "first_layer.0.weight", (576, 3)), _host_array(sd, prefix, "first_layer.0.bias", (576,))
+    q0w, q0b = _host_array(sd, prefix, "Q.0.0.weight", (HIDDEN, 576)), _host_array(sd, prefix, "Q.0.0.bias", (HIDDEN,))
     packed = np.empty(lib.diinn_initq_packed_floats(), dtype=np.float32)
     _native.check(lib.diinn_pack_initq(_native.fptr(fw), _native.fptr(fb), _native.fptr(q0w), _native.fptr(q0b),
                                        _native.fptr(packed)), "diinn_pack_initq")
@@ -440,22 +431,18 @@ def pack_liif_state_dict(sd, prefix: str = "imnet.") -> torch.Tensor:
     with the slot mapping documented at ``diinn_liif_decode`` in include/diinn_hip.h: the 576 feature
     columns of layer 0 become the hoisted 3x3 conv, its 4 coordinate columns the Q0 table, layers 2/4/6
     the synthesis slots of the stacked per-pixel layers, layer 8 the RGB head."""
-    def get(name, shape):
-        t = sd[prefix + name]
-        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
-        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
-
-    w0 = get("layers.0.weight", (HIDDEN, 580))
+    w0 = _host_array(sd, prefix, "layers.0.weight", (HIDDEN, 580))
     mapped = {
-        "K.0.0.weight": w0[:, :576], "K.0.0.bias": get("layers.0.bias", (HIDDEN,)),
+        "K.0.0.weight": w0[:, :576], "K.0.0.bias": _host_array(sd, prefix, "layers.0.bias", (HIDDEN,)),
         "Q.0.0.weight": w0[:, 576:579], "Q.0.0.bias": w0[:, 579],
-        "last_layer.weight": get("layers.8.weight", (3, HIDDEN)), "last_layer.bias": get("layers.8.bias", (3,)),
+        "last_layer.weight": _host_array(sd, prefix, "layers.8.weight", (3, HIDDEN)),
+        "last_layer.bias": _host_array(sd, prefix, "layers.8.bias", (3,)),
     }
     for i, layer in ((1, 2), (2, 4), (3, 6)):
         mapped[f"K.{i}.0.weight"] = np.zeros((HIDDEN, HIDDEN + 576), np.float32)
         mapped[f"K.{i}.0.bias"] = np.zeros((HIDDEN,), np.float32)
-        mapped[f"Q.{i}.0.weight"] = get(f"layers.{layer}.weight", (HIDDEN, HIDDEN))
-        mapped[f"Q.{i}.0.bias"] = get(f"layers.{layer}.bias", (HIDDEN,))
+        mapped[f"Q.{i}.0.weight"] = _host_array(sd, prefix, f"layers.{layer}.weight", (HIDDEN, HIDDEN))
+        mapped[f"Q.{i}.0.bias"] = _host_array(sd, prefix, f"layers.{layer}.bias", (HIDDEN,))
     return pack_state_dict(mapped, mode=3)
 
 
@@ -470,10 +457,10 @@ def liif_axis_tables(n_in: int, n_out: int, v: int) -> Tuple[np.ndarray, np.ndar
     return idx, rel, cell.value
 
 
-def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
-                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """LIIF query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (liif.py:59-127,148-155)."""
-    lib = _native.load()
+def _comparison_decode(fn, fn_name: str, workspace_bytes, feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
+                       out: Optional[torch.Tensor], workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    """The LIIF / MetaSR decode of every HR pixel: ``fn`` (a library entry point with diinn_liif_decode's signature, ``fn_name`` for
+    the error message) with ``workspace_bytes(B, H, W)`` bytes of workspace; a ``workspace`` that is too small is replaced."""
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
     if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
@@ -487,15 +474,22 @@ def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequenc
     elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
             or out.device != feat.device:
         raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
-    need = lib.diinn_workspace_bytes(b, h, w)
+    need = workspace_bytes(b, h, w)
     if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
     with torch.cuda.device(feat.device):
         stream = torch.cuda.current_stream().cuda_stream
-        st = lib.diinn_liif_decode(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                   C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()), b, h, w, hu, wu)
-    _native.check(st, "diinn_liif_decode")
+        st = fn(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()), b, h, w, hu, wu)
+    _native.check(st, fn_name)
     return out
+
+
+def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
+                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LIIF query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (liif.py:59-127,148-155)."""
+    lib = _native.load()
+    return _comparison_decode(lib.diinn_liif_decode, "diinn_liif_decode", lib.diinn_workspace_bytes, feat, packed, size, out, workspace)
 
 
 # ---------------------------------------------------------------------------
@@ -506,13 +500,8 @@ def pack_metasr_state_dict(sd, prefix: str = "imnet.") -> torch.Tensor:
     image (C ABI ``diinn_metasr_pack_weights``)."""
     lib = _native.load()
 
-    def get(name, shape):
-        t = sd[prefix + name]
-        a = t.detach().to("cpu", torch.float32).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float32)
-        return np.ascontiguousarray(a.reshape(shape), dtype=np.float32)
-
-    w1, b1 = get("layers.0.weight", (HIDDEN, 3)), get("layers.0.bias", (HIDDEN,))
-    w2, b2 = get("layers.2.weight", (1728, HIDDEN)), get("layers.2.bias", (1728,))
+    w1, b1 = _host_array(sd, prefix, "layers.0.weight", (HIDDEN, 3)), _host_array(sd, prefix, "layers.0.bias", (HIDDEN,))
+    w2, b2 = _host_array(sd, prefix, "layers.2.weight", (1728, HIDDEN)), _host_array(sd, prefix, "layers.2.bias", (1728,))
     packed = np.empty(lib.diinn_metasr_packed_floats(), dtype=np.float32)
     _native.check(lib.diinn_metasr_pack_weights(_native.fptr(w1), _native.fptr(b1), _native.fptr(w2), _native.fptr(b2),
                                                 _native.fptr(packed)), "diinn_metasr_pack_weights")
@@ -533,28 +522,8 @@ def metasr_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Seque
                            out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """MetaSR query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (metasr.py:70-104,125-135)."""
     lib = _native.load()
-    _require_cuda(feat, "feat")
-    _require_cuda(packed, "packed weights")
-    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
-        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
-    hu, wu = size
-    hu, wu = int(hu), int(wu)
-    feat = feat.contiguous()
-    b, _, h, w = feat.shape
-    if out is None:
-        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
-    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != feat.device:
-        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
-    need = lib.diinn_metasr_workspace_bytes(b, h, w)
-    if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
-    with torch.cuda.device(feat.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        st = lib.diinn_metasr_decode(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                     C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()), b, h, w, hu, wu)
-    _native.check(st, "diinn_metasr_decode")
-    return out
+    return _comparison_decode(lib.diinn_metasr_decode, "diinn_metasr_decode", lib.diinn_metasr_workspace_bytes, feat, packed, size, out,
+                              workspace)
 
 
 # ---------------------------------------------------------------------------

@@ -25,7 +25,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _native
+from . import _native, convs
+from .convs import _ptr
 
 G0 = 64                     # channels of a block's input and output
 GROWTH = 64                 # channels every dense layer appends
@@ -95,13 +96,7 @@ _block_packs: Dict[tuple, tuple] = {}
 BLOCK_PACKS_MAX = 128       # 16 blocks x the forms a multi-scale run alternates between, for a few models
 
 
-def _pack3x3(weight: torch.Tensor, form: str) -> torch.Tensor:
-    from . import modules as M                                   # (imported late: modules imports this module's users)
-    return M.pack_conv_wino4(weight) if form == "wino4" else M.pack_conv_wino(weight) if form == "wino" else M.pack_conv_ksplit(weight)
-
-
 def _packs(params: Sequence[torch.Tensor], form: str, dev, backward: bool):
-    from . import modules as M
     ws = [p.detach() for p in params[0:2 * LAYERS + 1:2]]        # W_0..W_7, W_LFF
     key = (form, str(dev)) + tuple(t.data_ptr() for t in ws)
     versions = tuple(t._version for t in ws)
@@ -109,12 +104,12 @@ def _packs(params: Sequence[torch.Tensor], form: str, dev, backward: bool):
     if ent is None or ent[0] != versions:
         ent = (versions, None, None, tuple(ws))
     if ent[1] is None:
-        fwd = [_pack3x3(ws[c], form) for c in range(LAYERS)] + [M.pack_conv_ksplit(ws[LAYERS])]
+        fwd = [convs.pack_conv3x3(ws[c], form) for c in range(LAYERS)] + [convs.pack_conv_ksplit(ws[LAYERS])]
         ent = (versions, fwd, ent[2], ent[3])
     if backward and ent[2] is None:
-        bwd = [_pack3x3(transposed_weight(ws, j), form) for j in range(LAYERS)]
+        bwd = [convs.pack_conv3x3(transposed_weight(ws, j), form) for j in range(LAYERS)]
         lff_t = ws[LAYERS].reshape(G0, LAYERS + 1, GROWTH).permute(1, 2, 0)          # [group, o, co] = W_LFF[co, 64 group + o]
-        bwd += [M.pack_conv_ksplit(lff_t[k].reshape(GROWTH, G0, 1, 1)) for k in range(LAYERS + 1)]
+        bwd += [convs.pack_conv_ksplit(lff_t[k].reshape(GROWTH, G0, 1, 1)) for k in range(LAYERS + 1)]
         ent = (versions, ent[1], bwd, ent[3])
     while len(_block_packs) >= BLOCK_PACKS_MAX:
         _block_packs.pop(next(iter(_block_packs)))
@@ -122,17 +117,7 @@ def _packs(params: Sequence[torch.Tensor], form: str, dev, backward: bool):
     return ent[1], ent[2]
 
 
-def choose_form(b: int, h: int, w: int) -> str:
-    """The trunk's rule (and training._conv_grads_native's): F(4x4) where diinn_rdn_wino4_applies, else F(2x2) from
-    DIINN_ENC_WINO_MIN pixels, else the split-K kernel."""
-    lib = _native.load()
-    if lib.diinn_rdn_wino4_applies(b, h, w):
-        return "wino4"
-    return "wino" if b * h * w >= _native.debug_get("DIINN_ENC_WINO_MIN") else "ksplit"
-
-
-def _ptr(t: Optional[torch.Tensor], offset: int = 0):
-    return None if t is None else C.c_void_p(t.data_ptr() + 4 * offset)
+choose_form = convs.conv_form    # the trunk's rule, which training._conv_grads_native follows as well
 
 
 class _Launcher:
@@ -143,24 +128,11 @@ class _Launcher:
         self.form, self.dev, self.b, self.h, self.w = form, dev, b, h, w
         self.hw = h * w
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self.ws = None
-        if form == "wino4":
-            from . import modules as M
-            self.ws = M.RDN._w4_area(dev)                         # the split area of this (device, stream)
+        self.ws = convs.w4_area(dev) if form == "wino4" else None    # the split area of this (device, stream)
 
     def conv3x3(self, inp, in_off, in_bs, cin, pk, bias, res, res_off, res_bs, out, out_off, out_bs, relu):
-        lib, b, h, w = self.lib, self.b, self.h, self.w
-        if self.form == "wino4":
-            self.ws[:512].zero_()                                # the arrival counters, as the trunk does (never the sticky status word)
-            _native.check(lib.diinn_conv_wino4_ws(self.stream, _ptr(inp, in_off), in_bs, cin, _ptr(pk), _ptr(bias), _ptr(res, res_off),
-                                                  res_bs, _ptr(out, out_off), out_bs, relu, b, h, w, _ptr(self.ws), self.ws.numel()),
-                          "diinn_conv_wino4_ws")
-        elif self.form == "wino":
-            _native.check(lib.diinn_conv_wino(self.stream, _ptr(inp, in_off), in_bs, cin, _ptr(pk), _ptr(bias), _ptr(res, res_off),
-                                              res_bs, _ptr(out, out_off), out_bs, relu, b, h, w), "diinn_conv_wino")
-        else:
-            _native.check(lib.diinn_conv_ksplit(self.stream, _ptr(inp, in_off), in_bs, cin, 9, _ptr(pk), _ptr(bias), _ptr(res, res_off),
-                                                res_bs, _ptr(out, out_off), out_bs, None, 0, relu, b, h, w), "diinn_conv_ksplit")
+        convs.launch_conv3x3(self.form, self.stream, self.ws, self.b, self.h, self.w, inp, in_off, in_bs, cin, pk, bias,
+                             res, res_off, res_bs, out, out_off, out_bs, relu)
 
     def conv1x1(self, inp, in_off, in_bs, cin, pk, bias, res, res_bs, out, out_off, out_bs):
         _native.check(self.lib.diinn_conv_ksplit(self.stream, _ptr(inp, in_off), in_bs, cin, 1, _ptr(pk), _ptr(bias), _ptr(res), res_bs,
@@ -207,7 +179,7 @@ def rdb_forward_buffer(x: torch.Tensor, params: Sequence[torch.Tensor], form: st
     dev = x.device
     hw = h * w
     if form == "auto":
-        form = choose_form(b, h, w)
+        form = convs.conv_form(b, h, w)
     fwd, _ = _packs(params, form, dev, backward=False)
     buf = torch.empty((b, DENSE, h, w), dtype=torch.float32, device=dev)
     buf[:, :G0] = x

@@ -155,13 +155,7 @@ def pack_gather_index() -> torch.Tensor:
     global _pack_index_cpu
     if _pack_index_cpu is None:
         from .decoder import pack_metasr_state_dict
-        sd, pos = {}, 1
-        for name in PARAM_NAMES:
-            k = int(np.prod(PARAM_SHAPES[name]))
-            sd[name] = np.arange(pos, pos + k, dtype=np.float32).reshape(PARAM_SHAPES[name])
-            pos += k
-        total = pos - 1
-        assert total < (1 << 24)
+        sd, total = T.position_state_dict(PARAM_NAMES, PARAM_SHAPES)
         idx = np.rint(pack_metasr_state_dict(sd, prefix="").numpy()).astype(np.int64) - 1
         if idx.min() < 0 or idx.max() >= total or np.unique(idx).size != total or idx.size != total:
             raise RuntimeError("the MetaSR packed image is not a permutation of the imnet tensors")
@@ -272,19 +266,8 @@ class MetaSRFunction(torch.autograd.Function):
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, *params: torch.Tensor) -> torch.Tensor:
         from .decoder import metasr_decode_features
         lib = _native.load()
-        if not feat.is_cuda:
-            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
-        if len(params) != len(PARAM_NAMES):
-            raise ValueError(f"expected {len(PARAM_NAMES)} parameter tensors in PARAM_NAMES order")
-        for name, p_ in zip(PARAM_NAMES, params):
-            if tuple(p_.shape) != PARAM_SHAPES[name]:
-                raise ValueError(f"{name}: expected shape {PARAM_SHAPES[name]}, got {tuple(p_.shape)}")
-        feat_c = feat.detach().contiguous().to(torch.float32)
-        if feat_c.dim() != 4 or feat_c.shape[1] != T.IN_CHANNELS:
-            raise ValueError(f"feat must be [B,{T.IN_CHANNELS},H,W]")
+        feat_c = T.checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, ROWS)
         b, _, h, w = feat_c.shape
-        if lib.diinn_training_plane_floats(b * hu * wu, ROWS) < 0:
-            raise RuntimeError(f"diinn_amd: B*Hu*Wu = {b * hu * wu} HR pixels in one training forward exceeds the limit; split the batch")
         packed, image, wx = images_on_device(params)
         out = metasr_decode_features(feat_c, packed, (hu, wu))
         m = torch.empty((b, h, w, ROWS), dtype=torch.float32, device=feat_c.device)

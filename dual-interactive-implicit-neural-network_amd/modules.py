@@ -21,6 +21,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import convs
+from .convs import (_WINO4_G, _winograd_weight, pack_conv_ksplit, pack_conv_wino, pack_conv_wino4,  # noqa: F401  (re-exported:
+                    pack_conv_x3)                                                                   # the weight images live in convs.py)
 from .decoder import ImplicitDecoder
 from .metrics import calc_psnr, psnr, resize_fn, ssim  # noqa: F401  (re-exported like the reference's sr_module)
 
@@ -79,80 +82,6 @@ class RDB(nn.Module):
             buf[:, c_in:c_in + g] = F.relu(F.conv2d(buf[:, :c_in], conv.weight, conv.bias, padding=conv.padding))
             c_in += g
         return self.LFF(buf) + x
-
-
-def pack_conv_ksplit(weight: torch.Tensor) -> torch.Tensor:
-    """Conv weight [64, Cin, kh, kw] (Cin % 64 == 0; 3x3 or 1x1) -> the layout ``diinn_conv_ksplit`` reads
-    (include/diinn_hip.h): [half 2][wave 8][tap][group][lane 64][4] with cout = 32 half + (lane & 31) and
-    input channel = wave*Cin/8 + 8 group + 2 e + (lane >> 5)."""
-    co, cin, kh, kw = weight.shape
-    if co != 64 or cin % 64 or (kh, kw) not in ((3, 3), (1, 1)):
-        raise ValueError(f"unsupported convolution shape {tuple(weight.shape)}")
-    taps, groups = kh * kw, cin // 64
-    w = weight.detach().to(torch.float32).reshape(2, 32, 8, groups, 4, 2, taps)     # [half, i, wave, g, e, h, tap]
-    return w.permute(0, 2, 6, 3, 5, 1, 4).reshape(-1)                               # [half, wave, tap, g, h, i, e]
-
-
-def _winograd_weight(weight: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    """U = G W G^T per (output, input) pair, [O, C, 3, 3] -> [O, C, R, R], in ``g``'s dtype as plain broadcast products and sums
-    (left to right, (G W) first: the host packer's order for the decoder's hoisted conv) -- not an einsum, which would run a
-    library GEMM per call (the training step re-packs the input gradient's weight whenever a parameter changed)."""
-    w = weight.detach().to(g.dtype)
-    r = g.shape[0]
-    gi = [g[:, a].view(1, 1, r, 1) for a in range(3)]
-    t = gi[0] * w[:, :, 0:1, :] + gi[1] * w[:, :, 1:2, :] + gi[2] * w[:, :, 2:3, :]          # [O, C, R, 3]
-    gj = [g[:, b].view(1, 1, 1, r) for b in range(3)]
-    return t[..., 0:1] * gj[0] + t[..., 1:2] * gj[1] + t[..., 2:3] * gj[2]                   # [O, C, R, R]
-
-
-def pack_conv_wino(weight: torch.Tensor, dtype: torch.dtype = torch.float64) -> torch.Tensor:
-    """3x3 conv weight [64, Cin, 3, 3] (Cin % 8 == 0) -> the Winograd F(2x2, 3x3) image ``diinn_conv_wino`` reads
-    (include/diinn_hip.h): U = G W G^T per (output, input) pair, computed in float64 and rounded once, laid out
-    [row i 4][chunk Cin/8][col j 4][half 2][lane 64][4] with cout = 32 half + (lane & 31) and input channel =
-    8 chunk + 2 e + (lane >> 5); column j = 2 is stored negated."""
-    co, cin, kh, kw = weight.shape
-    if co != 64 or cin % 8 or (kh, kw) != (3, 3):
-        raise ValueError(f"unsupported convolution shape {tuple(weight.shape)}")
-    g = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=dtype,
-                     device=weight.device)                       # on the weight's device: 1.4 s for the trunk on the CPU, ms on the GPU
-    u = _winograd_weight(weight, g).to(torch.float32)
-    u[..., 2] = -u[..., 2]                                      # the kernel's input transform produces column 2 negated
-    u = u.reshape(2, 32, cin // 8, 4, 2, 4, 4)                  # [half, m, chunk, e, h, i, j]
-    return u.permute(5, 2, 6, 0, 4, 1, 3).reshape(-1)           # [i, chunk, j, half, h, m, e]
-
-
-_WINO4_G = ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6), (0, 0, 1))
-
-
-def pack_conv_wino4(weight: torch.Tensor, dtype: torch.dtype = torch.float64) -> torch.Tensor:
-    """3x3 conv weight [64, Cin, 3, 3] (Cin % 8 == 0) -> the Winograd F(4x4, 3x3) image ``diinn_conv_wino4`` reads
-    (include/diinn_hip.h): U = G W G^T (6x6 per (output, input) pair), computed in float64 and rounded once, laid out
-    [wave 12][half 2][chunk Cin/8][q 3][lane 64][4] with position 6 i + j = 3 wave + q, cout = 32 half + (lane & 31)
-    and input channel = 8 chunk + 2 e + (lane >> 5)."""
-    co, cin, kh, kw = weight.shape
-    if co != 64 or cin % 8 or (kh, kw) != (3, 3):
-        raise ValueError(f"unsupported convolution shape {tuple(weight.shape)}")
-    g = torch.tensor(_WINO4_G, dtype=dtype, device=weight.device)
-    u = _winograd_weight(weight, g).to(torch.float32)
-    u = u.reshape(2, 32, cin // 8, 4, 2, 12, 3)                 # [half, m, chunk, e, h, wave, q]
-    return u.permute(5, 0, 2, 6, 4, 1, 3).reshape(-1)           # [wave, half, chunk, q, h, m, e]
-
-
-def pack_conv_x3(weight: torch.Tensor) -> torch.Tensor:
-    """Conv weight [64, Cin, k, k] (k = 3 or 1, Cin % 16 == 0) -> the split-bf16 image ``diinn_conv3x3_x3`` and the trunk's
-    split-bf16 fusion layer read (include/diinn_hip.h): every weight as hi = bf16(w), lo = bf16(w - hi), laid out
-    [group Cin/16][tap k*k][M-tile 2][hi, lo][lane 64][8 bf16] with cout = 32 mt + (lane & 31) and input channel =
-    16 group + 8 (lane >> 5) + j; returned as float32 words (two bf16 each), k*k * 64 * Cin of them."""
-    co, cin, kh, kw = weight.shape
-    if co != 64 or cin % 16 or (kh, kw) not in ((3, 3), (1, 1)):
-        raise ValueError(f"unsupported convolution shape {tuple(weight.shape)}")
-    taps = kh * kw
-    w = weight.detach().to(torch.float32)
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.to(torch.float32)).to(torch.bfloat16)
-    parts = torch.stack([hi, lo], 0).reshape(2, 2, 32, cin // 16, 2, 8, taps)       # [part, mt, m, g, h, j, tap]
-    img = parts.permute(3, 6, 1, 0, 4, 2, 5).contiguous()                           # [g, tap, mt, part, h, m, j]
-    return img.view(torch.int16).reshape(-1, 2).view(torch.int32).reshape(-1).view(torch.float32)
 
 
 class RDN(nn.Module):
@@ -250,49 +179,9 @@ class RDN(nn.Module):
                                      [pack_conv_x3(rdb.LFF.weight.to(device)) for rdb in self.RDBs]).to(device)
         return self._hip_x3
 
-    # the F(4x4) kernel's split area (34.6 MB: control words + partial-output slabs), ONE per (device, stream), kept across
-    # forwards: its sticky status word then remembers a hand-off that ever gave up (handoff_status()); two streams never
-    # share slabs or tickets.  Class-wide: every RDN of the process on that (device, stream) may use it (launches on one
-    # stream are ordered).
-    _w4_areas: dict = {}
-    _W4_AREAS_MAX = 16
-
-    @classmethod
-    def _w4_area(cls, device):
-        from . import _native
-        floats = _native.load().diinn_conv_wino4_workspace_floats()
-        if torch.cuda.is_current_stream_capturing():
-            # inside a hipGraph capture the area comes from the graph's private pool and lives with the graph (its control
-            # words are zeroed by a captured memset: a replay starts clean; a give-up is still NaN in that replay's output)
-            ws = torch.empty(floats, dtype=torch.float32, device=device)
-            ws[:1024].zero_()
-            return ws
-        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = cls._w4_areas.get(key)
-        if ws is None:
-            while len(cls._w4_areas) >= cls._W4_AREAS_MAX:       # streams come and go: the oldest area goes with them
-                cls._w4_areas.pop(next(iter(cls._w4_areas)))
-            ws = torch.empty(floats, dtype=torch.float32, device=device)
-            ws[:1024].zero_()                                 # the control words, once (a forward re-zeroes only the counters)
-            cls._w4_areas[key] = ws
-        return ws
-
-    @classmethod
-    def handoff_status(cls, clear: bool = True) -> int:
-        """1 if the F(4x4) kernel's cross-workgroup hand-off has ever given up on one of this process' split areas (the
-        features computed then, and since, are NaN: the failure is loud on the device already); synchronises the streams
-        concerned.  ``clear`` re-arms the areas."""
-        import ctypes as C
-        from . import _native
-        lib = _native.load()
-        worst = 0
-        for (dev, stream), ws in list(cls._w4_areas.items()):
-            st = C.c_int(0)
-            with torch.cuda.device(ws.device):
-                _native.check(lib.diinn_conv_wino4_ws_status(C.c_void_p(stream), C.c_void_p(ws.data_ptr()), int(clear), C.byref(st)),
-                              "diinn_conv_wino4_ws_status")
-            worst = max(worst, st.value)
-        return worst
+    # the F(4x4) kernel's split area and its sticky status word: ONE area per (device, stream) for every user in the process (convs.py)
+    _w4_area = staticmethod(convs.w4_area)
+    handoff_status = staticmethod(convs.handoff_status)
 
     def _forward_hip_trunk(self, shallow):
         import ctypes as C
@@ -303,9 +192,10 @@ class RDN(nn.Module):
         dev = shallow.device
         packed, biases = self._hip_packed(dev)
         x3 = self.hip_winograd and self.hip_split_bf16
-        w4 = self.hip_winograd and self.hip_winograd4 and not x3 and bool(lib.diinn_rdn_wino4_applies(b, h, w))
+        form = convs.conv_form(b, h, w)
+        w4 = self.hip_winograd and self.hip_winograd4 and not x3 and form == "wino4"
         # the F(2x2) image only where a kernel reads it (~0.6 GB of weight copies for an 88 MB encoder otherwise)
-        needs_wino = self.hip_winograd and not w4 and (x3 or b * h * w >= _native.debug_get("DIINN_ENC_WINO_MIN"))
+        needs_wino = self.hip_winograd and not w4 and (x3 or form != "ksplit")
         algo = (_native.RDN_ALGO_X3 if x3 else _native.RDN_ALGO_WINO4 if w4 else _native.RDN_ALGO_WINO if needs_wino
                 else _native.RDN_ALGO_DIRECT)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731

@@ -36,7 +36,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, convs
 
 HIDDEN = 256
 IN_CHANNELS = 64
@@ -57,7 +57,6 @@ PARAM_SHAPES: Dict[str, Tuple[int, ...]] = {
     **{f"Q.{i}.0.bias": (HIDDEN,) for i in (1, 2, 3)},
     "last_layer.weight": (3, HIDDEN, 1, 1), "last_layer.bias": (3,),
 }
-
 
 
 def param_shapes(mode: int = 3) -> Dict[str, Tuple[int, ...]]:
@@ -81,6 +80,18 @@ def _layout(mode: int) -> int:
     return 1 if mode == 1 else 3
 
 
+def position_state_dict(names: Sequence[str], shapes: Dict[str, Tuple[int, ...]]) -> Tuple[Dict[str, np.ndarray], int]:
+    """({name: fp32 array of ``shapes[name]`` whose elements are their own 1-based position in the tensors flattened in
+    ``names`` order}, the element count): packing it and reading the positions back gives a packer's permutation (exact in fp32)."""
+    sd, pos = {}, 1
+    for name in names:
+        n = int(np.prod(shapes[name]))
+        sd[name] = np.arange(pos, pos + n, dtype=np.float32).reshape(shapes[name])
+        pos += n
+    assert pos - 1 < (1 << 24)
+    return sd, pos - 1
+
+
 def pack_gather_index(mode: int = 3) -> torch.Tensor:
     """int64 [packed floats]: packed[i] = flat[index[i]] where ``flat`` is the 18 reference tensors
     flattened in PARAM_NAMES order followed by one 0.0 (padding and the bf16 section point at it).
@@ -92,15 +103,7 @@ def pack_gather_index(mode: int = 3) -> torch.Tensor:
         return _gather_index_cpu[layout]
     from .decoder import pack_state_dict
     lib = _native.load()
-    shapes = param_shapes(layout)
-    sd = {}
-    pos = 1
-    for name in PARAM_NAMES:
-        n = int(np.prod(shapes[name]))
-        sd[name] = np.arange(pos, pos + n, dtype=np.float32).reshape(shapes[name])
-        pos += n
-    total = pos - 1
-    assert total < (1 << 24)
+    sd, total = position_state_dict(PARAM_NAMES, param_shapes(layout))
     packed = pack_state_dict(sd, mode=layout).numpy()
     idx = np.rint(packed).astype(np.int64) - 1
     off, size = C.c_size_t(), C.c_size_t()
@@ -139,7 +142,6 @@ def pack_on_device(params: Sequence[torch.Tensor], mode: int = 3) -> torch.Tenso
     return packed
 
 
-_WPU_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 _section_cache: Dict[int, Tuple[int, int]] = {}
 
 
@@ -175,12 +177,7 @@ def _fill_wpu(packed: torch.Tensor, params: Sequence[torch.Tensor], mode: int = 
 
 def _fill_wpu_weight(packed: torch.Tensor, w: torch.Tensor) -> None:
     """``_fill_wpu`` for any 1024-output 3x3 weight ``w`` [1024,64,3,3] (the MetaSR training image brings its own: metasr_training.py)."""
-    w = w.detach().to(torch.float64)
-    g = torch.tensor(_WPU_G, dtype=torch.float64, device=w.device)
-    gi = [g[:, a].view(1, 1, 4, 1) for a in range(3)]
-    t = gi[0] * w[:, :, 0:1, :] + gi[1] * w[:, :, 1:2, :] + gi[2] * w[:, :, 2:3, :]          # [O, C, i 4, b 3]
-    gj = [g[:, b].view(1, 1, 1, 4) for b in range(3)]
-    u = t[..., 0:1] * gj[0] + t[..., 1:2] * gj[1] + t[..., 2:3] * gj[2]                      # [O, C, i 4, j 4]
+    u = convs._winograd_weight(w, torch.tensor(convs._WINO2_G, dtype=torch.float64, device=w.device))   # [O, C, i 4, j 4]
     u[..., 2] = -u[..., 2]
     u = u.to(torch.float32).reshape(32, 32, 8, 4, 2, 4, 4)                                   # [mt, m, sg, e, h, i, j]
     off, size = _section(13)
@@ -308,13 +305,12 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
       weight:  dWx[o, (c,ky,kx)] = sum over cells of dP[o, cell] * unfold3x3(feat)[(c,ky,kx), cell] -- the plane GEMM over the
                cell axis (plane_gemm_lds_kernel; the 576 unfolded rows padded to 640 = 5 x 128);
       input :  d_feat = conv3x3(dP; Wx transposed and flipped) -- a 64-output 3x3 convolution over 1024 planes, i.e. the
-               encoder's convolution kernels (Winograd F(4x4) / F(2x2) / split-K by the same rule as the trunk).
+               encoder's convolution kernels (Winograd F(4x4) / F(2x2) / split-K by the trunk's rule, convs.conv_form).
     ``rows`` < 1024 (decoder mode 1: 256, only P_0 is a convolution of the features): the conv is Wx[:rows], i.e. the first
     ``rows`` planes of ``dp`` [B,1024,H,W] / rows of ``a_t`` are used and ``wx`` is [rows,64,3,3].
     The weight and its cache key are the caller's: ``wx`` (a tensor, or a callable returning it, evaluated only when the
     transposed weight has to be repacked), ``wkey`` (what identifies its values: the DIINN callers pass their K weights'
     (address, version) pairs, MetaSR its own tagged tuple) and ``wpins`` (the tensors the key describes)."""
-    from . import modules as M                                   # (pack functions; imported late: modules imports the decoder)
     lib = _native.load()
     b, c, h, w = feat.shape
     n = b * h * w
@@ -347,7 +343,7 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
             d_feat = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
             zero = torch.zeros(64, dtype=torch.float32, device=dev)
             cin, in_bs = rows, 4 * HIDDEN * h * w                # the planes convolved; the batch stride of dp
-            form = "wino4" if lib.diinn_rdn_wino4_applies(b, h, w) else "wino" if n >= 8192 else "ksplit"
+            form = convs.conv_form(b, h, w)
             # the transposed weight in the kernel's form: repacked only when a K weight changed (an optimizer step, a
             # load_state_dict), not on every backward call.  The Winograd transforms are taken in float64 and rounded once,
             # like the encoder's: F(4x4)'s gradient error 2.5e-5 -> ~1e-5 of max|d_feat| (the fixtures' bound is 1e-4).
@@ -360,33 +356,16 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
                 if callable(wx):                                 # (a caller whose weight is itself derived builds it only for a repack)
                     wx = wx()
                 wt = wx.flip(2, 3).permute(1, 0, 2, 3).contiguous()      # [64, 1024, 3, 3]
-                pk = (M.pack_conv_wino4(wt) if form == "wino4" else M.pack_conv_wino(wt) if form == "wino" else M.pack_conv_ksplit(wt))
-                ent = (key, pk, tuple(t.detach() for t in (wpins or ())))
+                ent = (key, convs.pack_conv3x3(wt, form), tuple(t.detach() for t in (wpins or ())))
                 if wkey is not None:
                     _dgrad_pack[(form, str(dev))] = ent
-            pk = ent[1]
-            if form == "wino4":
-                ws = _wino4_workspace(dev)                       # (a partly filled last round is split over the input channels)
-                ws[:512].zero_()                                 # the arrival counters, whatever an aborted launch may have left (as the trunk does; never the sticky status word)
-                _native.check(lib.diinn_conv_wino4_ws(stream, ptr(dp), in_bs, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
-                                                      c * h * w, 0, b, h, w, ptr(ws), ws.numel()), "diinn_conv_wino4_ws")
-            elif form == "wino":
-                _native.check(lib.diinn_conv_wino(stream, ptr(dp), in_bs, cin, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
-                                                  c * h * w, 0, b, h, w), "diinn_conv_wino")
-            else:
-                _native.check(lib.diinn_conv_ksplit(stream, ptr(dp), in_bs, cin, 9, ptr(pk), ptr(zero), None, 0, ptr(d_feat),
-                                                    c * h * w, None, 0, 0, b, h, w), "diinn_conv_ksplit")
+            # (F(4x4) takes the encoder's split area of this (device, stream): a partly filled last round is split over the input channels)
+            ws = convs.w4_area(dev) if form == "wino4" else None
+            convs.launch_conv3x3(form, stream, ws, b, h, w, dp, 0, in_bs, cin, ent[1], zero, None, 0, 0, d_feat, 0, c * h * w, 0)
     return d_wx, d_feat
 
 
 _dgrad_pack: Dict[tuple, tuple] = {}               # (form, device) -> (key, the transposed hoisted-conv weight in that kernel's form, the pinned K weights)
-
-
-def _wino4_workspace(dev) -> torch.Tensor:
-    """diinn_conv_wino4_ws's workspace: the encoder's split area of this (device, current stream) (modules.RDN._w4_area:
-    control words zeroed once, launches on one stream are ordered, two streams never share slabs or tickets)."""
-    from . import modules as M
-    return M.RDN._w4_area(dev)
 
 
 def _assemble_k_grads(grads: Dict[str, torch.Tensor], d_wx: torch.Tensor, d_wq, d_bk) -> None:
@@ -765,23 +744,36 @@ def backward_fused_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.T
 # ---------------------------------------------------------------------------
 # autograd function
 # ---------------------------------------------------------------------------
+def checked_features(feat: torch.Tensor, params: Sequence[torch.Tensor], names: Sequence[str], shapes: Dict[str, Tuple[int, ...]],
+                     hu: int, wu: int, plane_rows: int, what: str = "") -> torch.Tensor:
+    """The entry check of the training Functions (decoder modes 1-3, MetaSR): ``feat`` on a GPU, ``params`` the tensors ``names`` with
+    ``shapes`` (``what`` completes the message), ``feat`` [B,64,H,W], B*Hu*Wu HR pixels within the limit of ``plane_rows``-row tiled
+    planes.  Returns ``feat`` detached, contiguous, fp32."""
+    if not feat.is_cuda:
+        raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
+    if len(params) != len(names):
+        raise ValueError(f"expected {len(names)} parameter tensors in PARAM_NAMES order")
+    for name, p_ in zip(names, params):
+        if tuple(p_.shape) != shapes[name]:
+            raise ValueError(f"{name}: expected shape {shapes[name]}{what}, got {tuple(p_.shape)}")
+    feat_c = feat.detach().contiguous().to(torch.float32)
+    if feat_c.dim() != 4 or feat_c.shape[1] != IN_CHANNELS:
+        raise ValueError(f"feat must be [B,{IN_CHANNELS},H,W]")
+    n = feat_c.shape[0] * hu * wu
+    if _native.load().diinn_training_plane_floats(n, plane_rows) < 0:
+        raise RuntimeError(f"diinn_amd: B*Hu*Wu = {n} HR pixels in one training forward exceeds the limit; split the batch")
+    return feat_c
+
+
 class DecodeMode3Function(torch.autograd.Function):
     """out = decoder(feat) on the HIP kernels, differentiable in feat and the 18 parameter tensors."""
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, *params: torch.Tensor) -> torch.Tensor:
         lib = _native.load()
-        if not feat.is_cuda:
-            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
-        if len(params) != len(PARAM_NAMES):
-            raise ValueError(f"expected {len(PARAM_NAMES)} parameter tensors in PARAM_NAMES order")
-        feat_c = feat.detach().contiguous().to(torch.float32)
+        feat_c = checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, 2 * HIDDEN, " for decoder mode 3")
         b, c, h, w = feat_c.shape
-        if c != IN_CHANNELS:
-            raise ValueError(f"feat must be [B,{IN_CHANNELS},H,W]")
         n = b * hu * wu
-        if lib.diinn_training_plane_floats(n, 2 * HIDDEN) < 0:
-            raise RuntimeError(f"diinn_amd: B*Hu*Wu = {n} HR pixels in one training forward exceeds the limit; split the batch")
         dev = feat_c.device
         packed = pack_on_device(params)
         workspace = torch.empty(b * h * w * 4 * HIDDEN, dtype=torch.float32, device=dev)
@@ -837,21 +829,7 @@ class DecodeModes12Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, mode: int, *params: torch.Tensor) -> torch.Tensor:
-        lib = _native.load()
-        if not feat.is_cuda:
-            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
-        if len(params) != len(PARAM_NAMES):
-            raise ValueError(f"expected {len(PARAM_NAMES)} parameter tensors in PARAM_NAMES order")
-        shapes = param_shapes(mode)
-        for name, p_ in zip(PARAM_NAMES, params):
-            if tuple(p_.shape) != shapes[name]:
-                raise ValueError(f"{name}: expected shape {shapes[name]} for decoder mode {mode}, got {tuple(p_.shape)}")
-        feat_c = feat.detach().contiguous().to(torch.float32)
-        if feat_c.dim() != 4 or feat_c.shape[1] != IN_CHANNELS:
-            raise ValueError(f"feat must be [B,{IN_CHANNELS},H,W]")
-        n = feat_c.shape[0] * hu * wu
-        if lib.diinn_training_plane_floats(n, 2 * HIDDEN) < 0:
-            raise RuntimeError(f"diinn_amd: B*Hu*Wu = {n} HR pixels in one training forward exceeds the limit; split the batch")
+        feat_c = checked_features(feat, params, PARAM_NAMES, param_shapes(mode), hu, wu, 2 * HIDDEN, f" for decoder mode {mode}")
         out, acts, chain, packed = train_forward_modes12(feat_c, params, hu, wu, sin_mode, mode)
         ctx.save_for_backward(feat_c, acts, chain, packed, *[p_.detach() for p_ in params])
         ctx.size = (hu, wu)
