@@ -12,6 +12,15 @@
 // decode_kernel with a ReLU epilogue; the weights travel in the same packed image (pack_liif in
 // decoder.py maps imnet.layers.{2,4,6} to the synthesis slots of WL, the 4 coordinate columns to the
 // Q0 table, the head to L).
+//
+// SAVE = true (training forward, reference query_rgb under autograd: liif.py:148-155 called with bsize=None from
+// sr_module.py:127-129): the same network, and the rectified activations h_1..h_4 of every ensemble member are written to
+// p.acts for the backward pass (diinn_liif_training.hip).  One wave then owns 32 consecutive pixels of the flattened (b, y, x)
+// index, like decode_kernel<SAVE>; a pixel's arithmetic does not depend on the lane that owns it, so the output is the
+// inference output bit for bit.  The planes run over the VIRTUAL-pixel axis vp = v * N + pix (member v = 2 vh + vw, N = B Hu Wu):
+// acts [4 layers][ceil(4 N / 32)][256][32], element (c, vp) of a layer at ((vp >> 5) * 256 + c) * 32 + (vp & 31).  v * N need not be
+// a multiple of 32, so a wave's 32 pixels of member v lie in two neighbouring tiles: one descriptor over both, the lane's
+// offset picks the tile.  Every SAVE branch is `if constexpr` around code the inference instantiation keeps whole.
 // ---------------------------------------------------------------------------------
 struct LiifParams {
     const float* P;        // [B,H,W,1024], channels 0..255 = first-layer pre-activation of the cell
@@ -19,15 +28,30 @@ struct LiifParams {
     float* out;            // [B,3,Hu,Wu]
     int B, H, W, Hu, Wu;
     LiifAxis ah, aw;
+    float* acts;           // SAVE: h_1..h_4, tiled planes over the virtual pixels [4][vtiles][256][32]
+    long long npix;        // SAVE: N = B*Hu*Wu
 };
 
+template <bool SAVE = false>
 __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31;
-    const int x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
-    const int y = blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
-    const int b = blockIdx.z;
+    int x, y, b;
+    const long long ptile = (long long)blockIdx.x * 4 + wave;   // SAVE: this wave's 32 consecutive flattened pixels
+    if constexpr (SAVE) {
+        const long long pix = ptile * PLANE_TILE + j;
+        const long long pc = pix < p.npix ? pix : p.npix - 1;    // lanes past the end compute on the last pixel
+        const int hw = p.Hu * p.Wu;
+        b = (int)(pc / hw);
+        const int rem = (int)(pc - (long long)b * hw);
+        y = rem / p.Wu;
+        x = pix < p.npix ? rem - y * p.Wu : p.Wu;                // ... and are marked invalid below
+    } else {
+        x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
+        y = blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
+        b = blockIdx.z;
+    }
     const bool valid = (x < p.Wu) && (y < p.Hu);
     if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
     const int xc = x < p.Wu ? x : p.Wu - 1;
@@ -58,6 +82,25 @@ __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
         const int vh = v >> 1, vw = v & 1;
         const float relh = rh[vh], relw = rw[vw];
         const float* __restrict__ Pc = p.P + (((size_t)b * p.H + iy[vh]) * p.W + ix[vw]) * PCH + 4 * h;
+        // SAVE: the two plane tiles that hold this wave's pixels of member v, and the lane's place in them (lanes past the end
+        // carry an offset outside the descriptor's range: the store is dropped)
+        [[maybe_unused]] const float* act0 = nullptr;
+        [[maybe_unused]] size_t act_group = 0;
+        [[maybe_unused]] int act_bytes = 0;
+        [[maybe_unused]] unsigned act_voff = 0xFFFFFFF0u;
+        if constexpr (SAVE) {
+            const long long vtiles = (4 * p.npix + PLANE_TILE - 1) / PLANE_TILE;
+            const long long vp0 = (long long)v * p.npix + ptile * PLANE_TILE;
+            const long long t0 = vp0 >> 5;
+            const unsigned qpos = (unsigned)(vp0 & 31) + (unsigned)j;
+            act_group = (size_t)vtiles * HID * PLANE_TILE;
+            act0 = p.acts + (size_t)t0 * HID * PLANE_TILE;
+            act_bytes = (int)((vtiles - t0 < 2 ? vtiles - t0 : 2) * HID * (long long)PLANE_ROW_BYTES);
+            if (valid) act_voff = (qpos >> 5) * (unsigned)(HID * PLANE_ROW_BYTES) + 4u * (qpos & 31) + 4u * h * PLANE_ROW_BYTES;
+        }
+        auto act_rsrc = [&](int layer) {
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(act0 + (size_t)layer * act_group), 0, act_bytes, 0x00020000);
+        };
         // ---- layer 1: relu(P[cell] + W1[:, 576:580] . (rel_h, rel_w, cell_h, cell_w))
         float q[128];
         {
@@ -79,6 +122,7 @@ __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
                         a = __builtin_fmaf(wch[e], p.ah.rel_cell, a);
                         a = __builtin_fmaf(wcw[e], p.aw.rel_cell, a);
                         q[16 * m + 4 * g + e] = relu0(a);
+                        if constexpr (SAVE) st_act(act_rsrc(0), act_voff, (unsigned)(c0 + e) * PLANE_ROW_BYTES, q[16 * m + 4 * g + e]);
                     }
                 }
             }
@@ -98,6 +142,7 @@ __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
             const float* __restrict__ Bn = Wt + OFF_BQ + nl * HID + 4 * h;
             float qn[128];
             f32x16 ps;
+            [[maybe_unused]] const __amdgpu_buffer_rsrc_t arl = act_rsrc(SAVE ? layer + 1 : 0);
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 f32x16 as;
@@ -123,6 +168,8 @@ __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
                         // opaque use: keeps each rectification where it is written, between the MFMAs.  Left free, the
                         // scheduler regroups the 128 of them and the layer needs 954 registers more than exist (r02).
                         asm volatile("" : "+v"(qn[16 * (m - 1) + r]));
+                        // register r of tile m-1 = channel 32(m-1) + (r&3) + 8(r>>2) + 4h
+                        if constexpr (SAVE) st_act(arl, act_voff, (unsigned)(32 * (m - 1) + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES, qn[16 * (m - 1) + r]);
                     }
                 }
                 ps = as;
@@ -131,6 +178,7 @@ __global__ __launch_bounds__(256, 1) void liif_kernel(const LiifParams p) {
             for (int r = 0; r < 16; ++r) {
                 qn[16 * 7 + r] = relu0(ps[r]);
                 asm volatile("" : "+v"(qn[16 * 7 + r]));
+                if constexpr (SAVE) st_act(arl, act_voff, (unsigned)(32 * 7 + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES, qn[16 * 7 + r]);
             }
 #pragma unroll
             for (int i = 0; i < 128; ++i) q[i] = qn[i];
@@ -361,7 +409,32 @@ int diinn_liif_decode(void* stream, const float* feat_dev, const float* packed_d
     p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu;
     p.ah = make_liif_axis(H, Hu);
     p.aw = make_liif_axis(W, Wu);
-    hipLaunchKernelGGL(liif_kernel, dim3(gx, gy, gz), dim3(blk), 0, (hipStream_t)stream, p);
+    p.acts = nullptr; p.npix = 0;
+    hipLaunchKernelGGL(liif_kernel<false>, dim3(gx, gy, gz), dim3(blk), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+int diinn_liif_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
+                         float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu) {
+    if (!feat_dev || !packed_dev || !out_dev || !workspace_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    const long long npix = (long long)B * Hu * Wu;
+    st = check_npix(4 * npix);                                   // the limit applies to the virtual pixels
+    if (st) return st;
+    const long long blocks = ((npix + PLANE_TILE - 1) / PLANE_TILE + 3) / 4;
+    if (blocks > 2147483000LL) return DIINN_ERR_TOO_LARGE;
+    st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, 0, H, 4);   // the inference forward's P, bit for bit
+    if (st) return st;
+    LiifParams p;
+    p.P = workspace_dev; p.Wt = packed_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu;
+    p.ah = make_liif_axis(H, Hu);
+    p.aw = make_liif_axis(W, Wu);
+    p.acts = acts_dev; p.npix = npix;
+    hipLaunchKernelGGL(liif_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }
 

@@ -16,6 +16,7 @@
 //   diinn_enc_training.hip     the encoder's dense blocks under autograd: conv_wgrad (weight-gradient GEMM over the pixel axis), relu_gate
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
 //   diinn_metasr_training.hip  metasr_bwd_cells_kernel (MetaSR under autograd: the per-cell backward pass)
+//   diinn_liif_training.hip    liif_bwd_layer_kernel, liif_cell_sum_kernel (LIIF under autograd; the forward is liif_kernel<SAVE> in diinn_baselines.hip)
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))
 //   diinn_conv_x3.hip          RDN trunk, optional split-bf16 arithmetic: conv3x3_x3m_kernel / conv3x3_x3_kernel (3x3 layers), conv1x1_x3_kernel (fusion)

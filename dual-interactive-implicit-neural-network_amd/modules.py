@@ -396,15 +396,24 @@ class LIIF(nn.Module, _GraphReplay):
     """The LIIF comparison model (reference liif.py:9-155; Chen et al. 2021) behind the same
     ``forward(inp, size, bsize=None)`` boundary: RDN encoder (PyTorch-ROCm) + the implicit MLP decoder on
     the HIP path (``liif_kernel``).  Constructor defaults only (local ensemble, feature unfolding, cell
-    decoding -- what ``make_net('liif')`` builds, sr_module.py:45-46); inference only.  ``bsize`` is the
-    reference's query-chunk size, a memory knob: accepted and ignored."""
+    decoding -- what ``make_net('liif')`` builds, sr_module.py:45-46).
 
-    def __init__(self, local_ensemble=True, feat_unfold=True, cell_decode=True, graphs: bool = False):
+    ``hip_autograd`` (a plain attribute, also a constructor keyword; default False): with it set, a call under autograd with
+    ``bsize=None`` -- the reference's training call, sr_module.py:127-129 -- runs the decoder through
+    ``liif_training.LIIFFunction`` (the inference kernels saving the activations, the backward pass on the HIP kernels; ROCm GPU
+    only), and with ``bsize`` given the decode runs under no_grad like the reference's ``batched_predict`` (liif.py:129-140): the
+    output carries no graph.  With it unset a call under autograd raises NotImplementedError, as it always did.  ``bsize`` itself
+    is the reference's query-chunk size, a memory knob: accepted and ignored.  Graph replay is inference-only."""
+
+    hip_autograd = False
+
+    def __init__(self, local_ensemble=True, feat_unfold=True, cell_decode=True, graphs: bool = False, hip_autograd: bool = False):
         super().__init__()
         self._init_graphs(graphs)
         if not (local_ensemble and feat_unfold and cell_decode):
             raise NotImplementedError("the HIP path implements LIIF with local_ensemble, feat_unfold and cell_decode on")
         self.local_ensemble, self.feat_unfold, self.cell_decode = local_ensemble, feat_unfold, cell_decode
+        self.hip_autograd = bool(hip_autograd)
         self.encoder = make_rdn()
         self.imnet = MLP(self.encoder.out_dim * 9 + 4, 3, [256, 256, 256, 256])
         self._packed = None
@@ -426,9 +435,22 @@ class LIIF(nn.Module, _GraphReplay):
         feat = self.gen_feat(inp)
         return liif_decode_features(feat, self._packed_weights(feat.device), size)
 
+    def _forward_train(self, inp, size):
+        from .liif_training import decode_with_grad
+        if not inp.is_cuda:
+            raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
+        return decode_with_grad(self.imnet, self.gen_feat(inp), size)
+
     def forward(self, inp, size, bsize=None):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("diinn_amd: LIIF runs on the HIP path for inference only; call under torch.no_grad()")
+        if torch.is_grad_enabled() and self.hip_autograd:
+            if inp.requires_grad or any(p.requires_grad for p in self.parameters()):
+                if bsize is None:
+                    return self._forward_train(inp, size)
+                with torch.no_grad():                            # batched_predict is no_grad in the reference: no graph
+                    return self._forward_eager(inp, size, bsize)
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("diinn_amd: LIIF under autograd is opt-in: set LIIF.hip_autograd = True (the decoder then trains "
+                                      "on the HIP kernels), or call under torch.no_grad()")
         if self._use_graph(inp):
             return self._forward_graphed(inp, size, bsize)
         return self._forward_eager(inp, size, bsize)

@@ -450,6 +450,34 @@ int diinn_conv_wgrad(void* stream, const float* g_dev, long long g_batch_stride,
 int diinn_liif_decode(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
                       float* out_dev, int B, int H, int W, int Hu, int Wu);
 int diinn_liif_make_axis_tables(int n_in, int n_out, int v, int32_t* idx, float* rel, float* rel_cell);
+/* LIIF under autograd (added under ABI 11, backward compatible).  Replaces what autograd records and runs backward for
+ * LIIF.query_rgb (liif.py:59-127) when forward(inp, size, None) runs under grad (sr_module.py:127-129).  Per HR pixel p and
+ * ensemble member v = 2 vh + vw (vx outer, vy inner: liif.py:88-89) -- the VIRTUAL pixel vp = v * N + p, N = B*Hu*Wu; 4 N is what
+ * DIINN_TRAIN_MAX_PIXELS limits here --
+ *     h_1 = relu(P1[c_v] + Wc r_v),  h_l = relu(W_l h_{l-1} + b_l) (l = 2..4),  out = sum_v w_v (L h_4 + bL),  w_v = area[3 - v] / tot.
+ * Plane groups are tiled over the virtual pixels: [ceil(4 N / 32)][256][32], element (c, vp) at ((vp >> 5) * 256 + c) * 32 + (vp & 31);
+ * the padding of a ragged last tile is neither written nor read as data.
+ * diinn_liif_train_fwd: diinn_liif_decode (same arguments, same kernels on the same image: out_dev is the inference output bit for
+ *   bit) that additionally writes acts_dev [4][ceil(4 N / 32)][256][32] = h_1..h_4 (diinn_training_plane_floats(4 N, 256) floats per
+ *   layer; a post-ReLU value is its own mask).  The image may be a gathered one: only permutation sections are read.  2 kernels.
+ * diinn_liif_backward_data: the per-virtual-pixel chain.  gout_planes_dev [3][N] = d loss / d out as plain planes; G_dev
+ *   [4][ceil(4 N / 32)][256][32] receives g_a,4 = (L^T (w_v g)) [h_4 > 0] and g_a,l-1 = (W_l^T g_a,l) [h_{l-1} > 0] (l = 4, 3, 2) in slots
+ *   3..0; w_v is recomputed with the forward's own expressions.  Reads sections 6 (L) and 8 (WLT, synthesis pieces) of the image
+ *   (16-byte aligned).  A zero or a NaN of h closes the gate.  3 kernels.
+ * diinn_liif_cell_sum: dP1[b][ch][cy][cx] = sum over the four members v, in member order, of g_a,1 (G1_dev = slot 0 of G_dev) over
+ *   the pixels whose shifted nearest cell c_v is (cy, cx): the gradient at the hoisted 3x3 convolution's output.  seg_h_dev [2][H+1] /
+ *   seg_w_dev [2][W+1] (int32, device): per shift vh / vw the first HR row / column of every LR row / column of
+ *   diinn_liif_make_axis_tables' index (last entry Hu / Wu; each table is monotone, so per member a cell's pixels form a rectangle).
+ *   Written in both layouts of diinn_backward_cell_sum, planes / rows 0..255 only: dP_dev NCHW [B][1024][H][W] and dP_tiled_dev
+ *   [ceil(B H W / 32)][1024][32] over the cells.  A cell that owns no virtual pixel gets zeros.  1 kernel.
+ * All three validate every argument before the first launch, allocate nothing, do not synchronise; fixed summation orders, no
+ * atomics: deterministic. */
+int diinn_liif_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
+                         float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu);
+int diinn_liif_backward_data(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
+                             float* G_dev, int B, int H, int W, int Hu, int Wu);
+int diinn_liif_cell_sum(void* stream, const float* G1_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
+                        float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu);
 
 /* ---- MetaSR comparison decoder ----------------------
  * Replaces: MetaSR.query_rgb + batched_predict + reshape_pred (metasr.py:70-104,106-123): per HR pixel the
