@@ -26,6 +26,7 @@ ABI_VERSION = 11
 PACKED_MAGIC = 0x44493038
 HEAD3X3_MAGIC = 0x44494833             # validity word of the mode-4 head image (diinn_pack_head3x3)
 INITQ_MAGIC = 0x44494951               # validity word of the init_q image (diinn_pack_initq)
+INITQ_TRAIN_MAGIC = 0x44495154         # validity word of the init_q training image (diinn_pack_initq_train)
 PACKED_MAGIC_WPU = 0x44495750          # a training image: permutation sections + section 13 (WPU) filled on the device
 P_ALGO_DIRECT, P_ALGO_WINOGRAD, P_ALGO_DIRECT_BF16, P_ALGO_DIRECT_BF16X3 = 0, 1, 2, 3
 RDN_ALGO_AUTO, RDN_ALGO_DIRECT, RDN_ALGO_WINO, RDN_ALGO_WINO4, RDN_ALGO_X3 = 0, 1, 2, 3, 4
@@ -99,6 +100,15 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_decode_initq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_initq_train_packed_floats": (C.c_size_t, []),
+    "diinn_pack_initq_train": (C.c_int, [_f, _f, _f, _f, _f, _f3, _f]),
+    "diinn_decode_initq_train_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_initq_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_cell_sum_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_fold3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_decode_launch_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "diinn_p_launch_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "diinn_decode_kernel_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),

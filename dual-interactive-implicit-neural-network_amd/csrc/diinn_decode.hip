@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
     constexpr bool INITQ = (SIN_X & DECODE_INITQ) != 0;
     static_assert(SIN_X >= 0 && SIN_X < 2 * DECODE_INITQ && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | DECODE_INITQ");
     static_assert(!(HEAD3 && SAVE), "mode 4 is inference only");
-    static_assert(!INITQ || (KPART && !SAVE && !HEAD3), "init_q: mode 3, inference");
+    static_assert(!INITQ || (KPART && !HEAD3), "init_q: mode 3");   // (with SAVE: the planes are in radians, INITQ_RAD of initq_planes_kernel)
     // The small tables of layer 0 and of the head go through LDS: a vector-memory instruction blocks its wave for
     // ~60 cycles (stamps), and a wave reading them straight from the packed image issued 128 + 96
     // of those per tile.  Rows: Q0h, Q0w, t = fma(Q0r, ratio, bQ0) (the pixel-independent part of the sine
@@ -1090,6 +1090,46 @@ static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_
 int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
                            float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
     return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true);
+}
+
+// init_q (mode 3) under autograd: the pixel planes of the WHOLE image in radians (initq_planes_kernel<SIN | INITQ_RAD> on the init_q
+// training image), then decode_kernel<SIN | DECODE_INITQ, true, SAVE>: acts in diinn_decode_train_fwd's layout, s_0 in radians.
+int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                 float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    if (!feat_dev || !packed_dev || !train_image_dev || !pix_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    const long long npix = (long long)B * Hu * Wu;
+    st = check_npix(npix);
+    if (st) return st;
+    if ((((size_t)packed_dev) | ((size_t)train_image_dev) | ((size_t)pix_dev)) & 15) return DIINN_ERR_INVALID_ARG;   // 16-byte pieces and seeds
+    st = launch_initq_planes(stream, feat_dev, packed_dev, train_image_dev, pix_dev, B, H, W, Hu, Wu, 0, Hu, sin_mode, true);
+    if (st) return st;
+    const dim3 grid((unsigned)((npix + 4 * PLANE_TILE - 1) / (4 * PLANE_TILE)));
+    DecodeParams p;
+    p.P = pix_dev; p.Wt = packed_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = 0; p.y1 = Hu;
+    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
+    p.Prow0 = 0; p.Prows = Hu; p.Orow0 = 0; p.Orows = Hu;          // P = the pixel planes: HR rows
+    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_rs = Wu; p.o_ps = (long long)Hu * Wu; p.o_bs = 3 * p.o_ps;
+    p.acts = acts_dev; p.npix = npix; p.seed_cols = 0; p.xcd_runs = 0;
+    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
+#ifdef DIINN_STAMPS
+    p.stamps = nullptr;
+#endif
+    const int small = diinn_uses_small_output_kernel(Hu, Wu);
+    p.ah = make_axis(H, Hu, small);
+    p.aw = make_axis(W, Wu, small);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
 }
 
 int diinn_decode_train_fwd_qonly(void* stream, const float* chain_dev, const float* packed_dev, float* out_dev,

@@ -17,6 +17,7 @@
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
 //   diinn_metasr_training.hip  metasr_bwd_cells_kernel (MetaSR under autograd: the per-cell backward pass)
 //   diinn_liif_training.hip    liif_bwd_layer_kernel, liif_cell_sum_kernel (LIIF under autograd; the forward is liif_kernel<SAVE> in diinn_baselines.hip)
+//   diinn_initq_training.hip   initq_bwd_kernel (init_q under autograd: the transposed per-pixel GEMMs), cell_sum_rows_kernel, fold3x3_kernel
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))
 //   diinn_conv_x3.hip          RDN trunk, optional split-bf16 arithmetic: conv3x3_x3m_kernel / conv3x3_x3_kernel (3x3 layers), conv1x1_x3_kernel (fusion)
@@ -344,6 +345,10 @@ int launch_P_wino(void* stream, const float* feat_dev, const float* packed_dev, 
 // diinn_bf16.hip: the bf16 decode of HR rows [p.y0, p.y1) (grid of the one-tile kernel: gx, gy, gz)
 __attribute__((visibility("hidden")))
 int launch_decode_bf16(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+// diinn_initq.hip: initq_planes_kernel for HR rows [y0,y1); rad: the radians form on the init_q training image (the training forward)
+__attribute__((visibility("hidden")))
+int launch_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad);
 // diinn_conv_x3.hip: a split-bf16 3x3 layer reading planes or the trunk's split-format buffer (and optionally extending it);
 // a block's 1x1 fusion layer from that buffer (diinn_rdn_forward_ex, DIINN_RDN_ALGO_X3)
 extern "C" __attribute__((visibility("hidden")))

@@ -475,6 +475,63 @@ int diinn_pack_initq(const float* Fw, const float* Fb, const float* Q0w, const f
     return DIINN_OK;
 }
 
+// ---- decoder init_q=True under autograd: the training image (diinn_layout.h "the init_q TRAINING image") -----------
+size_t diinn_initq_train_packed_floats(void) { return IQT_FLOATS; }
+
+int diinn_pack_initq_train(const float* Fw, const float* Fb, const float* Q0w, const float* Q0b, const float* K0w,
+                           const float* const Kw[3], float* packed) {
+    if (!Fw || !Fb || !Q0w || !Q0b || !K0w || !Kw || !Kw[0] || !Kw[1] || !Kw[2] || !packed) return DIINN_ERR_INVALID_ARG;
+    float* f = packed + IQ_OFF_F;
+    for (int n = 0; n < UNF; ++n) {                             // the init_q image's layout, in radians
+        f[0 * UNF + n] = Fw[n * 3 + 0];
+        f[1 * UNF + n] = Fw[n * 3 + 1];
+        f[2 * UNF + n] = Fw[n * 3 + 2];
+        f[3 * UNF + n] = Fb[n];
+    }
+    for (int mo = 0; mo < 8; ++mo)
+        for (int kg = 0; kg < WP_KG; ++kg) {
+            float* dst = packed + IQ_OFF_Q0W + ((((size_t)(mo >> 1) * WP_KG + kg) * 2) + (mo & 1)) * WL_PIECE;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int o = 32 * mo + (lane & 31);
+                const int h = lane >> 5;
+                for (int e = 0; e < 4; ++e) {
+                    const int kk = 4 * kg + e;
+                    const int t = kk >> 5;
+                    const int c = 2 * (kk & 31) + h;
+                    dst[lane * 4 + e] = Q0w[(size_t)o * UNF + (size_t)c * 9 + t];
+                }
+            }
+        }
+    for (int ch = 0; ch < HID; ++ch) packed[IQ_OFF_BQ0 + ch] = Q0b[ch];
+    const uint32_t magic = DIINN_INITQ_TRAIN_MAGIC;
+    std::memcpy(packed + IQ_OFF_BQ0 + HID, &magic, 4);
+    for (int i = 1; i < 4; ++i) packed[IQ_OFF_BQ0 + HID + i] = 0.0f;
+    for (int wave = 0; wave < 4; ++wave)                        // the transposed weights, in initq_bwd_kernel's stream order
+      for (int pass = 0; pass < 2; ++pass) {
+        const int nm = pass ? IQT_MT - IQT_MT_A : IQT_MT_A;
+        for (int chunk = 0; chunk < IQT_CHUNKS; ++chunk)
+            for (int kg = 0; kg < IQT_KG; ++kg)
+                for (int mt = 0; mt < nm; ++mt) {
+                    float* dst = packed + IQT_OFF_WT + wave * IQT_WAVE + (pass ? IQT_PASS_B : 0) +
+                                 (((size_t)chunk * IQT_KG + kg) * nm + mt) * WL_PIECE;
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int n = 32 * (IQT_MT * wave + IQT_MT_A * pass + mt) + (lane & 31);
+                        for (int e = 0; e < 4; ++e) {
+                            const int ch = 2 * (4 * kg + e) + (lane >> 5);
+                            float v = 0.0f;
+                            if (n < UNF) {
+                                if (chunk == 0) v = K0w[(size_t)ch * UNF + n];
+                                else if (chunk < 4) v = Kw[chunk - 1][(size_t)ch * (HID + UNF) + HID + n];
+                                else v = Q0w[(size_t)ch * UNF + n];
+                            }
+                            dst[lane * 4 + e] = v;
+                        }
+                    }
+                }
+      }
+    return DIINN_OK;
+}
+
 size_t diinn_initq_pix_bytes(int B, int Wu, int rows) {
     if (B <= 0 || Wu <= 0 || rows <= 0) return 0;
     return (size_t)B * (size_t)rows * (size_t)Wu * PIX_CH * sizeof(float);

@@ -41,8 +41,15 @@ constexpr int IQ_BUF = WP_KSTEPS * 2 * 64;                // 36,864 floats = 147
 constexpr int IQ_TR_PITCH = 20;                           // floats per pixel in the store transpose (16 + 4)
 constexpr int IQ_ITERS = IQ_BUF / 256;                    // 144 slots per thread and pass
 
-template <int SIN_MODE>
+// INITQ_RAD (the training forward, diinn_decode_initq_train_fwd): `iq` is the init_q TRAINING image, whose F / Q0W / BQ0 part is
+// in radians (a pure permutation of the reference tensors: diinn_layout.h), so E = sin(a) takes a in radians and channels
+// 1024..1279 leave in radians, as decode_kernel<SIN | DECODE_INITQ, true, SAVE> saves them.  The flag rides in the template
+// argument, SIN_X = sine mode | INITQ_RAD, like DECODE_INITQ in decode_kernel: the inference instantiations keep their symbols.
+constexpr int INITQ_RAD = 4;
+template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams p) {
+    constexpr int SIN_MODE = SIN_X & (INITQ_RAD - 1);
+    constexpr bool RAD = (SIN_X & INITQ_RAD) != 0;
     __shared__ __attribute__((aligned(16))) float buf[IQ_BUF];
     __shared__ __attribute__((aligned(16))) float tr[4][32 * IQ_TR_PITCH];
     const int lane = threadIdx.x & 63;
@@ -73,7 +80,8 @@ __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams 
         float a = __builtin_fmaf(F[2 * UNF + n], p.ratio, F[3 * UNF + n]);
         a = __builtin_fmaf(F[1 * UNF + n], relw, a);
         a = __builtin_fmaf(F[0 * UNF + n], relh, a);
-        buf[i * 256 + threadIdx.x] = dsin_rev<SIN_MODE>(a);
+        if constexpr (RAD) buf[i * 256 + threadIdx.x] = dsin<SIN_MODE>(a);
+        else buf[i * 256 + threadIdx.x] = dsin_rev<SIN_MODE>(a);
     }
 
     // where this lane's two store pixels of each N-tile go: transposed reads hand lane L pixel (L >> 2) + 16 i, chunk L & 3
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams 
         const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)p.iq, 0, (int)(IQ_FLOATS * sizeof(float)), 0x00020000);   // reads past the end return 0
         // an image without its validity word answers NaN in every sine argument
-        const unsigned nanm = __builtin_bit_cast(unsigned, p.iq[IQ_OFF_BQ0 + HID]) == DIINN_INITQ_MAGIC ? 0u : 0x7fc00000u;
+        const unsigned nanm = __builtin_bit_cast(unsigned, p.iq[IQ_OFF_BQ0 + HID]) == (RAD ? DIINN_INITQ_TRAIN_MAGIC : DIINN_INITQ_MAGIC) ? 0u : 0x7fc00000u;
         gemm_pair(qrs, (int)(IQ_OFF_Q0W * sizeof(float)) + wave * (WP_KG * 2 * PIECE_BYTES), p.iq + IQ_OFF_BQ0 + 64 * wave, nanm,
                   PCH + 64 * wave);
     }
@@ -200,8 +208,8 @@ __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams 
     }
 }
 
-extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
-                                  float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+int launch_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad) {
     if (!feat_dev || !packed_dev || !initq_dev || !pix_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -219,6 +227,15 @@ extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const flo
     p.aw = make_axis(W, Wu, small);
     // streaming stores once the planes no longer fit beside anything in the 256 MiB last-level cache (launch_P's rule)
     p.stream_stores = (double)B * (y1 - y0) * Wu * PIX_CH * 4.0 >= 128.0 * 1024 * 1024;
+    if (rad) {
+        if (sin_mode == DIINN_SIN_HW)
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (sin_mode == DIINN_SIN_HW_REDUCED)
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW_REDUCED | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        return hip_status(hipGetLastError());
+    }
     if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
@@ -226,4 +243,9 @@ extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const flo
     else
         hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
+}
+
+extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                  float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return launch_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
 }

@@ -142,6 +142,28 @@ constexpr size_t IQ_SZ_Q0W    = (size_t)8 * WP_KG * WL_PIECE;   // 147,456 float
 constexpr size_t IQ_OFF_BQ0   = IQ_OFF_Q0W + IQ_SZ_Q0W;         // 149,760
 constexpr size_t IQ_FLOATS    = IQ_OFF_BQ0 + HID + 4;           // 150,020 (validity word at IQ_OFF_BQ0 + HID)
 
+// ---- decoder init_q=True, mode 3, under autograd: the init_q TRAINING image (diinn_pack_initq_train) ----
+// A pure permutation of the reference tensors (plus zero padding and a validity word), so the device re-pack of an optimiser step is
+// one gather.  It starts with the init_q image's own layout -- F, Q0W, BQ0 at IQ_OFF_* -- in RADIANS (nothing divided by 2 pi: the
+// training forward saves sine arguments in radians) with DIINN_INITQ_TRAIN_MAGIC as the validity word at IQ_OFF_BQ0 + HID; the
+// radians form of initq_planes_kernel reads that part.  Behind it the transposed weights of the backward pass, initq_bwd_kernel's A
+// operands of v_mfma_f32_32x32x2_f32 in the order its waves stream them:
+//   WT [wave 4][pass 2][chunk 5][kg 32][mt 3 | 2][lane 64][e 4]   a wave owns 5 of the 20 M-tiles (640 rows = 576 + zero padding) and
+//       walks the reduction twice, M-tiles 0..2 of its five in pass 0 and 3..4 in pass 1: output row
+//       n = 32 (5 wave + 3 pass + mt) + (lane & 31); k-step 4 kg + e of the chunk = rows ch = 2 (4 kg + e) + (lane >> 5) of a
+//       256-row gate-gradient group; chunk i = 0..3: value = Wx_i[ch][n] (Wx_0 = K.0.weight, Wx_i = K.i.weight[:, 256:]),
+//       chunk 4: Q0w[ch][n]; n >= 576: 0.
+constexpr int    IQT_ROWS     = 640;                            // 576 padded to 20 M-tiles: 5 per wave
+constexpr int    IQT_MT       = 5;
+constexpr int    IQT_MT_A     = 3;                              // M-tiles of a wave's first pass (the second: IQT_MT - IQT_MT_A)
+constexpr int    IQT_CHUNKS   = 5;
+constexpr int    IQT_KG       = HID / 2 / 4;                    // 32 groups of 4 k-steps per chunk
+constexpr size_t IQT_WAVE     = (size_t)IQT_CHUNKS * IQT_KG * IQT_MT * WL_PIECE;   // 204,800 floats per wave
+constexpr size_t IQT_PASS_B   = (size_t)IQT_CHUNKS * IQT_KG * IQT_MT_A * WL_PIECE; // where a wave's second pass starts
+constexpr size_t IQT_OFF_WT   = IQ_FLOATS;                      // 150,020 (16-byte aligned)
+constexpr size_t IQT_SZ_WT    = 4 * IQT_WAVE;                   // 819,200 floats
+constexpr size_t IQT_FLOATS   = IQT_OFF_WT + IQT_SZ_WT;         // 969,220
+
 // channel held by activation register (m, r) of lane-half h
 DIINN_HD int chan_of(int kk /* = 16*m + r */, int h) {
     const int m = kk >> 4, r = kk & 15;

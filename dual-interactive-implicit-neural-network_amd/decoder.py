@@ -131,7 +131,7 @@ def initq_chunk_rows(b: int, wu: int, cap_bytes: int) -> int:
     return max(8, (int(cap_bytes) // per_row) // 8 * 8)
 
 
-def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "") -> torch.Tensor:
+def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "", planes: Optional[list] = None) -> torch.Tensor:
     """The formula sheet of the ``init_q=True``, mode-3 path in tensor algebra, in the RESTRUCTURED form the kernels run
     (any device, any float dtype; the tests' one restatement, as ``encoder_training.rdb_backward_reference`` is for its path).
 
@@ -146,7 +146,8 @@ def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "
     ``PIX[1024:1280] = Q0 . E + bQ0`` are two GEMMs per pixel (``initq_planes_kernel``), and the layers read their seeds
     there: ``k_i = relu(K_i[:, :256] . q_{i-1} + PIX[256 i : 256 i + 256])`` (``decode_kernel<SIN | DECODE_INITQ>``).  E depends on the
     pixel only, not on the batch item.  Coordinates: the fp32 tables of ``axis_tables`` (the reference computes them in fp32
-    whatever the module's dtype); ``ratio`` is the Python double rounded to ``dtype``, as ``x.new_tensor`` does."""
+    whatever the module's dtype); ``ratio`` is the Python double rounded to ``dtype``, as ``x.new_tensor`` does.
+    ``planes`` (a list): receives every layer's (k_i, s_i), each [B,256,Hu*Wu] -- what the training forward saves."""
     def get(name, shape):
         t = sd[prefix + name]
         t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
@@ -175,9 +176,14 @@ def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "
     pix = wx @ xp + bk                                                                                             # [b, 1024, n]
     a0 = get("Q.0.0.weight", (HIDDEN, 576)) @ e + get("Q.0.0.bias", (HIDDEN, 1))                                   # [256, n]
     q = torch.relu(pix[:, :HIDDEN]) * torch.sin(a0)[None]
+    if planes is not None:
+        planes.append((torch.relu(pix[:, :HIDDEN]), a0[None].expand(b, HIDDEN, n)))
     for i in (1, 2, 3):
         k = torch.relu(get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, :HIDDEN] @ q + pix[:, HIDDEN * i:HIDDEN * (i + 1)])
-        q = k * torch.sin(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1)))
+        s = get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1))
+        if planes is not None:
+            planes.append((k, s))
+        q = k * torch.sin(s)
     out = get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))
     return out.reshape(b, 3, hu, wu)
 
@@ -537,13 +543,22 @@ class ImplicitDecoder(nn.Module):
     init_q=False`` (README.md:111-112 of the reference), the ablation modes 1 and 2, whose
     modulation branch depends on the LR cell only, and mode 4, mode 3 with a 3x3 reflect-padded
     head (inference, fp32).  ``init_q=True`` (the per-pixel sine embedding ``first_layer``, diinn.py:48-51,113-115) runs
-    for mode 3, inference, fp32; with modes 1, 2, 4 or under autograd ``forward`` raises ``NotImplementedError``."""
+    for mode 3, inference, fp32; with modes 1, 2, 4 or under autograd ``forward`` raises ``NotImplementedError``.
+
+    ``hip_autograd`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, fp32 into
+    training: with it set, ``forward(x, size, None)`` under autograd runs ``initq_training.DecodeInitqFunction`` (the HIP kernels
+    saving the activations, the backward pass on the HIP kernels; ROCm GPU only).  With ``bsize`` given the call stays the no_grad
+    inference path, like the reference's ``batched_step``.  It changes nothing else: modes 1, 2 and 4 with ``init_q``, the bf16
+    arithmetics and every decoder with ``init_q=False`` behave as without it."""
+
+    hip_autograd = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
-                 init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32"):
+                 init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
+        self.hip_autograd = bool(hip_autograd)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -636,13 +651,16 @@ class ImplicitDecoder(nn.Module):
 
         ``init_q=True`` (mode 3, fp32, inference only): the per-pixel planes the two kernels hand over take 5,120 bytes per
         HR pixel, so the image is decoded in chunks of ``initq_chunk_rows(B, W_up, INITQ_CHUNK_BYTES)`` HR rows; chunking
-        changes no bit of the result either.  ``bsize=30000`` and ``bsize=None`` give the same bits, as in the reference."""
+        changes no bit of the result either.  ``bsize=30000`` and ``bsize=None`` give the same bits, as in the reference.
+        Under autograd with ``bsize=None`` it raises unless ``hip_autograd`` is set (then: ``initq_training.DecodeInitqFunction``,
+        the whole image at once)."""
         self._check_supported()
         wants_grad = bsize is None and torch.is_grad_enabled() and (
             x.requires_grad or any(p.requires_grad for p in self.parameters()))
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
-        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or self.init_q):
+        initq_grad = self.init_q and self.hip_autograd and self.mode == 3 and self.compute == "f32"     # the opt-in (initq_training.py)
+        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
             raise NotImplementedError(
                 "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
                 "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
@@ -651,6 +669,9 @@ class ImplicitDecoder(nn.Module):
             raise ValueError("init_q=True runs in fp32 only")
         _require_cuda(x, "x")
         if wants_grad:
+            if self.init_q:
+                from .initq_training import decode_with_grad as decode_initq_with_grad
+                return decode_initq_with_grad(self, x, size)
             from .training import decode_with_grad
             return decode_with_grad(self, x, size)
         b, c, h, w = x.shape

@@ -323,6 +323,42 @@ int    diinn_decode_initq(void* stream, const float* feat_dev, const float* pack
                           float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                           int sin_mode);
 
+/* ---- decoder init_q=True, mode 3, under autograd (diinn.py:48-51,113-115,132-139 recorded by autograd; caller
+ * SRLitModule.training_step, sr_module.py:127-129).  Tiled planes: see "training" below. ---------------------------
+ * TRAINING IMAGE.  diinn_pack_initq_train(Fw [576][3], Fb [576], Q0w [256][576], Q0b [256], K0w [256][576],
+ * Kw[i] = K.(i+1).weight [256][832]) writes diinn_initq_train_packed_floats() floats: the init_q image's layout in RADIANS
+ * (nothing divided by 2 pi) with the validity word DIINN_INITQ_TRAIN_MAGIC, then the transposed weights of the backward pass,
+ *     [wave 4][pass 2][chunk 5][kg 32][mt 3 | 2][lane 64][e 4]   (3 M-tiles per k-group in pass 0, 2 in pass 1)
+ *                row n = 32 (5 wave + 3 pass + mt) + (lane & 31) of 640 (n >= 576: zero),  ch = 2 (4 kg + e) + (lane >> 5);
+ *                chunk 0: K0w[ch][n], chunk i = 1..3: Kw[i-1][ch][256 + n], chunk 4: Q0w[ch][n].
+ * Every float is a reference value, zero or the validity word: the device re-pack of an optimiser step is one gather.
+ * The body image is the training image of mode 3 with a zero Q0 table.
+ *
+ * diinn_decode_initq_train_fwd: the training forward.  feat_dev [B,64,H,W] -> the pixel planes of the WHOLE image in radians
+ *   (pix_dev: diinn_initq_pix_bytes(B, Wu, Hu) bytes) -> out_dev [B,3,Hu,Wu] and acts_dev in diinn_decode_train_fwd's layout
+ *   (k_i in rows 0..255, s_i in rows 256..511 of group i, radians).  The inference entry points answer NaN on a training image.
+ * diinn_initq_backward: from the gate gradients G_dev [4][T][512][32] of diinn_backward_data, per HR pixel
+ *       dx' = sum_i Wx_i^T g_a,i,  t = Q0^T g_s,0,  a = Fw syn + bF (the forward's operation order),  E = sin a,
+ *       U = dx' * E,  dA = (dx' * X[cell] + t) * cos a,  XP = E * X[cell]
+ *   as tiled groups U_dev, dA_dev [T][576][32] and XP_dev, E_dev [T][640][32] (rows 576..639 written as zeros, so that
+ *   diinn_plane_gemm_nt takes them as its 640-row operand).  9,728 bytes per HR pixel.  fp32 MFMA; no atomics.
+ * diinn_cell_sum_rows: out_dev [B][R][H][W] = per-LR-cell sums of rows [0, R) of one tiled group of `rows` rows per tile
+ *   (seg tables as for diinn_backward_cell_sum; a cell that owns no pixel gets zero).
+ * diinn_fold3x3: dfeat_dev [B][C][H][W] = the adjoint of F.unfold(., 3, padding=1) applied to dxunf_dev [B][9 C][H][W].
+ * All validate every argument before the first launch; none allocates or synchronises. */
+#define DIINN_INITQ_TRAIN_MAGIC 0x44495154u   /* "DIQT" */
+size_t diinn_initq_train_packed_floats(void);
+int    diinn_pack_initq_train(const float* Fw, const float* Fb, const float* Q0w, const float* Q0b, const float* K0w,
+                              const float* const Kw[3], float* packed);
+int    diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                    float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu,
+                                    int sin_mode);
+int    diinn_initq_backward(void* stream, const float* feat_dev, const float* G_dev, const float* train_image_dev,
+                            float* U_dev, float* dA_dev, float* XP_dev, float* E_dev, int B, int H, int W, int Hu, int Wu);
+int    diinn_cell_sum_rows(void* stream, const float* group_dev, int rows, int R, const int32_t* seg_h_dev,
+                           const int32_t* seg_w_dev, float* out_dev, int B, int H, int W, int Hu, int Wu);
+int    diinn_fold3x3(void* stream, const float* dxunf_dev, float* dfeat_dev, int B, int C, int H, int W);
+
 /* ---- training ------------------------------------
  * TILED PLANES.  Every per-pixel training buffer is a group of C channel rows over npix = B*Hu*Wu
  * pixels (pixel index (b*Hu + y)*Wu + x), stored as [ceil(npix/32) tiles][C rows][32 pixels] fp32:
