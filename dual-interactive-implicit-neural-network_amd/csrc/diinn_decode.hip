@@ -907,6 +907,25 @@ static int decode_mode4_band_impl(void* stream, const float* P_dev, const float*
     return hip_status(hipGetLastError());
 }
 
+// The gather over a WHOLE image for a tap buffer that did not come from decode_kernel<HEAD3>: the training forward of mode 4
+// (diinn_mode4_training.hip: head3x3_taps_from_planes_kernel).  That kernel checks the body image itself and accepts a training
+// image (DIINN_PACKED_MAGIC_WPU), which the gather -- an inference kernel -- answers with NaN; the gather reads nothing of the body
+// image but its validity word, so here it is pointed at a device constant that holds DIINN_PACKED_MAGIC: its own check is then
+// the head image's word alone.  The caller has validated the arguments (Hu, Wu >= 2; B and the row blocks within the grid limits).
+__attribute__((visibility("hidden"))) __device__ unsigned gather_body_word = DIINN_PACKED_MAGIC;     // (never written)
+
+__attribute__((visibility("hidden")))
+int launch_head3x3_whole(void* stream, const float* taps_dev, const float* head_dev, float* out_dev, int B, int Hu, int Wu) {
+    void* word = nullptr;
+    const hipError_t e = hipGetSymbolAddress(&word, HIP_SYMBOL(gather_body_word));      // a table lookup: no allocation, no synchronisation
+    if (e != hipSuccess) return hip_status(e);
+    const float* body = (const float*)word - (OFF_BL + 3);                               // the kernel reads body[OFF_BL + 3] only
+    const dim3 hgrid((Wu + H3_BLOCK_W - 1) / H3_BLOCK_W, (Hu + H3_BLOCK_H - 1) / H3_BLOCK_H, B);
+    const Head3Params hp{taps_dev, body, head_dev, out_dev, Hu, Wu, 0, Hu, 0, Hu, 0, Hu};
+    hipLaunchKernelGGL(head3x3_reflect_kernel, hgrid, dim3(256), 0, (hipStream_t)stream, hp);
+    return hip_status(hipGetLastError());
+}
+
 // init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
 // The throughput kernel only (no 16-pixel latency twin).
 static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,

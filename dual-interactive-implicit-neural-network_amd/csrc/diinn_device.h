@@ -12,7 +12,8 @@
 //   diinn_bf16.hip             decode_bf16_kernel, decode_bf16x2_kernel, decode_bf16_coop_kernel (4 waves),
 //                              decode_bf16_coop8_kernel (8 waves), decode_bf16_coop8p_kernel (8 waves, persistent)
 //   diinn_bf16x3.hip           decode_bf16x3h_kernel (persistent, hi weight pieces through LDS), decode_bf16x3_kernel: split bf16
-//   diinn_training.hip         backward pass: bwd_head / bwd_layer (<KPART=false>: modes 1/2), cell_chain_bwd (modes 1/2), plane_gemm, plane_rowdot, cell_sum
+//   diinn_training.hip         backward pass: bwd_head / bwd_head3x3 (mode 4) / bwd_layer (<KPART=false>: modes 1/2), cell_chain_bwd (modes 1/2), plane_gemm, plane_rowdot, cell_sum
+//   diinn_mode4_training.hip   head3x3_taps_from_planes_kernel (mode 4 under autograd: the 3x3 head's tap values from the saved planes)
 //   diinn_enc_training.hip     the encoder's dense blocks under autograd: conv_wgrad (weight-gradient GEMM over the pixel axis), relu_gate
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
 //   diinn_metasr_training.hip  metasr_bwd_cells_kernel (MetaSR under autograd: the per-cell backward pass)
@@ -85,6 +86,17 @@ __device__ __forceinline__ float dsin<DIINN_SIN_HW_REDUCED>(float x) {
     float r = __builtin_fmaf(x, C_HI, -k);
     r = __builtin_fmaf(x, C_LO, r);
     return __builtin_amdgcn_sinf(r);
+}
+
+// sine and cosine of one argument in radians with HW_REDUCED's reduction: the training backward's gates (q_i = k_i sin(s_i), g_s,i = g_q,i k_i cos(s_i))
+__device__ __forceinline__ void dsincos(float x, float& sn, float& cs) {
+    constexpr float C_HI = 0.15915494309189533577f;
+    constexpr float C_LO = 6.4206383650924e-09f;
+    const float k = __builtin_rintf(x * C_HI);
+    float r = __builtin_fmaf(x, C_HI, -k);
+    r = __builtin_fmaf(x, C_LO, r);
+    sn = __builtin_amdgcn_sinf(r);
+    cs = __builtin_amdgcn_cosf(r);
 }
 
 // The same three modes for an argument already in REVOLUTIONS (the bf16 kernels: synthesis weights and biases

@@ -48,16 +48,6 @@ struct BwdParams {
     int layer;               // bwd_layer_kernel: consumes G_layer, produces G_{layer-1}, Q_{layer-1}
 };
 
-__device__ __forceinline__ void dsincos(float x, float& sn, float& cs) {
-    constexpr float C_HI = 0.15915494309189533577f;
-    constexpr float C_LO = 6.4206383650924e-09f;
-    const float k = __builtin_rintf(x * C_HI);
-    float r = __builtin_fmaf(x, C_HI, -k);
-    r = __builtin_fmaf(x, C_LO, r);
-    sn = __builtin_amdgcn_sinf(r);
-    cs = __builtin_amdgcn_cosf(r);
-}
-
 
 __global__ __launch_bounds__(256) void bwd_head_kernel(const BwdParams p) {
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -74,6 +64,101 @@ __global__ __launch_bounds__(256) void bwd_head_kernel(const BwdParams p) {
         float g = L[c] * g0;
         g = __builtin_fmaf(L[HID + c], g1, g);
         g = __builtin_fmaf(L[2 * HID + c], g2, g);
+        const float kv = p.acts[a0 + (size_t)c * PLANE_TILE];
+        const float sv = p.acts[a0 + (size_t)(HID + c) * PLANE_TILE];
+        float sn, cs;
+        dsincos(sv, sn, cs);
+        p.G[a0 + (size_t)c * PLANE_TILE] = kv > 0.0f ? g * sn : 0.0f;
+        p.G[a0 + (size_t)(HID + c) * PLANE_TILE] = g * kv * cs;
+        p.Q[q0 + (size_t)c * PLANE_TILE] = kv * sn;
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// bwd_head3x3_kernel (decoder mode 4: the adjoint of last_layer = Conv2d(256, 3, 3, padding=1, 'reflect'), diinn.py:89-90,146)
+// bwd_head_kernel's structure -- a thread owns one pixel and 16 channels -- with the 3x3 head in place of the 1x1 one.  With the
+// forward written as T[pix, r = 3 k + c] = H[r] . q_3[pix], out[b, c, y, x] = Lb[c] + sum_k T[b, refl(y + ky - 1), refl(x + kx - 1), k, c]
+// (include/diinn_hip.h, decoder mode 4):
+//     dT[b, y', x', k, c] = sum of g[b, c, y, x] over the (y, x) with refl(y + ky - 1, Hu) = y' and refl(x + kx - 1, Wu) = x'
+//     g_q,3[pix, ch]      = sum_r H[r][ch] dT[pix, r]
+// Per axis a tap has at most two sources: the direct neighbour p - t + 1 (when inside the image) and the reflected border --
+// row 0 into p = 1 for t = 0 (refl(-1) = 1), row n - 1 into p = n - 2 for t = 2 (refl(n) = n - 2); the two never coincide.  The up
+// to four terms of dT are added in the order (direct y, direct x), (direct y, border x), (border y, direct x), (border y, border x),
+// the first one present starting the sum.  g_q,3 is ONE FMA chain over r = 0..26 ascending that starts from the product of r = 0, and
+// the gates are bwd_head_kernel's term for term: with a head whose only non-zero tap is the centre one, carrying a 1x1 head L, the
+// planes are bit-identical to bwd_head_kernel's on L (dT[12..14] = g, and adding 0 * x leaves the chain's value unchanged).
+// The workgroups of channel group 0 also write dT as seven tiled 4-row groups [7][ntiles][4][32] (row 27 zero): the right-hand
+// sides of the head's weight gradient dLw[c, ch, ky, kx] = sum_pix q_3[pix, ch] dT[pix, k, c] (diinn_plane_rowdot).
+// ---------------------------------------------------------------------------------
+struct BwdHead3Params {
+    const float* head3;      // head image [27][256]
+    const float* acts;       // as BwdParams
+    const float* gout;       // [3][npix] plain planes
+    float* G;
+    float* Q;
+    float* dT;               // [7][ntiles][4][32]
+    long long npix, ntiles;
+    int Hu, Wu;
+};
+
+__global__ __launch_bounds__(256) void bwd_head3x3_kernel(const BwdHead3Params p) {
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= p.npix) return;
+    const size_t np = (size_t)p.npix;
+    const long long hw = (long long)p.Hu * p.Wu;
+    const long long b = pix / hw;
+    const int rem = (int)(pix - b * hw);
+    const int y = rem / p.Wu, x = rem - y * p.Wu;
+    const float* __restrict__ gb = p.gout + (size_t)b * hw;        // plane 0 of this pixel's image; plane c is c * npix further
+    float dt[TAPS];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int yd = y - ky + 1;
+        const bool ydv = yd >= 0 && yd < p.Hu;
+        const bool yev = (ky == 0 && y == 1) || (ky == 2 && y == p.Hu - 2);
+        const int ye = ky == 0 ? 0 : p.Hu - 1;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int xd = x - kx + 1;
+            const bool xdv = xd >= 0 && xd < p.Wu;
+            const bool xev = (kx == 0 && x == 1) || (kx == 2 && x == p.Wu - 2);
+            const int xe = kx == 0 ? 0 : p.Wu - 1;
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+            bool any = false;
+            auto term = [&](bool v, int yy, int xx) {
+                if (v) {
+                    const float* __restrict__ s = gb + (size_t)yy * p.Wu + xx;
+                    const float t0 = s[0], t1 = s[np], t2 = s[2 * np];
+                    a0 = any ? a0 + t0 : t0;
+                    a1 = any ? a1 + t1 : t1;
+                    a2 = any ? a2 + t2 : t2;
+                    any = true;
+                }
+            };
+            term(ydv && xdv, yd, xd);
+            term(ydv && xev, yd, xe);
+            term(yev && xdv, ye, xd);
+            term(yev && xev, ye, xe);
+            dt[3 * (3 * ky + kx) + 0] = a0;
+            dt[3 * (3 * ky + kx) + 1] = a1;
+            dt[3 * (3 * ky + kx) + 2] = a2;
+        }
+    }
+    const size_t tile = (size_t)(pix >> 5), lane = (size_t)(pix & 31);
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int r = 0; r < TAP_STRIDE; ++r)
+            p.dT[(((size_t)(r >> 2) * p.ntiles + tile) * 4 + (r & 3)) * PLANE_TILE + lane] = r < TAPS ? dt[r < TAPS ? r : 0] : 0.0f;
+    }
+    const float* __restrict__ H = p.head3;
+    const size_t a0 = ((size_t)3 * p.ntiles + tile) * ACT_ROWS * PLANE_TILE + lane;   // layer 3 tile, row 0
+    const size_t q0 = ((size_t)3 * p.ntiles + tile) * HID * PLANE_TILE + lane;
+    const int c0 = blockIdx.y * 16;
+#pragma unroll 2
+    for (int c = c0; c < c0 + 16; ++c) {
+        float g = H[c] * dt[0];
+#pragma unroll
+        for (int r = 1; r < TAPS; ++r) g = __builtin_fmaf(H[r * HID + c], dt[r], g);
         const float kv = p.acts[a0 + (size_t)c * PLANE_TILE];
         const float sv = p.acts[a0 + (size_t)(HID + c) * PLANE_TILE];
         float sn, cs;
@@ -812,6 +897,33 @@ int diinn_backward_data(void* stream, const float* gout_planes_dev, const float*
         p.layer = layer;
         if (layer == 3 && !split_head) hipLaunchKernelGGL(bwd_layer_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
         else hipLaunchKernelGGL(bwd_layer_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_status(e);
+    }
+    return DIINN_OK;
+}
+
+int diinn_backward_data_head3x3(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
+                                const float* head_dev, float* G_dev, float* Q_dev, float* dT_tiled_dev, int B, int Hu, int Wu) {
+    if (!gout_planes_dev || !acts_dev || !packed_dev || !head_dev || !G_dev || !Q_dev || !dT_tiled_dev) return DIINN_ERR_INVALID_ARG;
+    if (B <= 0 || Hu < 2 || Wu < 2) return DIINN_ERR_INVALID_ARG;
+    const long long npix = (long long)B * Hu * Wu;
+    const int stp = check_npix(npix);
+    if (stp) return stp;
+    BwdHead3Params hp;
+    hp.head3 = head_dev; hp.acts = acts_dev; hp.gout = gout_planes_dev; hp.G = G_dev; hp.Q = Q_dev; hp.dT = dT_tiled_dev;
+    hp.npix = npix; hp.ntiles = (npix + PLANE_TILE - 1) / PLANE_TILE; hp.Hu = Hu; hp.Wu = Wu;
+    hipLaunchKernelGGL(bwd_head3x3_kernel, dim3((unsigned)((npix + 255) / 256), HID / 16), dim3(256), 0, (hipStream_t)stream, hp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_status(e);
+    // everything below layer 3's gates is mode 3's backward: the split form of diinn_backward_data (G_3 and q_3 are in place)
+    BwdParams p;
+    p.Wt = packed_dev; p.acts = acts_dev; p.gout = gout_planes_dev; p.G = G_dev; p.Q = Q_dev;
+    p.npix = npix; p.ntiles = hp.ntiles; p.layer = 0;
+    const unsigned blocks = (unsigned)((p.ntiles + 3) / 4);
+    for (int layer = 3; layer >= 1; --layer) {
+        p.layer = layer;
+        hipLaunchKernelGGL(bwd_layer_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_status(e);
     }

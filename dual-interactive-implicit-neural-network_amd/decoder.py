@@ -542,23 +542,32 @@ class ImplicitDecoder(nn.Module):
     loads); the MI355X kernels implement the paper's final variant, ``mode=3,
     init_q=False`` (README.md:111-112 of the reference), the ablation modes 1 and 2, whose
     modulation branch depends on the LR cell only, and mode 4, mode 3 with a 3x3 reflect-padded
-    head (inference, fp32).  ``init_q=True`` (the per-pixel sine embedding ``first_layer``, diinn.py:48-51,113-115) runs
+    head (fp32; inference, and training with ``hip_autograd_mode4``).  ``init_q=True`` (the per-pixel sine embedding ``first_layer``, diinn.py:48-51,113-115) runs
     for mode 3, inference, fp32; with modes 1, 2, 4 or under autograd ``forward`` raises ``NotImplementedError``.
 
     ``hip_autograd`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, fp32 into
     training: with it set, ``forward(x, size, None)`` under autograd runs ``initq_training.DecodeInitqFunction`` (the HIP kernels
     saving the activations, the backward pass on the HIP kernels; ROCm GPU only).  With ``bsize`` given the call stays the no_grad
     inference path, like the reference's ``batched_step``.  It changes nothing else: modes 1, 2 and 4 with ``init_q``, the bf16
-    arithmetics and every decoder with ``init_q=False`` behave as without it."""
+    arithmetics and every decoder with ``init_q=False`` behave as without it.
+
+    ``hip_autograd_mode4`` (a plain attribute, also a constructor keyword; default False) opts mode 4, ``init_q=False``, fp32 into
+    training: with it set, ``forward(x, size, None)`` under autograd runs ``mode4_training.DecodeMode4Function`` (mode 3's training
+    forward for the saved activations, the 3x3 head from those planes, the backward pass on the HIP kernels; ROCm GPU only, the
+    output at least 2 x 2).  With ``bsize`` given the call stays the no_grad inference path.  It changes nothing else:
+    ``hip_autograd`` alone does not open mode 4, and mode 4 with ``init_q=True`` or a bf16 arithmetic keeps refusing."""
 
     hip_autograd = False
+    hip_autograd_mode4 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
-                 init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False):
+                 init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
+                 hip_autograd_mode4: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
         self.hip_autograd = bool(hip_autograd)
+        self.hip_autograd_mode4 = bool(hip_autograd_mode4)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -646,8 +655,10 @@ class ImplicitDecoder(nn.Module):
 
         Mode 4: the reference's ``batched_step`` applies the head's reflect padding at every column-strip edge, so
         the reference's own result depends on ``bsize`` there.  This path reproduces ``bsize=None``, the whole-image
-        convolution, for any ``bsize``.  Inference only (``torch.no_grad()``), fp32; the image is decoded in chunks
+        convolution, for any ``bsize``.  fp32; the image is decoded in chunks
         of at most ``MODE4_CHUNK_ROWS`` HR rows, which bounds the tap workspace and changes no bit of the result.
+        Under autograd with ``bsize=None`` it raises unless ``hip_autograd_mode4`` is set (then:
+        ``mode4_training.DecodeMode4Function``, the whole image at once).
 
         ``init_q=True`` (mode 3, fp32, inference only): the per-pixel planes the two kernels hand over take 5,120 bytes per
         HR pixel, so the image is decoded in chunks of ``initq_chunk_rows(B, W_up, INITQ_CHUNK_BYTES)`` HR rows; chunking
@@ -660,11 +671,14 @@ class ImplicitDecoder(nn.Module):
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
         initq_grad = self.init_q and self.hip_autograd and self.mode == 3 and self.compute == "f32"     # the opt-in (initq_training.py)
-        if wants_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
+        mode4_grad = self.mode == 4 and self.hip_autograd_mode4 and not self.init_q and self.compute == "f32"   # the opt-in (mode4_training.py)
+        if wants_grad and not mode4_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
             raise NotImplementedError(
                 "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
                 "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
-                "torch.no_grad()")
+                "torch.no_grad() (mode 4 in fp32 with init_q=False trains once ImplicitDecoder.hip_autograd_mode4 is set)")
+        if wants_grad and mode4_grad and (int(size[0]) < 2 or int(size[1]) < 2):
+            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {int(size[0])} x {int(size[1])}")
         if self.init_q and self.compute != "f32":
             raise ValueError("init_q=True runs in fp32 only")
         _require_cuda(x, "x")
@@ -672,6 +686,9 @@ class ImplicitDecoder(nn.Module):
             if self.init_q:
                 from .initq_training import decode_with_grad as decode_initq_with_grad
                 return decode_initq_with_grad(self, x, size)
+            if self.mode == 4:
+                from .mode4_training import decode_with_grad as decode_mode4_with_grad
+                return decode_mode4_with_grad(self, x, size)
             from .training import decode_with_grad
             return decode_with_grad(self, x, size)
         b, c, h, w = x.shape

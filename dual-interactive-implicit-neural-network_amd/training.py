@@ -60,7 +60,10 @@ PARAM_SHAPES: Dict[str, Tuple[int, ...]] = {
 
 
 def param_shapes(mode: int = 3) -> Dict[str, Tuple[int, ...]]:
-    """PARAM_SHAPES for decoder ``mode``: modes 2 and 3 share them; mode 1's K.1..3 see k alone, [256,256,1,1] (diinn.py:53-60)."""
+    """PARAM_SHAPES for decoder ``mode``: modes 2 and 3 share them; mode 1's K.1..3 see k alone, [256,256,1,1] (diinn.py:53-60);
+    mode 4 is mode 3 with the 3x3 head, ``last_layer.weight`` [3,256,3,3] (diinn.py:89-90)."""
+    if mode == 4:
+        return {**PARAM_SHAPES, "last_layer.weight": (3, HIDDEN, 3, 3)}
     if mode != 1:
         return PARAM_SHAPES
     return {**PARAM_SHAPES, **{f"K.{i}.0.weight": (HIDDEN, HIDDEN, 1, 1) for i in (1, 2, 3)}}
@@ -75,8 +78,10 @@ _gather_index_dev: Dict[tuple, torch.Tensor] = {}
 
 
 def _layout(mode: int) -> int:
-    if mode not in (1, 2, 3):
-        raise ValueError(f"the training path covers decoder modes 1-3, got {mode}")
+    """Weight layout of the packed body image: 1 (mode 1) or 3 (modes 2 and 3; mode 4, whose body image is mode 3's with a zero 1x1
+    head -- its 3x3 head is an image of its own, mode4_training.py)."""
+    if mode not in (1, 2, 3, 4):
+        raise ValueError(f"the training path covers decoder modes 1-4, got {mode}")
     return 1 if mode == 1 else 3
 
 
@@ -232,7 +237,7 @@ def _cell_sum(g: torch.Tensor, b: int, hu: int, wu: int, h: int, w: int,
 
 def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor,
                         params: Sequence[torch.Tensor], size: Sequence[int],
-                        need_feat_grad: bool = True) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+                        need_feat_grad: bool = True, head=None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """Gradients of the mode-3 decoder given d(loss)/d(out).
 
     gout [B,3,Hu,Wu]; feat [B,64,H,W]; acts [4,2,256,N] plain planes k_i, s_i (``untile_planes`` of the
@@ -243,22 +248,31 @@ def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tens
     s_0 = Q0 syn + bQ0, s_i = Qw_i q_{i-1} + bQ_i, out = L q_3 + bL:
         g_a,i = g_q,i * sin(s_i) * [k_i > 0]          g_s,i = g_q,i * k_i * cos(s_i)
         g_q,i-1 = Wq_i^T g_a,i + Qw_i^T g_s,i         dWq_i = g_a,i q_{i-1}^T   dQw_i = g_s,i q_{i-1}^T
-        dP_i[cell] = sum over the cell's pixels of g_a,i;  P = conv3x3(feat; Wx) + bK."""
-    p = dict(zip(PARAM_NAMES, params))
+        dP_i[cell] = sum over the cell's pixels of g_a,i;  P = conv3x3(feat; Wx) + bK.
+    Computed in the dtype of ``acts`` (fp32 from the kernels; float64 planes give the formulas' own ground truth).
+    ``head`` (decoder mode 4, mode4_training.backward_from_saved_mode4): (g_q,3 [256,N], d last_layer.weight, d last_layer.bias) of
+    another head than the 1x1 one; ``params``' own ``last_layer`` tensors are then not read."""
+    dt = acts.dtype
+    p = {name: t.to(dt) for name, t in zip(PARAM_NAMES, params)}
+    feat = feat.to(dt)
     b, _, h, w = feat.shape
     hu, wu = int(size[0]), int(size[1])
     n = b * hu * wu
     dev = gout.device
     idx_h, rel_h, idx_w, rel_w, ratio = coordinate_tensors(h, w, hu, wu, dev)
+    rel_h, rel_w = rel_h.to(dt), rel_w.to(dt)
     grads: Dict[str, torch.Tensor] = {}
 
-    g_out = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n)
-    lw = p["last_layer.weight"].reshape(3, HIDDEN)
-    q3 = acts[3, 0] * torch.sin(acts[3, 1])
-    grads["last_layer.weight"] = (g_out @ q3.t()).reshape(3, HIDDEN, 1, 1)
-    grads["last_layer.bias"] = g_out.sum(1)
-    del q3
-    g_q = lw.t() @ g_out                                          # [256, N]
+    if head is not None:
+        g_q, grads["last_layer.weight"], grads["last_layer.bias"] = head
+    else:
+        g_out = gout.to(dt).permute(1, 0, 2, 3).reshape(3, n)
+        lw = p["last_layer.weight"].reshape(3, HIDDEN)
+        q3 = acts[3, 0] * torch.sin(acts[3, 1])
+        grads["last_layer.weight"] = (g_out @ q3.t()).reshape(3, HIDDEN, 1, 1)
+        grads["last_layer.bias"] = g_out.sum(1)
+        del q3
+        g_q = lw.t() @ g_out                                      # [256, N]
 
     d_p: List[Optional[torch.Tensor]] = [None] * 4                # each [B,256,H,W]
     d_wq: List[Optional[torch.Tensor]] = [None] * 4
@@ -439,7 +453,8 @@ def _sum_parts(part: torch.Tensor) -> torch.Tensor:
 
 def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, params: Sequence[torch.Tensor],
                    packed: torch.Tensor, size: Sequence[int],
-                   need_feat_grad: bool = True) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+                   need_feat_grad: bool = True, head: Optional[torch.Tensor] = None
+                   ) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """The same gradients as ``backward_from_saved``, on the HIP kernels throughout:
       diinn_backward_data   3 x bwd_layer_kernel (the head's gates inside layer 3's): the per-pixel chain; leaves the
                             gate gradients G_i = (g_a,i ; g_s,i) and the activations q_i as tiled planes
@@ -447,7 +462,11 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
       diinn_plane_rowdot    the two skinny products (layer 0 against (rel_h, rel_w, ratio, 1); head against g_out)
       diinn_backward_cell_sum   dP = per-cell sums of g_a, NCHW and tiled over the cell axis
       _conv_grads_native    the 3x3 convolution's weight gradient (unfold + plane GEMM) and input gradient (encoder conv kernels)
-    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward."""
+    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward.
+    ``head`` (decoder mode 4): the 3x3 head image (mode4_training.pack_head3x3_on_device); ``packed`` is then the body image with a
+    zero 1x1 head.  Three things change, the rest is the same code: the chain starts with diinn_backward_data_head3x3 (the head's
+    adjoint dT and layer 3's gates in bwd_head3x3_kernel, then layers 3, 2, 1); d last_layer.weight [3,256,3,3] is q_3 against the
+    seven 4-row groups of dT (7 x diinn_plane_rowdot, diinn_sum_parts); d last_layer.bias is the sum of g as before."""
     lib = _native.load()
     p = dict(zip(PARAM_NAMES, params))
     b, _, h, w = feat.shape
@@ -462,12 +481,16 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
     g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
     q = torch.empty((4, t, HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    gout_t = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))     # 4-row right-hand side of the head product
     ksplit = max(1, min(WGRAD_KSPLIT, t))
     rsplit = max(1, min(ROWDOT_SPLITS, t))
+    if head is None:
+        heads = [tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))]     # 4-row right-hand side of the head product
+    else:
+        # dT as seven 4-row groups (row 27 zero), written by bwd_head3x3_kernel; the rowdot reads whole tiles: a ragged last tile's padding is zeroed here
+        heads = (torch.empty if n % PLANE_TILE == 0 else torch.zeros)((7, t, 4, PLANE_TILE), dtype=torch.float32, device=dev)
     part = torch.empty((3, ksplit, 2 * HIDDEN, HIDDEN + 1), dtype=torch.float32, device=dev)
     part0 = torch.empty((rsplit, 2 * HIDDEN, 4), dtype=torch.float32, device=dev)
-    partl = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
+    partl = torch.empty((len(heads), rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
     dp = torch.empty((b, 4 * HIDDEN, h, w), dtype=torch.float32, device=dev)
     # the hoisted conv's weight gradient on the library's own GEMM wants dP tiled over the cell axis as well: cell_sum_kernel
     # writes it (a ragged last tile's padding must be zero: the GEMM reads whole tiles)
@@ -477,21 +500,29 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
-                      "diinn_backward_data")
+        if head is None:
+            _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
+                          "diinn_backward_data")
+        else:
+            _native.check(lib.diinn_backward_data_head3x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(head), ptr(g), ptr(q), ptr(heads),
+                                                          b, hu, wu), "diinn_backward_data_head3x3")
         for i in (3, 2, 1):
             _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(q[i - 1]), HIDDEN, 0,
                                                   ptr(part[i - 1]), 2 * HIDDEN, HIDDEN, n, ksplit, 1),
                           "diinn_plane_gemm_nt")
         _native.check(lib.diinn_plane_rowdot(stream, ptr(g[0]), 2 * HIDDEN, ptr(syn_t), ptr(part0), 2 * HIDDEN, n, rsplit),
                       "diinn_plane_rowdot")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(gout_t), ptr(partl), HIDDEN, n, rsplit),
-                      "diinn_plane_rowdot")
+        for i, rhs in enumerate(heads):
+            _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(rhs), ptr(partl[i]), HIDDEN, n, rsplit),
+                          "diinn_plane_rowdot")
         _native.check(lib.diinn_backward_cell_sum(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t), b, h, w, hu, wu),
                       "diinn_backward_cell_sum")
     grads: Dict[str, torch.Tensor] = {}
-    dl = _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: q_3 . (g_out ; 0)^T
-    grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
+    dl = _sum_parts(partl.view(len(heads), rsplit, -1)).view(len(heads), HIDDEN, 4)    # group i: q_3 . (rows 4 i .. 4 i + 3 of the right-hand side)^T
+    if head is None:                                             # [256, 4]: q_3 . (g_out ; 0)^T
+        grads["last_layer.weight"] = dl[0, :, :3].t().reshape(3, HIDDEN, 1, 1)
+    else:                                                        # [256, r = 3 (3 ky + kx) + c] -> [c, ch, ky, kx]
+        grads["last_layer.weight"] = dl.permute(1, 0, 2).reshape(HIDDEN, 28)[:, :27].t().reshape(3, 3, 3, HIDDEN).permute(2, 3, 0, 1).contiguous()
     grads["last_layer.bias"] = gp.sum(1)
     dws = _sum_parts(part.view(3, ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)   # [3, 512, 257]: [dWq_i ; dQw_i | bias sums]
     d_wq: List[Optional[torch.Tensor]] = [None] * 4
@@ -846,7 +877,7 @@ class DecodeModes12Function(torch.autograd.Function):
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
-    """``ImplicitDecoder.forward(x, size, None)`` under autograd (modes 1, 2 and 3)."""
+    """``ImplicitDecoder.forward(x, size, None)`` under autograd (modes 1, 2 and 3; mode 4: mode4_training.decode_with_grad)."""
     named = dict(decoder.named_parameters())
     params = [named[name] for name in PARAM_NAMES]
     hu, wu = size

@@ -254,7 +254,9 @@ int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B,
  *     refl(-1, n) = 1, refl(n, n) = n - 2     (PyTorch 'reflect': Hu >= 2 and Wu >= 2, else DIINN_ERR_INVALID_ARG -- the
  *                                              reference raises there too)
  * The first line runs inside the register-resident decode kernel (27 dot products in place of mode 3's 3), the second is a
- * small kernel of its own over the TAP BUFFER.  fp32 only; inference only.
+ * small kernel of its own over the TAP BUFFER.  fp32 only.  These entry points are the inference path; under autograd the same
+ * head runs from the saved planes of the mode-3 training forward (diinn_head3x3_from_planes, diinn_backward_data_head3x3 below,
+ * "Training, decoder mode 4").
  *
  * IMAGES.  The body image is diinn_pack_weights of the K / Q tensors with a ZERO 1x1 head (Lw [3,256] and Lb all zero);
  * the head is a second, small image: diinn_pack_head3x3(Lw [3][256][3][3], Lb [3]) writes diinn_head3x3_packed_floats()
@@ -408,6 +410,34 @@ int diinn_backward_data(void* stream, const float* gout_planes_dev, const float*
  * diinn_cell_chain_bwd.  dQw_i = g_s,i q_{i-1}^T is diinn_plane_gemm_nt on rows 256..511 of G_i.  3 kernels. */
 int diinn_backward_data_qonly(void* stream, const float* gout_planes_dev, const float* acts_dev,
                               const float* packed_dev, float* G_dev, float* Q_dev, long long npix);
+
+/* ---- Training, decoder mode 4 (autograd through diinn.py:89-90,140-147 with bsize = None) ---------------------------------------
+ * Mode 4 differs from mode 3 only behind q_3 = k_3 sin(s_3), and the mode-3 training forward saves k_3 and s_3.  So the forward is
+ * diinn_precompute_P_wpu + diinn_decode_train_fwd on the BODY image (the training image of the K / Q tensors with a zero 1x1 head;
+ * its `out` is discarded) followed by diinn_head3x3_from_planes; the backward is diinn_backward_data_head3x3 and, below layer 3's
+ * gates, everything mode 3 has.  With k = 3 ky + kx, r = 3 k + c, H the head image's [27][256] rows and g = d loss / d out:
+ *     dT[b, y', x', k, c] = sum of g[b, c, y, x] over the (y, x) with refl(y + ky - 1, Hu) = y' and refl(x + kx - 1, Wu) = x'
+ *                           (per axis the direct neighbour, plus row 0 into y' = 1 for ky = 0 and row Hu - 1 into y' = Hu - 2 for
+ *                            ky = 2; added in a fixed order)
+ *     g_q,3[pix, ch]      = sum_r H[r][ch] dT[pix, r]      (one FMA chain, r ascending, started by the product of r = 0)
+ *     dLw[c, ch, ky, kx]  = sum_pix q_3[pix, ch] dT[pix, k, c],      dLb[c] = sum of g[:, c]
+ *
+ * diinn_head3x3_from_planes: acts_dev from diinn_decode_train_fwd (group 3 is read, 2 KiB per HR pixel) -> taps_dev, the tap buffer
+ *   of the whole image [B][Hu][Wu][28] (diinn_mode4_taps_bytes(B, Hu, Wu, 0, Hu) bytes), -> out_dev [B,3,Hu,Wu] by the inference
+ *   path's 9-point gather.  Two kernels (the first a 32-row fp32 MFMA per 32-pixel plane tile, bound by the planes it reads).  packed_dev: the body image, of which only the validity word is read: DIINN_PACKED_MAGIC
+ *   or DIINN_PACKED_MAGIC_WPU (a training image); any other word, or a head image without DIINN_HEAD3X3_MAGIC, answers NaN in
+ *   every output.
+ * diinn_backward_data_head3x3: diinn_backward_data with the 3x3 head.  gout_planes_dev [3][B Hu Wu] plain planes; G_dev, Q_dev
+ *   as there; dT_tiled_dev receives dT as seven tiled 4-row groups [7][T][4][32] (group i, row j = r = 4 i + j; row 27 zero), the
+ *   right-hand sides of dLw under diinn_plane_rowdot with A = q_3 -- the caller zeroes it first when B Hu Wu % 32 != 0 (the rowdot
+ *   reads whole tiles).  Four kernels: the head's adjoint and gates, then layers 3, 2, 1 as in diinn_backward_data.
+ * Both: NULL pointers, B <= 0, Hu < 2 or Wu < 2 return DIINN_ERR_INVALID_ARG before any HIP call; B Hu Wu is limited like
+ * diinn_backward_data's npix (DIINN_TRAIN_MAX_PIXELS); diinn_head3x3_from_planes wants acts_dev, head_dev and taps_dev 16-byte
+ * aligned.  No allocation, no synchronisation. */
+int diinn_head3x3_from_planes(void* stream, const float* acts_dev, const float* packed_dev, const float* head_dev,
+                              float* taps_dev, float* out_dev, int B, int Hu, int Wu);
+int diinn_backward_data_head3x3(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
+                                const float* head_dev, float* G_dev, float* Q_dev, float* dT_tiled_dev, int B, int Hu, int Wu);
 
 /* Weight-gradient GEMM over the pixel axis: C[M x Nc] = A . B^T where A = rows [a_row0, a_row0+M) of a tiled
  * group with a_rows rows per tile and B = rows [b_row0, b_row0+Nc) of a tiled group with b_rows rows;
