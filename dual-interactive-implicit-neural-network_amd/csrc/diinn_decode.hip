@@ -18,6 +18,7 @@
 //                         training forward, k_i of the pixel's cell replicated per pixel);
 //                         <HEAD3>: decoder mode 4, the head is the 27 per-pixel tap values of the 3x3 conv
 //   head3x3_reflect_kernel : decoder mode 4, the reflect-padded 9-point gather over the tap buffer
+//   cell_chain_kernel, pixel_chain_kernel : decoder modes 1/2, the modulation chain per LR cell / (init_q=True) per HR pixel
 //   decode_bf16_kernel, decode_bf16x2_kernel : bf16 operands in layers 1..3 (optional paths)
 //   bwd_layer_kernel (+ bwd_head_kernel), plane_gemm_lds_kernel, plane_rowdot_kernel, cell_sum_kernel :
 //                         backward pass of the decoder (training)
@@ -49,14 +50,25 @@ struct TagCoopT { static constexpr bool value = true; };
 // its sine argument there and not from the Q0 table (whose rows the preamble skips); everything else is the code below as it is.
 // INITQ rides in the first template argument, SIN_X = sine mode | DECODE_INITQ: the kernel keeps its four parameters, so every
 // instantiation that existed before keeps its symbol name (and its instructions); the new ones are decode_kernel<SIN | DECODE_INITQ>.
+//
+// init_q with the other modes (inference only):
+//   * modes 1/2, decode_kernel<SIN | DECODE_INITQ, KPART = false>: pixel_chain_kernel has written k_1..3 over channels 256..1023 of
+//     the pixel's record, which the layers read as the multiplier exactly as they read the per-cell chain in P otherwise;
+//   * mode 4, decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS>: the tap form (HEAD3) reading the pixel's own record.  The tap form of
+//     init_q rides in SIN_X too, NOT in the fourth template argument: the three decode_kernel<SIN, true, false, true> symbols stay
+//     the only ones of that spelling (what picks mode 4's tap kernels out of the library by name keeps finding exactly those).
 constexpr int DECODE_INITQ = 4;
-template <int SIN_X, bool KPART = true, bool SAVE = false, bool HEAD3 = false>
+constexpr int DECODE_TAPS = 8;
+template <int SIN_X, bool KPART = true, bool SAVE = false, bool HEAD3_ARG = false>
 __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
     constexpr int SIN_MODE = SIN_X & (DECODE_INITQ - 1);
     constexpr bool INITQ = (SIN_X & DECODE_INITQ) != 0;
-    static_assert(SIN_X >= 0 && SIN_X < 2 * DECODE_INITQ && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | DECODE_INITQ");
+    constexpr bool HEAD3 = HEAD3_ARG || (SIN_X & DECODE_TAPS) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * DECODE_TAPS && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | DECODE_INITQ | DECODE_TAPS");
+    static_assert(!(SIN_X & DECODE_TAPS) || (INITQ && !HEAD3_ARG), "DECODE_TAPS: the tap form of init_q only");
     static_assert(!(HEAD3 && SAVE), "mode 4 is inference only");
-    static_assert(!INITQ || (KPART && !HEAD3), "init_q: mode 3");   // (with SAVE: the planes are in radians, INITQ_RAD of initq_planes_kernel)
+    // init_q: mode 3 (with SAVE: the planes are in radians, INITQ_RAD of initq_planes_kernel); modes 1/2 and mode 4, inference only
+    static_assert(!INITQ || (KPART && !HEAD3) || (!SAVE && KPART == HEAD3), "init_q: mode 3, or modes 1/2 / mode 4 without SAVE");
     // The small tables of layer 0 and of the head go through LDS: a vector-memory instruction blocks its wave for
     // ~60 cycles (stamps), and a wave reading them straight from the packed image issued 128 + 96
     // of those per tile.  Rows: Q0h, Q0w, t = fma(Q0r, ratio, bQ0) (the pixel-independent part of the sine
@@ -586,19 +598,11 @@ struct ChainParams {
     int B, H, W, r0, r1, Prow0, Prows;
 };
 
-__global__ __launch_bounds__(256, 1) void cell_chain_kernel(const ChainParams p) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5, j = lane & 31;
-    const int x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
-    const int y = p.r0 + blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
-    const int b = blockIdx.z;
-    const bool valid = (x < p.W) && (y < p.r1);
-    if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
-    const int xc = x < p.W ? x : p.W - 1;
-    const int yc = y < p.r1 ? y : p.r1 - 1;
-    float* __restrict__ Pc = p.P + (((size_t)b * p.Prows + (yc - p.Prow0)) * p.W + xc) * PCH + 4 * h;
-
+// The chain of one wave's 32 records (shared by cell_chain_kernel and pixel_chain_kernel): Pc = the lane's record + 4 h, the
+// first 1024 floats of which are the four 256-channel slots.  BK_SEEDS: layers 1..3 are seeded from bK_i of the packed image
+// (slots 1..3 of the record are written, never read); otherwise from the slot itself, which k_i then overwrites.
+template <bool BK_SEEDS>
+__device__ __forceinline__ void chain_body(float* __restrict__ Pc, const float* Wt, const bool valid, const int lane, const int h) {
     float k[128];
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
@@ -609,7 +613,7 @@ __global__ __launch_bounds__(256, 1) void cell_chain_kernel(const ChainParams p)
 
     constexpr int PF = DECODE_PREFETCH;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
+        (void*)Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
     const int lane_off = lane * 16;
     int wp = (int)(OFF_WL * sizeof(float));
     f32x4 rk[PF];
@@ -624,7 +628,9 @@ __global__ __launch_bounds__(256, 1) void cell_chain_kernel(const ChainParams p)
             f32x16 ak;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4 pv = *(const f32x4*)(Pl + 32 * m + 8 * g);
+                f32x4 pv;
+                if constexpr (BK_SEEDS) pv = *(const f32x4*)(Wt + OFF_BK + (layer + 1) * HID + 4 * h + 32 * m + 8 * g);
+                else pv = *(const f32x4*)(Pl + 32 * m + 8 * g);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ak[4 * g + e] = pv[e];
             }
@@ -651,6 +657,66 @@ __global__ __launch_bounds__(256, 1) void cell_chain_kernel(const ChainParams p)
         for (int i = 0; i < 128; ++i) k[i] = kn[i];
         wp += (int)(WL_LAYER * sizeof(float));
     }
+}
+
+__global__ __launch_bounds__(256, 1) void cell_chain_kernel(const ChainParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31;
+    const int x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
+    const int y = p.r0 + blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
+    const int b = blockIdx.z;
+    const bool valid = (x < p.W) && (y < p.r1);
+    if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
+    const int xc = x < p.W ? x : p.W - 1;
+    const int yc = y < p.r1 ? y : p.r1 - 1;
+    float* __restrict__ Pc = p.P + (((size_t)b * p.Prows + (yc - p.Prow0)) * p.W + xc) * PCH + 4 * h;
+    chain_body<false>(Pc, p.Wt, valid, lane, h);
+}
+
+// ---------------------------------------------------------------------------------
+// pixel_chain_kernel (decoder modes 1 and 2 with init_q=True, diinn.py:113-131): x' = E * X[cell] depends on the HR pixel, so the
+// modulation chain does too.  cell_chain_kernel's scheme with the HR pixels of a chunk in place of LR cells and the pixel
+// records of initq_planes_kernel (stride PIX_CH) in place of P: k_i = relu(K_i[:, :256] k_{i-1} + seed_i) overwrites channels
+// 256 i .. 256 i + 255 of the pixel's record, and decode_kernel<SIN | DECODE_INITQ, KPART = false> reads it as the multiplier.
+// seed_i is the slot itself (mode 2: Wx_i . x' + bK_i from the 1280-row planes) or, BK_SEEDS (mode 1, the 512-row planes, which
+// leave those slots unwritten), bK_i from the packed image.  A lane past the chunk's edge computes on a record of its own wave
+// and stores nothing (as in cell_chain_kernel).  No atomics, no scratch; a pixel's arithmetic depends on the pixel alone.
+// ---------------------------------------------------------------------------------
+struct PixChainParams {
+    float* pix;          // [B][rows][Wu][PIX_CH]: the pixel planes of one chunk of HR rows
+    const float* Wt;
+    int B, Wu, rows;
+};
+
+template <bool BK_SEEDS>
+__global__ __launch_bounds__(256, 1) void pixel_chain_kernel(const PixChainParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31;
+    const int x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
+    const int y = blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
+    const int b = blockIdx.z;
+    const bool valid = (x < p.Wu) && (y < p.rows);
+    if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
+    const int xc = x < p.Wu ? x : p.Wu - 1;
+    const int yc = y < p.rows ? y : p.rows - 1;
+    float* __restrict__ Pc = p.pix + (((size_t)b * p.rows + yc) * p.Wu + xc) * PIX_CH + 4 * h;
+    chain_body<BK_SEEDS>(Pc, p.Wt, valid, lane, h);
+}
+
+static int pixel_chain_impl(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, bool bk_seeds) {
+    if (!pix_dev || !packed_dev) return DIINN_ERR_INVALID_ARG;
+    if (B <= 0 || Wu <= 0 || rows <= 0) return DIINN_ERR_INVALID_ARG;
+    if ((((size_t)pix_dev) | ((size_t)packed_dev)) & 15) return DIINN_ERR_INVALID_ARG;      // 16-byte seeds and pieces
+    if ((double)rows * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    const dim3 grid((Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X),
+                    (rows + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y), B);
+    if (grid.y > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
+    const PixChainParams p{pix_dev, packed_dev, B, Wu, rows};
+    if (bk_seeds) hipLaunchKernelGGL(pixel_chain_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(pixel_chain_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
 }
 
 
@@ -927,9 +993,9 @@ int launch_head3x3_whole(void* stream, const float* taps_dev, const float* head_
 }
 
 // init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
-// The throughput kernel only (no 16-pixel latency twin).
+// The throughput kernel only (no 16-pixel latency twin).  kpart = false: modes 1/2, the planes hold the per-pixel chain (diinn_pixel_chain).
 static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
-                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool kpart = true) {
     if (!pix_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -955,6 +1021,15 @@ static int decode_initq_band_impl(void* stream, const float* pix_dev, const floa
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
     const dim3 grid(gx, gy, B);
+    if (!kpart) {
+        if (sin_mode == DIINN_SIN_HW)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (sin_mode == DIINN_SIN_HW_REDUCED)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        return hip_status(hipGetLastError());
+    }
     if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
@@ -964,7 +1039,120 @@ static int decode_initq_band_impl(void* stream, const float* pix_dev, const floa
     return hip_status(hipGetLastError());
 }
 
+// init_q with mode 4: HR rows [y0,y1) from the pixel planes of the tap rows [ty0,ty1) = [max(0, y0-1), min(Hu, y1+1)): the tap form
+// decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS> over those rows into the tap buffer of decode_mode4_band_impl's layout, then the same
+// gather.  out_dev is a contiguous [B,3,Hu,Wu].
+static int decode_initq_mode4_band_impl(void* stream, const float* pix_dev, const float* packed_dev, const float* head_dev,
+                                        float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                        int sin_mode) {
+    if (!pix_dev || !packed_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
+    int st = check_dims(B, H, W);
+    if (st) return st;
+    int ty0, ty1, r0, r1;
+    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);      // Hu, Wu >= 2 and 0 <= y0 < y1 <= Hu
+    if (st) return st;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
+    const int gy = (ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
+    const dim3 hgrid((Wu + H3_BLOCK_W - 1) / H3_BLOCK_W, (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H, B);
+    if (gy > 65535 || hgrid.y > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
+    DecodeParams p;
+    p.P = pix_dev; p.Wt = packed_dev; p.out = taps_dev; p.head3 = head_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = ty0; p.y1 = ty1;
+    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
+    p.Prow0 = ty0; p.Prows = ty1 - ty0; p.Orow0 = ty0; p.Orows = ty1 - ty0;         // the pixel planes and the tap buffer: the tap rows
+    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_bs = 0; p.o_ps = 0; p.o_rs = 0;           // (unused by the tap form)
+    p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;                                    // (p.acts shares p.head3's storage: left alone)
+    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
+#ifdef DIINN_STAMPS
+    p.stamps = nullptr;
+#endif
+    const int small = diinn_uses_small_output_kernel(Hu, Wu);
+    p.ah = make_axis(H, Hu, small);
+    p.aw = make_axis(W, Wu, small);
+    const dim3 grid(gx, gy, B);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    st = hip_status(hipGetLastError());
+    if (st) return st;
+    const Head3Params hp{taps_dev, packed_dev, head_dev, out_dev, Hu, Wu, y0, y1, ty0, ty1 - ty0, 0, Hu};
+    hipLaunchKernelGGL(head3x3_reflect_kernel, hgrid, dim3(256), 0, (hipStream_t)stream, hp);
+    return hip_status(hipGetLastError());
+}
+
+// The launches of an init_q entry point all validate alike; the "all in order" entries check everything a later launch would
+// refuse BEFORE the first launch, so that a bad argument launches nothing.
+static int initq_args_ok(const void* a, const void* b, const void* c, const void* d, const void* e,
+                         int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!a || !b || !c || !d || !e) return DIINN_ERR_INVALID_ARG;
+    const int st = check_dims(B, H, W);
+    if (st) return st;
+    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    if (B > 65535 || (y1 - y0 + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
+    return DIINN_OK;
+}
+
+static int decode_initq_mode12(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                               float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode,
+                               bool rows512) {
+    int st = initq_args_ok(feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    if ((((size_t)pix_dev) | ((size_t)packed_dev)) & 15) return DIINN_ERR_INVALID_ARG;
+    st = launch_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, rows512);
+    if (st) return st;
+    st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, y1 - y0, rows512);
+    if (st) return st;
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
 extern "C" {
+
+int diinn_pixel_chain(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, int bk_seeds) {
+    return pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, rows, bk_seeds != 0);
+}
+
+int diinn_decode_initq_qonly_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+int diinn_decode_initq_mode1(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_initq_mode12(stream, feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, true);
+}
+
+int diinn_decode_initq_mode2(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_initq_mode12(stream, feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+int diinn_decode_initq_mode4_band(void* stream, const float* pix_dev, const float* packed_dev, const float* head_dev,
+                                  float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                  int sin_mode) {
+    return decode_initq_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
+
+int diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             const float* head_dev, float* pix_dev, float* taps_dev, float* out_dev,
+                             int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!head_dev || !taps_dev) return DIINN_ERR_INVALID_ARG;
+    int st = initq_args_ok(feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    int ty0, ty1, r0, r1;
+    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
+    if (st) return st;
+    if ((ty1 - ty0 + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
+    st = diinn_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, ty0, ty1, sin_mode);
+    if (st) return st;
+    return decode_initq_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
 
 int diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
                             int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {

@@ -360,7 +360,8 @@ int launch_decode_bf16(void* stream, const DecodeParams& p, int gx, int gy, int 
 // diinn_initq.hip: initq_planes_kernel for HR rows [y0,y1); rad: the radians form on the init_q training image (the training forward)
 __attribute__((visibility("hidden")))
 int launch_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
-                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad);
+                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad,
+                        bool rows512 = false);
 // diinn_conv_x3.hip: a split-bf16 3x3 layer reading planes or the trunk's split-format buffer (and optionally extending it);
 // a block's 1x1 fusion layer from that buffer (diinn_rdn_forward_ex, DIINN_RDN_ALGO_X3)
 extern "C" __attribute__((visibility("hidden")))

@@ -537,6 +537,13 @@ size_t diinn_initq_pix_bytes(int B, int Wu, int rows) {
     return (size_t)B * (size_t)rows * (size_t)Wu * PIX_CH * sizeof(float);
 }
 
+// init_q with mode 4: the planes of the tap rows [max(0, y0-1), min(Hu, y1+1)) of output rows [y0,y1)
+size_t diinn_initq_mode4_pix_bytes(int B, int Hu, int Wu, int y0, int y1) {
+    if (B <= 0 || Hu < 2 || Wu < 2 || y0 < 0 || y1 > Hu || y0 >= y1) return 0;
+    const int a = y0 > 0 ? y0 - 1 : 0, b = y1 < Hu ? y1 + 1 : Hu;
+    return diinn_initq_pix_bytes(B, Wu, b - a);
+}
+
 int diinn_window_rows(int H, int Hu, int Wu, int y0, int y1,
                       int* feat_row0, int* feat_rows, int* p_row0, int* p_rows) {
     int r0, r1;

@@ -1,4 +1,4 @@
-// diinn_initq.hip -- decoder init_q=True, mode 3: the per-pixel sine embedding and the two per-pixel GEMMs it forces
+// diinn_initq.hip -- decoder init_q=True: the per-pixel sine embedding and the two per-pixel GEMMs it forces (every mode's planes)
 // (part of libdiinn_hip.so; shared definitions in diinn_device.h, image and plane layout in diinn_layout.h)
 //
 // Reference path replaced: ImplicitDecoder.step with init_q (diinn.py:48-51,113-115):
@@ -8,7 +8,8 @@
 // (precompute_P_kernel) is gone: per pixel,
 //   PIX[0..1023]    = Wx . x' + bK                           (1024 x 576; what P[cell] holds when init_q is off)
 //   PIX[1024..1279] = (Q0 . E + bQ0) / (2 pi)                (256 x 576; layer 0's sine argument, in revolutions)
-// decode_kernel<SIN | DECODE_INITQ> (diinn_decode.hip) runs the layers and the head from these planes.
+// decode_kernel<SIN | DECODE_INITQ> (diinn_decode.hip) runs the layers and the head from these planes (mode 3; modes 1/2 after
+// pixel_chain_kernel, mode 4 in its tap form: see there).  Mode 1 needs channels 0..255 and 1024..1279 only: INITQ_ROWS512.
 #include "diinn_device.h"
 
 // ---------------------------------------------------------------------------------
@@ -46,10 +47,18 @@ constexpr int IQ_ITERS = IQ_BUF / 256;                    // 144 slots per threa
 // 1024..1279 leave in radians, as decode_kernel<SIN | DECODE_INITQ, true, SAVE> saves them.  The flag rides in the template
 // argument, SIN_X = sine mode | INITQ_RAD, like DECODE_INITQ in decode_kernel: the inference instantiations keep their symbols.
 constexpr int INITQ_RAD = 4;
+// INITQ_ROWS512 (decoder mode 1 with init_q: K.1..3 are [256 x 256], the feature halves of Wx_1..3 do not exist and the body image
+// holds zeros there): pass 2 computes Wx_0 alone, ONE M-tile pair per wave (channels 64 wave .. 64 wave + 63) in place of four, and
+// channels 256..1023 of the record are NOT written -- pixel_chain_kernel<BK_SEEDS = true> seeds layers 1..3 from bK_i of the body
+// image and writes k_i there.  Channels 0..255 and 1024..1279 hold the bits of the 1280-row form (the same gemm_pair, the same k
+// order).  Rides in SIN_X as well; inference only.
+constexpr int INITQ_ROWS512 = 8;
 template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams p) {
     constexpr int SIN_MODE = SIN_X & (INITQ_RAD - 1);
     constexpr bool RAD = (SIN_X & INITQ_RAD) != 0;
+    constexpr bool ROWS512 = (SIN_X & INITQ_ROWS512) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * INITQ_ROWS512 && !(RAD && ROWS512), "sine mode | INITQ_RAD or sine mode | INITQ_ROWS512");
     __shared__ __attribute__((aligned(16))) float buf[IQ_BUF];
     __shared__ __attribute__((aligned(16))) float tr[4][32 * IQ_TR_PITCH];
     const int lane = threadIdx.x & 63;
@@ -202,14 +211,19 @@ __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams 
     {
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
+        if constexpr (ROWS512) {
+            gemm_pair(wrs, (int)(OFF_WP * sizeof(float)) + wave * (WP_KG * 2 * PIECE_BYTES), p.Wt + OFF_BK + 64 * wave, 0u, 64 * wave);
+        } else {
 #pragma unroll 1
-        for (int mp = 4 * wave; mp < 4 * wave + 4; ++mp)
-            gemm_pair(wrs, (int)(OFF_WP * sizeof(float)) + mp * (WP_KG * 2 * PIECE_BYTES), p.Wt + OFF_BK + 64 * mp, 0u, 64 * mp);
+            for (int mp = 4 * wave; mp < 4 * wave + 4; ++mp)
+                gemm_pair(wrs, (int)(OFF_WP * sizeof(float)) + mp * (WP_KG * 2 * PIECE_BYTES), p.Wt + OFF_BK + 64 * mp, 0u, 64 * mp);
+        }
     }
 }
 
 int launch_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
-                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad) {
+                        float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad, bool rows512) {
+    if (rad && rows512) return DIINN_ERR_UNSUPPORTED;
     if (!feat_dev || !packed_dev || !initq_dev || !pix_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -236,6 +250,15 @@ int launch_initq_planes(void* stream, const float* feat_dev, const float* packed
             hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
         return hip_status(hipGetLastError());
     }
+    if (rows512) {
+        if (sin_mode == DIINN_SIN_HW)
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (sin_mode == DIINN_SIN_HW_REDUCED)
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW_REDUCED | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        return hip_status(hipGetLastError());
+    }
     if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
@@ -248,4 +271,10 @@ int launch_initq_planes(void* stream, const float* feat_dev, const float* packed
 extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                                   float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
     return launch_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+// decoder mode 1 with init_q: channels 0..255 and 1024..1279 only (INITQ_ROWS512)
+extern "C" int diinn_initq_planes_m1(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                     float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return launch_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, true);
 }

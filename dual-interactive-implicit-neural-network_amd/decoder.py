@@ -188,6 +188,75 @@ def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "
     return out.reshape(b, 3, hu, wu)
 
 
+def initq_modes_forward_reference(sd, feat, size, mode: int, dtype=torch.float64, prefix: str = "") -> torch.Tensor:
+    """The formula sheet of ``init_q=True`` with modes 1, 2 and 4 in tensor algebra, in the RESTRUCTURED form the kernels run (any
+    device, any float dtype), beside ``initq_forward_reference`` (mode 3).
+
+    Reference (diinn.py:112-147), per HR pixel: ``E`` and ``x' = E * X[cell]`` as for mode 3, ``k0 = relu(K0 . x' + bK0)``,
+    ``q0 = k0 * sin(Q0 . E + bQ0)``, ``q_i = k_i * sin(Q_i . q_{i-1} + bQ_i)`` and
+
+        mode 1   k_i = relu(K_i . k_{i-1} + bK_i)            K_i [256,256]
+        mode 2   k_i = relu(K_i . [k_{i-1}; x'] + bK_i)      K_i [256,832]
+        mode 4   k_i = relu(K_i . [q_{i-1}; x'] + bK_i),     then Conv2d(256, 3, 3, padding=1, 'reflect') over the HR grid
+
+    Restructured, with the pixel record ``PIX`` of ``initq_forward_reference``:
+
+        modes 1/2  PIX[0:256] = K0 . x' + bK0, PIX[1024:1280] = Q0 . E + bQ0 (mode 1: these 512 rows are the whole GEMM,
+                   ``initq_planes_kernel<SIN | INITQ_ROWS512>``); PIX[256 i : 256 i + 256] = K_i[:, 256:] . x' + bK_i (mode 2) or the seed
+                   is bK_i itself (mode 1).  The chain ``k_i = relu(K_i[:, :256] . k_{i-1} + seed_i)`` runs per pixel on its own
+                   (``pixel_chain_kernel``) and the layers read it as the multiplier (``decode_kernel<SIN | DECODE_INITQ, KPART=false>``).
+        mode 4     mode 3's layers from the 1280-row record, the head as 27 tap values per pixel, T[3 ky + kx][c] =
+                   Lw[c, :, ky, kx] . q3 (``decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS>``), and the reflect-padded 9-point gather
+                   over the image (``head3x3_reflect_kernel``).
+    Coordinates and ``ratio`` as in ``initq_forward_reference``."""
+    if mode not in (1, 2, 4):
+        raise ValueError(f"initq_modes_forward_reference states modes 1, 2 and 4 (mode 3: initq_forward_reference), got {mode}")
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
+        return t.to(device=feat.device, dtype=dtype).reshape(shape)
+
+    hu, wu = int(size[0]), int(size[1])
+    x = feat.to(dtype)
+    b, c, h, w = x.shape
+    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
+    iy, rel_h = axis_tables(h, hu, small)
+    ix, rel_w = axis_tables(w, wu, small)
+    dev = feat.device
+    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
+    syn = torch.empty((3, hu, wu), dtype=dtype, device=dev)
+    syn[0] = torch.from_numpy(rel_h).to(dev, dtype)[:, None]
+    syn[1] = torch.from_numpy(rel_w).to(dev, dtype)[None, :]
+    syn[2] = torch.tensor((h * w) / (hu * wu), dtype=dtype, device=dev)
+    n = hu * wu
+    e = torch.sin(get("first_layer.0.weight", (576, 3)) @ syn.reshape(3, n) + get("first_layer.0.bias", (576, 1)))   # [576, n]
+    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
+    xp = e[None] * unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)                                               # [b, 576, n]
+    kin = HIDDEN if mode == 1 else HIDDEN + 576
+    kw = [get(f"K.{i}.0.weight", (HIDDEN, kin)) for i in (1, 2, 3)]
+    bk = [get(f"K.{i}.0.bias", (HIDDEN, 1)) for i in range(4)]
+    k = torch.relu(get("K.0.0.weight", (HIDDEN, 576)) @ xp + bk[0])                                                 # PIX[0:256]
+    q = k * torch.sin(get("Q.0.0.weight", (HIDDEN, 576)) @ e + get("Q.0.0.bias", (HIDDEN, 1)))[None]              # PIX[1024:1280]
+    for i in (1, 2, 3):
+        seed = bk[i] if mode == 1 else kw[i - 1][:, HIDDEN:] @ xp + bk[i]                                         # PIX[256 i : 256 i + 256]
+        k = torch.relu(kw[i - 1][:, :HIDDEN] @ (q if mode == 4 else k) + seed)
+        q = k * torch.sin(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1)))
+    if mode != 4:
+        return (get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))).reshape(b, 3, hu, wu)
+    lw = get("last_layer.weight", (3, HIDDEN, 3, 3))
+    taps = torch.einsum("chyx,bhn->byxcn", lw, q).reshape(b, 3, 3, 3, hu, wu)                                     # T[ky][kx][c] per pixel
+    ry = torch.arange(-1, hu + 1, device=dev).abs()
+    ry = torch.where(ry >= hu, 2 * (hu - 1) - ry, ry)                                                              # 'reflect': -1 -> 1, Hu -> Hu - 2
+    rx = torch.arange(-1, wu + 1, device=dev).abs()
+    rx = torch.where(rx >= wu, 2 * (wu - 1) - rx, rx)
+    out = get("last_layer.bias", (1, 3, 1, 1)).expand(b, 3, hu, wu).clone()
+    for ky in range(3):
+        for kx in range(3):
+            out = out + taps[:, ky, kx][:, :, ry[ky:ky + hu]][:, :, :, rx[kx:kx + wu]]
+    return out
+
+
 def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     """((ty0, ty1), (r0, r1)): the HR rows whose tap values mode 4 needs for output rows [y0,y1) (one more row each way,
     clipped to the image) and the LR rows those read (C ABI ``diinn_mode4_rows``)."""
@@ -327,6 +396,75 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
                                  C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()),
                                  b, h, w, hu, wu, y0, y1, int(sin_mode), comp)
     _native.check(st, "diinn_decode_ex")
+    return out
+
+
+def decode_features_initq(feat: torch.Tensor, packed: torch.Tensor, initq: torch.Tensor, size: Sequence[int], mode: int,
+                          head: Optional[torch.Tensor] = None, taps: Optional[torch.Tensor] = None,
+                          pix: Optional[torch.Tensor] = None, rows: Optional[Tuple[int, int]] = None,
+                          out: Optional[torch.Tensor] = None, sin_mode: int = _native.SIN_DEFAULT,
+                          planes_rows: Optional[int] = None) -> torch.Tensor:
+    """``init_q=True`` with decoder modes 1, 2 and 4 (fp32, inference): encoder features ``feat`` [B,64,H,W] -> RGB [B,3,Hu,Wu].
+    (Mode 3 is ``decode_features(..., initq=...)``, which keeps refusing these modes.)
+
+    ``packed`` = ``pack_state_dict(initq_body_state_dict(sd), mode=mode)``, ``initq`` = ``pack_initq(sd)``, ``head`` (mode 4) =
+    ``pack_head3x3(sd)``, all on feat's device.  ``rows=(y0,y1)`` computes only that HR row band, bit-identical to the same rows
+    of a whole-image decode; the rest of ``out`` is left untouched.  ``pix``: the pixel planes, 5,120 bytes per HR pixel of the
+    rows decoded -- for mode 4 of the tap rows [max(0, y0-1), min(Hu, y1+1)) (``diinn_initq_mode4_pix_bytes``), as is ``taps``
+    (``diinn_mode4_taps_bytes``); both allocated if None.  ``planes_rows`` (mode 1): 512 (default; the planes kernel computes the 512
+    GEMM rows mode 1 has, the chain takes its seeds from the biases) or 1280 (mode 2's form on the zero-widened image: the
+    same bits).  Enqueues three kernels on the current stream; never synchronises."""
+    lib = _native.load()
+    if mode not in (1, 2, 4):
+        raise NotImplementedError(f"decode_features_initq covers modes 1, 2 and 4 (mode 3: decode_features(..., initq=...)), got mode {mode}")
+    if planes_rows not in ((None, 512, 1280) if mode == 1 else (None, 1280)):
+        raise ValueError(f"planes_rows={planes_rows}: mode 1 takes 512 or 1280, modes 2 and 4 the 1280-row planes only")
+    _require_cuda(feat, "feat")
+    _require_cuda(packed, "packed weights")
+    _require_cuda(initq, "init_q image")
+    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
+        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
+    hu, wu = size
+    hu, wu = int(hu), int(wu)
+    feat = feat.contiguous()
+    b, _, h, w = feat.shape
+    y0, y1 = (0, hu) if rows is None else (int(rows[0]), int(rows[1]))
+    if mode == 4:
+        if head is None:
+            raise ValueError("mode 4 needs its 3x3 head image: head=pack_head3x3(state_dict) on feat's device")
+        _require_cuda(head, "head image")
+        if hu < 2 or wu < 2:
+            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+    if out is None:
+        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
+    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feat.device:
+        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
+    pneed = lib.diinn_initq_mode4_pix_bytes(b, hu, wu, y0, y1) if mode == 4 else \
+        (lib.diinn_initq_pix_bytes(b, wu, y1 - y0) if 0 <= y0 < y1 <= hu else 0)
+    if pneed == 0:
+        raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
+    if pix is None:
+        pix = torch.empty(pneed // 4, dtype=torch.float32, device=feat.device)
+    elif pix.numel() * pix.element_size() < pneed or pix.dtype != torch.float32 or not pix.is_contiguous() \
+            or pix.device != feat.device:
+        raise ValueError(f"pix must be a contiguous fp32 buffer of >= {pneed} bytes on feat's device")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(feat.device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if mode == 4:
+            tneed = lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1)
+            if taps is None:
+                taps = torch.empty(tneed // 4, dtype=torch.float32, device=feat.device)
+            elif taps.numel() * taps.element_size() < tneed or not taps.is_contiguous() or taps.device != feat.device:
+                raise ValueError(f"taps must be a contiguous buffer of >= {tneed} bytes on feat's device")
+            name = "diinn_decode_initq_mode4"
+            st = lib.diinn_decode_initq_mode4(stream, ptr(feat), ptr(packed), ptr(initq), ptr(head), ptr(pix), ptr(taps), ptr(out),
+                                              b, h, w, hu, wu, y0, y1, int(sin_mode))
+        else:
+            name = "diinn_decode_initq_mode1" if mode == 1 and planes_rows != 1280 else "diinn_decode_initq_mode2"
+            st = getattr(lib, name)(stream, ptr(feat), ptr(packed), ptr(initq), ptr(pix), ptr(out),
+                                    b, h, w, hu, wu, y0, y1, int(sin_mode))
+    _native.check(st, name)
     return out
 
 
@@ -543,7 +681,8 @@ class ImplicitDecoder(nn.Module):
     init_q=False`` (README.md:111-112 of the reference), the ablation modes 1 and 2, whose
     modulation branch depends on the LR cell only, and mode 4, mode 3 with a 3x3 reflect-padded
     head (fp32; inference, and training with ``hip_autograd_mode4``).  ``init_q=True`` (the per-pixel sine embedding ``first_layer``, diinn.py:48-51,113-115) runs
-    for mode 3, inference, fp32; with modes 1, 2, 4 or under autograd ``forward`` raises ``NotImplementedError``.
+    for mode 3, inference, fp32; with modes 1, 2, 4 (unless ``hip_initq_modes`` is set, below) or under autograd ``forward`` raises
+    ``NotImplementedError``.
 
     ``hip_autograd`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, fp32 into
     training: with it set, ``forward(x, size, None)`` under autograd runs ``initq_training.DecodeInitqFunction`` (the HIP kernels
@@ -555,19 +694,27 @@ class ImplicitDecoder(nn.Module):
     training: with it set, ``forward(x, size, None)`` under autograd runs ``mode4_training.DecodeMode4Function`` (mode 3's training
     forward for the saved activations, the 3x3 head from those planes, the backward pass on the HIP kernels; ROCm GPU only, the
     output at least 2 x 2).  With ``bsize`` given the call stays the no_grad inference path.  It changes nothing else:
-    ``hip_autograd`` alone does not open mode 4, and mode 4 with ``init_q=True`` or a bf16 arithmetic keeps refusing."""
+    ``hip_autograd`` alone does not open mode 4, and mode 4 with ``init_q=True`` or a bf16 arithmetic keeps refusing.
+
+    ``hip_initq_modes`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True`` with modes 1, 2 and 4
+    into INFERENCE on the HIP path (fp32; ``decode_features_initq``: the per-pixel modulation chain of modes 1/2, mode 4's tap form
+    on the pixel planes).  With it unset those decoders refuse exactly as before.  With it set they still
+    refuse autograd (``hip_autograd`` / ``hip_autograd_mode4`` do not open it), the bf16 arithmetics, ``DIINN(graphs=True)`` and the
+    sharded forward; it changes nothing for mode 3 or ``init_q=False``."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
+    hip_initq_modes = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
-                 hip_autograd_mode4: bool = False):
+                 hip_autograd_mode4: bool = False, hip_initq_modes: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
         self.hip_autograd = bool(hip_autograd)
         self.hip_autograd_mode4 = bool(hip_autograd_mode4)
+        self.hip_initq_modes = bool(hip_initq_modes)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -637,8 +784,12 @@ class ImplicitDecoder(nn.Module):
         self.packed_weights(device)
         return self._packed_initq
 
+    def _initq_modes(self) -> bool:
+        """``init_q=True`` with mode 1, 2 or 4 and the opt-in set: the paths of ``decode_features_initq``."""
+        return bool(self.init_q and self.hip_initq_modes and self.mode in (1, 2, 4))
+
     def _check_supported(self):
-        if self.mode not in (1, 2, 3, 4) or (self.init_q and self.mode != 3):
+        if self.mode not in (1, 2, 3, 4) or (self.init_q and self.mode != 3 and not self._initq_modes()):
             raise NotImplementedError(
                 f"diinn_amd HIP decode path implements modes 1-4 with init_q=False (mode 3 is the reference's "
                 f"final model) and init_q=True for mode 3, which is covered; got mode={self.mode}, init_q={self.init_q}")
@@ -664,10 +815,20 @@ class ImplicitDecoder(nn.Module):
         HR pixel, so the image is decoded in chunks of ``initq_chunk_rows(B, W_up, INITQ_CHUNK_BYTES)`` HR rows; chunking
         changes no bit of the result either.  ``bsize=30000`` and ``bsize=None`` give the same bits, as in the reference.
         Under autograd with ``bsize=None`` it raises unless ``hip_autograd`` is set (then: ``initq_training.DecodeInitqFunction``,
-        the whole image at once)."""
+        the whole image at once).
+
+        ``init_q=True`` with modes 1, 2, 4 (``hip_initq_modes`` set; fp32, inference only): the same chunks of HR rows; mode 4
+        computes the planes and the taps of a chunk's rows plus one row each way, clipped to the image, and it is those
+        ``initq_chunk_rows`` rows that stay within the cap (a chunk is two output rows shorter).  Chunks change no bit,
+        ``bsize`` is ignored, and mode 4 reproduces ``bsize=None`` as it does without ``init_q``."""
         self._check_supported()
         wants_grad = bsize is None and torch.is_grad_enabled() and (
             x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if wants_grad and self._initq_modes():
+            raise NotImplementedError(
+                f"diinn_amd: init_q=True with mode {self.mode} (ImplicitDecoder.hip_initq_modes) is inference only: autograd "
+                "through it is not covered, and hip_autograd / hip_autograd_mode4 do not open it; call it under "
+                "torch.no_grad() or with bsize given")
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
         initq_grad = self.init_q and self.hip_autograd and self.mode == 3 and self.compute == "f32"     # the opt-in (initq_training.py)
@@ -710,6 +871,27 @@ class ImplicitDecoder(nn.Module):
                 ws = cache[key] = torch.empty(numel, dtype=torch.float32, device=x.device)
             return ws
 
+        if self._initq_modes():
+            hu, wu = size
+            hu, wu = int(hu), int(wu)
+            if self.mode == 4 and (hu < 2 or wu < 2):
+                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+            # mode 4 computes the planes and the taps of one more row each way (clipped to the image): THOSE rows follow the chunk
+            # rule -- within the cap and a whole number of the kernels' 8-row blocks, as MODE4_CHUNK_ROWS = 254 does without
+            # init_q -- so a chunk is two output rows shorter (16 + 2 tap rows would start a third block row of both kernels:
+            # B = 16 of 48 x 48 x4 measured 22.8 ms that way against the eager sequence's 21.4)
+            halo = 2 if self.mode == 4 else 0
+            chunk = initq_chunk_rows(b, wu, self.INITQ_CHUNK_BYTES) - halo
+            pix = cached(self._pix_workspaces, b * min(chunk + halo, hu) * wu * (P_CHANNELS + HIDDEN))
+            taps = cached(self._tap_workspaces, _native.load().diinn_mode4_taps_bytes(b, hu, wu, 1, min(hu, chunk + 1)) // 4) \
+                if self.mode == 4 else None
+            with torch.no_grad():
+                packed = self.packed_weights(x.device)
+                out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
+                for y0 in range(0, hu, chunk):
+                    decode_features_initq(x, packed, self._packed_initq, (hu, wu), self.mode, head=self._packed_head, taps=taps,
+                                          pix=pix, rows=(y0, min(hu, y0 + chunk)), out=out, sin_mode=self.sin_mode)
+                return out
         if self.init_q:
             hu, wu = size
             hu, wu = int(hu), int(wu)

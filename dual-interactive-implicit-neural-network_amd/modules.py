@@ -351,6 +351,9 @@ class DIINN(nn.Module, _GraphReplay):
         if self.decoder.mode == 4:
             raise NotImplementedError("forward_sharded does not cover mode 4 (its 3x3 head reads the neighbouring band's "
                                       "rows); use forward, which decodes mode 4 in row chunks on one GPU")
+        if self.decoder.init_q and self.decoder.mode != 3 and self.decoder.hip_initq_modes:
+            raise NotImplementedError("forward_sharded does not cover init_q=True with modes 1 and 2 (hip_initq_modes: the per-pixel "
+                                      "chain has no band-sized form); use forward, which decodes in row chunks on one GPU")
         if not dist.is_initialized() or dist.get_world_size(group) == 1:
             out = self._forward_eager(x, size, None)
             return out if gather_to is not None else (out, (0, int(size[0])))

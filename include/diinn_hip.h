@@ -325,6 +325,52 @@ int    diinn_decode_initq(void* stream, const float* feat_dev, const float* pack
                           float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                           int sin_mode);
 
+/* ---- decoder init_q=True with modes 1, 2 and 4 (diinn.py:112-147; inference, fp32, every sine_mode) -------------------
+ * The same images as above (body image: diinn_pack_weights of the mode's tensors with a zero Q0 table, mode 1's K.1..3
+ * widened with zero feature columns, mode 4's with a zero 1x1 head; the init_q image; for mode 4 the head image of
+ * diinn_pack_head3x3) and the same PIXEL PLANES record of 1280 floats per HR pixel.
+ *
+ * MODES 1 / 2.  With init_q the modulation chain k_0 = relu(K0 . x' + bK0), k_i = relu(K_i . [k_{i-1}; x'] + bK_i) (mode 1:
+ * K_i . k_{i-1} + bK_i) depends on the HR pixel.  diinn_pixel_chain runs it over the records of one chunk, pix_dev =
+ * [B][rows][Wu][1280]: k_i = relu(K_i[:, :256] . k_{i-1} + seed_i) OVERWRITES channels 256 i .. 256 i + 255, i = 1..3.
+ *   bk_seeds = 0 (mode 2): seed_i = the slot itself, Wx_i . x' + bK_i from diinn_initq_planes.
+ *   bk_seeds = 1 (mode 1): seed_i = bK_i from the body image; the slots are written, never read.  diinn_initq_planes_m1 is
+ *     the planes form that goes with it: it computes channels 0..255 and 1024..1279 only (512 of the 1280 GEMM rows; the
+ *     bits of the same channels of diinn_initq_planes) and leaves channels 256..1023 UNWRITTEN.
+ * diinn_decode_initq_qonly_band: pix_dev of rows [y0,y1) AFTER diinn_pixel_chain -> out_dev[b, :, y0:y1, :] of a contiguous
+ *   [B,3,Hu,Wu] tensor (the layers read k_i as the multiplier of the synthesis branch).
+ * diinn_decode_initq_mode1 / _mode2: planes (_m1 form for mode 1), chain, band decode, in order.  A mode-1 body image through
+ *   diinn_decode_initq_mode2 gives the bits of diinn_decode_initq_mode1 (its Wx_1..3 rows are zero).
+ *
+ * MODE 4.  Mode 3's layers, then the 3x3 reflect-padded head of "decoder mode 4" above: the tap form of the decode kernel reads
+ * the pixel's record and writes the TAP BUFFER of diinn_decode_mode4_band's layout, and the same gather follows.  For output
+ * rows [y0,y1) BOTH pix_dev and taps_dev hold the tap rows [ty0,ty1) = [max(0, y0-1), min(Hu, y1+1)) (diinn_mode4_rows;
+ * diinn_initq_mode4_pix_bytes and diinn_mode4_taps_bytes bytes, 0 for invalid arguments); reflection is applied to image
+ * coordinates, never to band edges.  Needs Hu, Wu >= 2.
+ * diinn_decode_initq_mode4_band: pix_dev = diinn_initq_planes of rows [ty0,ty1) -> out_dev[b, :, y0:y1, :].
+ * diinn_decode_initq_mode4: diinn_initq_planes on [ty0,ty1), then the band decode.
+ *
+ * For every mode a band is BIT-IDENTICAL to the same rows of a whole-image decode.  Every argument is validated before the
+ * first launch (DIINN_ERR_INVALID_ARG / _UNSUPPORTED for a sine mode / _TOO_LARGE); none allocates or synchronises. */
+size_t diinn_initq_mode4_pix_bytes(int B, int Hu, int Wu, int y0, int y1);
+int    diinn_initq_planes_m1(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_pixel_chain(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, int bk_seeds);
+int    diinn_decode_initq_qonly_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                                     int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq_mode1(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                int sin_mode);
+int    diinn_decode_initq_mode2(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                int sin_mode);
+int    diinn_decode_initq_mode4_band(void* stream, const float* pix_dev, const float* packed_dev, const float* head_dev,
+                                     float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                     int sin_mode);
+int    diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                const float* head_dev, float* pix_dev, float* taps_dev, float* out_dev,
+                                int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+
 /* ---- decoder init_q=True, mode 3, under autograd (diinn.py:48-51,113-115,132-139 recorded by autograd; caller
  * SRLitModule.training_step, sr_module.py:127-129).  Tiled planes: see "training" below. ---------------------------
  * TRAINING IMAGE.  diinn_pack_initq_train(Fw [576][3], Fb [576], Q0w [256][576], Q0b [256], K0w [256][576],
