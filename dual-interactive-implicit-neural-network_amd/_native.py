@@ -26,6 +26,7 @@ ABI_VERSION = 11
 PACKED_MAGIC = 0x44493038
 HEAD3X3_MAGIC = 0x44494833             # validity word of the mode-4 head image (diinn_pack_head3x3)
 INITQ_MAGIC = 0x44494951               # validity word of the init_q image (diinn_pack_initq)
+INITQ_X3_MAGIC = 0x44495833            # validity word of the init_q split image (diinn_pack_initq_x3)
 INITQ_TRAIN_MAGIC = 0x44495154         # validity word of the init_q training image (diinn_pack_initq_train)
 PACKED_MAGIC_WPU = 0x44495750          # a training image: permutation sections + section 13 (WPU) filled on the device
 P_ALGO_DIRECT, P_ALGO_WINOGRAD, P_ALGO_DIRECT_BF16, P_ALGO_DIRECT_BF16X3 = 0, 1, 2, 3
@@ -100,6 +101,14 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_decode_initq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_initq_x3_packed_floats": (C.c_size_t, []),
+    "diinn_pack_initq_x3": (C.c_int, [_f, _f, _f]),
+    "diinn_initq_planes_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_decode_initq_band_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_decode_initq_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_initq_mode4_pix_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_initq_planes_m1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -49,8 +49,19 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
     lo = (__bf16)(v - (float)hi);               // exact difference: v and hi share sign and exponent range
 }
 
-template <int SIN_MODE>
+// INITQ (decoder init_q=True, mode 3, behind ImplicitDecoder.hip_initq_split_bf16): `p.P` holds the PIXEL PLANES of
+// initq_planes_x3_kernel (diinn_initq_x3.hip) -- per HR pixel a record of PIX_CH floats, channels 0..1023 what P holds per cell,
+// channels 1024..1279 layer 0's sine argument in revolutions -- so Pc points at the pixel's own record, layer 0 reads its argument
+// there and the Q0 rows of the table are neither loaded nor read; the seeds of layers 1..3 come through the same pointer.  The
+// flag rides in the template argument, SIN_X = sine mode | X3_INITQ, as DECODE_INITQ does in decode_kernel: the instantiations that
+// existed before keep their symbol names and their instructions.  The one-block form only: the persistent form's gain is the next
+// block's layer 0 (table reads and fmas) under the last layer, and with init_q layer 0 is 64 loads and 256 sines.
+constexpr int X3_INITQ = 4;
+template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParams p) {
+    constexpr int SIN_MODE = SIN_X & (X3_INITQ - 1);
+    constexpr bool INITQ = (SIN_X & X3_INITQ) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * X3_INITQ && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ");
     __shared__ __attribute__((aligned(16))) bf16x8 park[4][2][16][64];     // [wave][hi, lo][fragment][lane] = 128 KiB
     __shared__ __attribute__((aligned(16))) float tab[6 * HID + 4];        // Q0h, Q0w (revolutions), t, L[3], bL | validity
     const int lane = threadIdx.x & 63;
@@ -60,14 +71,18 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     {   // the tables every pixel shares (as decode_kernel): t = fma(Q0r, ratio, bQ0) once per workgroup
         const float* __restrict__ Q0s = Wt + OFF_Q0R + 4 * lane;
         if (wave == 0) {
-            *(f32x4*)(tab + 0 * HID + 4 * lane) = *(const f32x4*)(Q0s + 0 * HID);
-            *(f32x4*)(tab + 1 * HID + 4 * lane) = *(const f32x4*)(Q0s + 1 * HID);
+            if constexpr (!INITQ) {
+                *(f32x4*)(tab + 0 * HID + 4 * lane) = *(const f32x4*)(Q0s + 0 * HID);
+                *(f32x4*)(tab + 1 * HID + 4 * lane) = *(const f32x4*)(Q0s + 1 * HID);
+            }
         } else if (wave == 1) {
-            const f32x4 wr = *(const f32x4*)(Q0s + 2 * HID), bq = *(const f32x4*)(Q0s + 3 * HID);
-            f32x4 t;
+            if constexpr (!INITQ) {
+                const f32x4 wr = *(const f32x4*)(Q0s + 2 * HID), bq = *(const f32x4*)(Q0s + 3 * HID);
+                f32x4 t;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
-            *(f32x4*)(tab + 2 * HID + 4 * lane) = t;
+                for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
+                *(f32x4*)(tab + 2 * HID + 4 * lane) = t;
+            }
         } else if (wave == 2) {
             *(f32x4*)(tab + 3 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 0 * HID + 4 * lane);
             *(f32x4*)(tab + 4 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 1 * HID + 4 * lane);
@@ -91,7 +106,8 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     float relh, relw;
     axis_eval(p.ah, yc, iy, relh);
     axis_eval(p.aw, xc, ix, relw);
-    const float* __restrict__ Pc = p.P + (((size_t)b * p.Prows + (iy - p.Prow0)) * p.W + ix) * PCH + 4 * h;
+    const float* __restrict__ Pc = INITQ ? p.P + (((size_t)b * p.Prows + (yc - p.Prow0)) * p.Wu + xc) * PIX_CH + 4 * h
+                                         : p.P + (((size_t)b * p.Prows + (iy - p.Prow0)) * p.W + ix) * PCH + 4 * h;
 
     // ---- layer 0 (fp32), split into hi/lo fragments: register r = 4g+e of tile m -> q[2m + (r>>3)][r&7]
     bf16x8 qh[16], ql[16];
@@ -103,13 +119,21 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
             for (int g = 0; g < 4; ++g) {
                 const int c0 = 32 * m + 8 * g;
                 const f32x4 pv = *(const f32x4*)(Pc + c0);
-                const f32x4 wh = *(const f32x4*)(Q0 + 0 * HID + c0);
-                const f32x4 ww = *(const f32x4*)(Q0 + 1 * HID + c0);
-                const f32x4 tq = *(const f32x4*)(Q0 + 2 * HID + c0);
+                f32x4 wh, ww, tq;
+                if constexpr (INITQ) {
+                    tq = *(const f32x4*)(Pc + PCH + c0);         // the pixel's own sine argument
+                } else {
+                    wh = *(const f32x4*)(Q0 + 0 * HID + c0);
+                    ww = *(const f32x4*)(Q0 + 1 * HID + c0);
+                    tq = *(const f32x4*)(Q0 + 2 * HID + c0);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float a = __builtin_fmaf(ww[e], relw, tq[e]);
-                    a = __builtin_fmaf(wh[e], relh, a);
+                    float a = tq[e];
+                    if constexpr (!INITQ) {
+                        a = __builtin_fmaf(ww[e], relw, tq[e]);
+                        a = __builtin_fmaf(wh[e], relh, a);
+                    }
                     __bf16 vh, vl;
                     split_bf16(relu0(pv[e]) * dsin_rev<SIN_MODE>(a), vh, vl);
                     qh[2 * m + (g >> 1)][4 * (g & 1) + e] = vh;
@@ -658,5 +682,17 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+// init_q (mode 3): `p.P` = the pixel planes of HR rows [p.y0, p.y1) (p.Prow0 = p.y0); the one-block form (see X3_INITQ)
+int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
+    const dim3 grid(gx, gy, gz);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }

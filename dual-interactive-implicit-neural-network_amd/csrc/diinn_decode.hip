@@ -995,7 +995,8 @@ int launch_head3x3_whole(void* stream, const float* taps_dev, const float* head_
 // init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
 // The throughput kernel only (no 16-pixel latency twin).  kpart = false: modes 1/2, the planes hold the per-pixel chain (diinn_pixel_chain).
 static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
-                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool kpart = true) {
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool kpart = true,
+                                  bool x3 = false) {
     if (!pix_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -1020,6 +1021,7 @@ static int decode_initq_band_impl(void* stream, const float* pix_dev, const floa
     const int small = diinn_uses_small_output_kernel(Hu, Wu);
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
+    if (x3) return launch_decode_bf16x3_initq(stream, p, gx, gy, B, sin_mode);   // split bf16: decode_bf16x3_kernel<SIN | X3_INITQ>
     const dim3 grid(gx, gy, B);
     if (!kpart) {
         if (sin_mode == DIINN_SIN_HW)
@@ -1157,6 +1159,21 @@ int diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float* p
 int diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
                             int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
     return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
+
+// init_q (mode 3) in split-bf16 arithmetic: initq_planes_x3_kernel, decode_bf16x3_kernel<SIN | X3_INITQ>
+int diinn_decode_initq_band_x3(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                               int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, true, true);
+}
+
+int diinn_decode_initq_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                          const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                          int y0, int y1, int sin_mode) {
+    if (!out_dev) return DIINN_ERR_INVALID_ARG;
+    const int st = diinn_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, true, true);
 }
 
 int diinn_decode_initq(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,

@@ -6,6 +6,7 @@
 //   diinn_decode.hip           decode_kernel (+ modes 1/2 chain, training forward, mode 4's tap form), decode_coop16_kernel (latency
 //                              form), head3x3_reflect_kernel (mode 4's 9-point gather) and the decode entry points of the C ABI
 //   diinn_initq.hip            initq_planes_kernel (decoder init_q=True: the per-pixel sine embedding and its two per-pixel GEMMs; decode_kernel<SIN | DECODE_INITQ> reads its planes)
+//   diinn_initq_x3.hip         initq_planes_x3_kernel (the same planes in split-bf16 arithmetic; decode_bf16x3_kernel<SIN | X3_INITQ> reads them)
 //   diinn_precompute.hip       precompute_P_kernel (direct fp32), precompute_P_bf16_kernel / _bf16_wide_kernel, launch_P
 //   diinn_precompute_wino.hip  precompute_P_wino_kernel (the fp32 hoisted conv in Winograd F(2x2,3x3) form: inference)
 //   diinn_precompute_x3.hip    precompute_P_x3_kernel (the hoisted conv in split-bf16 arithmetic: DIINN_COMPUTE_BF16X3, large maps)
@@ -375,3 +376,11 @@ int diinn_conv1x1_x3_split(void* stream, float* xs_dev, long long xs_bs16, int C
 // diinn_bf16.hip: the split-bf16 decode (DIINN_COMPUTE_BF16X3) of HR rows [p.y0, p.y1)
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+// diinn_bf16x3.hip: the same arithmetic from the pixel planes of init_q (decode_bf16x3_kernel<SIN | X3_INITQ>)
+__attribute__((visibility("hidden")))
+int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+// diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1)
+__attribute__((visibility("hidden")))
+int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                           const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                           int sin_mode);

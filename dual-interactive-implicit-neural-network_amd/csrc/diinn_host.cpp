@@ -475,6 +475,36 @@ int diinn_pack_initq(const float* Fw, const float* Fb, const float* Q0w, const f
     return DIINN_OK;
 }
 
+// ---- decoder init_q=True in split-bf16 arithmetic: the Q.0 split image (diinn_layout.h "the init_q SPLIT image") -----------
+size_t diinn_initq_x3_packed_floats(void) { return IQX_FLOATS; }
+
+int diinn_pack_initq_x3(const float* Q0w, const float* Q0b, float* packed) {
+    if (!Q0w || !Q0b || !packed) return DIINN_ERR_INVALID_ARG;
+    uint16_t* q0x = reinterpret_cast<uint16_t*>(packed + IQX_OFF_Q0X);
+    for (int og = 0; og < 4; ++og)                              // Q0w is [256][576]: WPX's piece order
+        for (int g = 0; g < 4; ++g)
+            for (int tap = 0; tap < 9; ++tap)
+                for (int mt = 0; mt < 2; ++mt) {
+                    uint16_t* dhi = q0x + (((((size_t)og * 4 + g) * 9 + tap) * 2 + mt) * 2 + 0) * (64 * 8);
+                    uint16_t* dlo = dhi + 64 * 8;
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int o = 64 * og + 32 * mt + (lane & 31);
+                        for (int j = 0; j < 8; ++j) {
+                            const int c = 16 * g + 8 * (lane >> 5) + j;
+                            const float v = Q0w[(size_t)o * UNF + (size_t)c * 9 + tap] * INV_2PI;
+                            const uint16_t hi = f32_to_bf16(v);
+                            dhi[lane * 8 + j] = hi;
+                            dlo[lane * 8 + j] = f32_to_bf16(v - bf16_to_f32(hi));   // exact difference, then one rounding
+                        }
+                    }
+                }
+    for (int ch = 0; ch < HID; ++ch) packed[IQX_OFF_BQ0 + ch] = Q0b[ch] * INV_2PI;
+    const uint32_t magic = DIINN_INITQ_X3_MAGIC;
+    std::memcpy(packed + IQX_OFF_BQ0 + HID, &magic, 4);
+    for (int i = 1; i < 4; ++i) packed[IQX_OFF_BQ0 + HID + i] = 0.0f;
+    return DIINN_OK;
+}
+
 // ---- decoder init_q=True under autograd: the training image (diinn_layout.h "the init_q TRAINING image") -----------
 size_t diinn_initq_train_packed_floats(void) { return IQT_FLOATS; }
 

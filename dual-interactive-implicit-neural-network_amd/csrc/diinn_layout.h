@@ -142,6 +142,20 @@ constexpr size_t IQ_SZ_Q0W    = (size_t)8 * WP_KG * WL_PIECE;   // 147,456 float
 constexpr size_t IQ_OFF_BQ0   = IQ_OFF_Q0W + IQ_SZ_Q0W;         // 149,760
 constexpr size_t IQ_FLOATS    = IQ_OFF_BQ0 + HID + 4;           // 150,020 (validity word at IQ_OFF_BQ0 + HID)
 
+// ---- decoder init_q=True, mode 3, in split-bf16 arithmetic: the init_q SPLIT image (diinn_pack_initq_x3) ----
+// A third small image beside the body image and the init_q image, for the Q0 GEMM of initq_planes_x3_kernel (which takes F from the
+// init_q image, and Wx from section WPX of the body image):
+//   Q0X [og 4][group 4][tap 9][M-tile 2][hi, lo][lane 64][j 8] bf16   A operands of v_mfma_f32_32x32x16_bf16 in WPX's k order (one B
+//       operand serves Wx and Q0): k-step (group, tap), output channel o = 64 og + 32 mt + (lane&31) of the 256, unfolded input
+//       n = c*9 + tap with c = 16 group + 8 (lane>>5) + j;  v = fp32(Q0w[o][n] * fp32(1/(2 pi))), hi = bf16(v), lo = bf16(v - hi)
+//       (round to nearest even; the division happens in fp32 BEFORE the split, like sections WLX / BQR of the body image).
+//       A piece [lane 64][j 8] is 1 KiB; the four pieces of a (og, group, tap) -- mt0 hi, mt0 lo, mt1 hi, mt1 lo -- are contiguous.
+//   BQ0 [256]  Q0b / (2 pi), natural order, then the image's own validity word DIINN_INITQ_X3_MAGIC and three zero floats.
+constexpr size_t IQX_OFF_Q0X  = 0;
+constexpr size_t IQX_SZ_Q0X   = (size_t)4 * 4 * 9 * 2 * 2 * WLB_PIECE;   // 147,456 floats = 576 KiB
+constexpr size_t IQX_OFF_BQ0  = IQX_OFF_Q0X + IQX_SZ_Q0X;
+constexpr size_t IQX_FLOATS   = IQX_OFF_BQ0 + HID + 4;          // 147,716 (validity word at IQX_OFF_BQ0 + HID)
+
 // ---- decoder init_q=True, mode 3, under autograd: the init_q TRAINING image (diinn_pack_initq_train) ----
 // A pure permutation of the reference tensors (plus zero padding and a validity word), so the device re-pack of an optimiser step is
 // one gather.  It starts with the init_q image's own layout -- F, Q0W, BQ0 at IQ_OFF_* -- in RADIANS (nothing divided by 2 pi: the

@@ -17,6 +17,7 @@ backward is library GEMMs over those (training.py).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -116,6 +117,21 @@ def pack_initq(sd, prefix: str = "") -> torch.Tensor:
     return torch.from_numpy(packed)
 
 
+INV_2PI_F32 = float(np.float32(0.15915494309189533577))     # fp32(1 / (2 pi)): the factor the host packers multiply by
+
+
+def pack_initq_x3(sd, prefix: str = "") -> torch.Tensor:
+    """``init_q=True`` in split-bf16 arithmetic: ``Q.0.0.weight`` [256,576,1,1] and ``Q.0.0.bias`` [256] -> the init_q SPLIT image
+    (1-D fp32 CPU tensor; C ABI ``diinn_pack_initq_x3``: Q.0 / (2 pi) as hi / lo bf16 A operands in the piece order of the body
+    image's section WPX, its bias / (2 pi), a validity word).  The third image of such a decode, beside ``pack_state_dict`` of
+    ``initq_body_state_dict`` and ``pack_initq``."""
+    lib = _native.load()
+    q0w, q0b = _host_array(sd, prefix, "Q.0.0.weight", (HIDDEN, 576)), _host_array(sd, prefix, "Q.0.0.bias", (HIDDEN,))
+    packed = np.empty(lib.diinn_initq_x3_packed_floats(), dtype=np.float32)
+    _native.check(lib.diinn_pack_initq_x3(_native.fptr(q0w), _native.fptr(q0b), _native.fptr(packed)), "diinn_pack_initq_x3")
+    return torch.from_numpy(packed)
+
+
 def initq_body_state_dict(sd, prefix: str = ""):
     """The tensors ``pack_state_dict(..., mode=3)`` takes for an ``init_q=True`` decoder: the same dict with a zero [256,3]
     in place of the 576-wide ``Q.0.0.weight`` (the init_q kernels never read the body image's Q0 rows)."""
@@ -131,7 +147,102 @@ def initq_chunk_rows(b: int, wu: int, cap_bytes: int) -> int:
     return max(8, (int(cap_bytes) // per_row) // 8 * 8)
 
 
-def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "", planes: Optional[list] = None) -> torch.Tensor:
+def _split_bf16(v: torch.Tensor):
+    """hi = bf16(v), lo = bf16(v - hi) (round to nearest even), both back in v's dtype."""
+    hi = v.to(torch.bfloat16).to(v.dtype)
+    return hi, (v - hi).to(torch.bfloat16).to(v.dtype)
+
+
+def _mm_split(w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The split-bf16 product of DESIGN.md 3.5: (w_lo . x_hi + w_hi . x_lo) + w_hi . x_hi, accumulated in the operands' dtype."""
+    wh, wl = _split_bf16(w)
+    xh, xl = _split_bf16(x)
+    return (wl @ xh + wh @ xl) + wh @ xh
+
+
+def _sin_rev(a: torch.Tensor) -> torch.Tensor:
+    """sin of an argument in revolutions, taken in float64 and rounded to the argument's dtype."""
+    return torch.sin(a.double() * (2.0 * math.pi)).to(a.dtype)
+
+
+def initq_planes_reference(sd, feat, size, arith: str = "split", prefix: str = "") -> torch.Tensor:
+    """The pixel planes of the split-bf16 ``init_q`` path, [B, Hu*Wu, 1280] (channels 1024.. in REVOLUTIONS), as
+    ``initq_planes_x3_kernel`` forms them: everything that feeds a sine divided by fp32(1/(2 pi)) in fp32, ``E`` by the kernel's
+    fp32 fma sequence (ratio, rel_w, rel_h) with the sine taken in float64, ``x' = E * X`` in fp32.  ``arith`` = "split": both GEMMs
+    as ``_mm_split`` in fp32 (torch matmuls, not the MFMA's summation order); "f64": the float64 products of the same fp32
+    operands, the yardstick of the planes test."""
+    if arith not in ("split", "f64"):
+        raise ValueError(f"arith must be 'split' or 'f64', got {arith!r}")
+    f32 = torch.float32
+    dev = feat.device
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
+        return t.to(device=dev, dtype=f32).reshape(shape)
+
+    inv = torch.tensor(INV_2PI_F32, dtype=f32, device=dev)
+    hu, wu = int(size[0]), int(size[1])
+    x = feat.to(f32)
+    b, c, h, w = x.shape
+    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
+    iy, rel_h = axis_tables(h, hu, small)
+    ix, rel_w = axis_tables(w, wu, small)
+    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
+    n = hu * wu
+    relh = torch.from_numpy(rel_h).to(dev, f32)[:, None].expand(hu, wu).reshape(1, n)
+    relw = torch.from_numpy(rel_w).to(dev, f32)[None, :].expand(hu, wu).reshape(1, n)
+    ratio = torch.tensor(np.float32((h * w) / (hu * wu)), dtype=f32, device=dev)
+    fw, fb = get("first_layer.0.weight", (576, 3)) * inv, get("first_layer.0.bias", (576, 1)) * inv
+
+    def fma(a_, b_, c_):                                      # one rounding: the fp32 product is exact in float64
+        return (a_.double() * b_.double() + c_.double()).to(f32)
+
+    a = fma(fw[:, 2:3], ratio, fb)
+    a = fma(fw[:, 1:2], relw, a)
+    a = fma(fw[:, 0:1], relh, a)
+    e = _sin_rev(a)                                           # [576, n]
+    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
+    xc = unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)
+    xp = e[None] * xc                                         # [b, 576, n], fp32
+    wx = torch.cat([get("K.0.0.weight", (HIDDEN, 576))] +
+                   [get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, HIDDEN:] for i in (1, 2, 3)], 0)
+    bk = torch.cat([get(f"K.{i}.0.bias", (HIDDEN,)) for i in range(4)])[None, :, None]
+    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 576)) * inv, get("Q.0.0.bias", (HIDDEN, 1)) * inv
+    if arith == "f64":
+        pk = wx.double() @ xp.double() + bk.double()
+        a0 = q0w.double() @ e.double() + q0b.double()
+    else:
+        pk = _mm_split(wx, xp) + bk
+        a0 = _mm_split(q0w, e) + q0b
+    return torch.cat([pk, a0[None].expand(b, HIDDEN, n)], 1).transpose(1, 2).contiguous()
+
+
+def _initq_forward_split(sd, feat, size, dtype, prefix: str) -> torch.Tensor:
+    """``initq_forward_reference(..., split_bf16=True)``: the three split stages -- both planes GEMMs (``initq_planes_reference``),
+    and the two 256 x 256 products of layers 1..3 -- with every sine taken of revolutions in float64."""
+    dev = feat.device
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
+        return t.to(device=dev, dtype=torch.float32).reshape(shape)
+
+    inv = torch.tensor(INV_2PI_F32, dtype=torch.float32, device=dev)
+    hu, wu = int(size[0]), int(size[1])
+    pix = initq_planes_reference(sd, feat, size, "split", prefix).transpose(1, 2)      # [b, 1280, n]
+    b = pix.shape[0]
+    q = torch.relu(pix[:, :HIDDEN]) * _sin_rev(pix[:, P_CHANNELS:])
+    for i in (1, 2, 3):
+        k = torch.relu(_mm_split(get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, :HIDDEN], q) + pix[:, HIDDEN * i:HIDDEN * (i + 1)])
+        s = _mm_split(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) * inv, q) + get(f"Q.{i}.0.bias", (HIDDEN, 1)) * inv
+        q = k * _sin_rev(s)
+    out = get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))
+    return out.reshape(b, 3, hu, wu).to(dtype)
+
+
+def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "", planes: Optional[list] = None,
+                            split_bf16: bool = False) -> torch.Tensor:
     """The formula sheet of the ``init_q=True``, mode-3 path in tensor algebra, in the RESTRUCTURED form the kernels run
     (any device, any float dtype; the tests' one restatement, as ``encoder_training.rdb_backward_reference`` is for its path).
 
@@ -147,7 +258,16 @@ def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "
     there: ``k_i = relu(K_i[:, :256] . q_{i-1} + PIX[256 i : 256 i + 256])`` (``decode_kernel<SIN | DECODE_INITQ>``).  E depends on the
     pixel only, not on the batch item.  Coordinates: the fp32 tables of ``axis_tables`` (the reference computes them in fp32
     whatever the module's dtype); ``ratio`` is the Python double rounded to ``dtype``, as ``x.new_tensor`` does.
-    ``planes`` (a list): receives every layer's (k_i, s_i), each [B,256,Hu*Wu] -- what the training forward saves."""
+    ``planes`` (a list): receives every layer's (k_i, s_i), each [B,256,Hu*Wu] -- what the training forward saves.
+    ``split_bf16`` (with ``dtype=torch.float32``): the EMULATION of the split-bf16 path (``hip_initq_split_bf16``) -- the two planes
+    GEMMs, the ``Q0 . E`` sine argument and layers 1..3 with every operand carried as hi + lo bf16 and a product formed as
+    ``(w_lo.x_hi + w_hi.x_lo) + w_hi.x_hi`` in fp32 torch matmuls; sine arguments in revolutions (weights and biases divided by
+    fp32(1/(2 pi)) in fp32 before the split, as the images hold them), the sines taken in float64."""
+    if split_bf16:
+        if dtype != torch.float32 or planes is not None:
+            raise ValueError("split_bf16=True emulates fp32 accumulation: dtype=torch.float32, and no planes")
+        return _initq_forward_split(sd, feat, size, dtype, prefix)
+
     def get(name, shape):
         t = sd[prefix + name]
         t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
@@ -302,7 +422,7 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
                     rows: Optional[Tuple[int, int]] = None, sin_mode: int = _native.SIN_DEFAULT,
                     compute: str = "f32", mode: int = 3, head: Optional[torch.Tensor] = None,
                     taps: Optional[torch.Tensor] = None, initq: Optional[torch.Tensor] = None,
-                    pix: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    pix: Optional[torch.Tensor] = None, initq_x3: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode encoder features ``feat`` [B,64,H,W] to RGB [B,3,Hu,Wu].
 
     ``rows=(y0,y1)`` computes only that HR row band (tile sharding across GPUs);
@@ -317,15 +437,21 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
     ``initq`` (mode 3, fp32 only): the init_q image (``pack_initq``) of an ``init_q=True`` decoder, with ``packed`` the body image
     of ``initq_body_state_dict``; ``pix`` is its workspace, the pixel planes of the rows decoded (``diinn_initq_pix_bytes``,
     5,120 bytes per HR pixel; allocated if None; ``workspace`` is not used).  A row band is bit-identical to the same rows of a
-    whole-image decode.
+    whole-image decode.  ``initq_x3`` (with ``initq``, mode 3, ``compute="bf16x3"`` only): the init_q split image (``pack_initq_x3``)
+    opens the split-bf16 arithmetic for such a decoder (``initq_planes_x3_kernel``, ``decode_bf16x3_kernel<SIN | X3_INITQ>``; the
+    same ``pix``); without it ``compute="bf16x3"`` refuses like the other bf16 arithmetics.
     Enqueues two kernels (three for modes 1/2: + the per-cell modulation chain; three for mode 4: + the 9-point
     gather) on the current stream; never synchronises."""
     lib = _native.load()
     if initq is not None:
         if mode != 3:
             raise NotImplementedError(f"init_q=True is covered for mode 3 only (got mode {mode})")
-        if compute != "f32":
+        if compute != "f32" and not (compute == "bf16x3" and initq_x3 is not None):
             raise ValueError("init_q=True runs in fp32 only")
+        if compute == "f32" and initq_x3 is not None:
+            raise ValueError("initq_x3 is the image of compute='bf16x3'")
+    elif initq_x3 is not None:
+        raise ValueError("initq_x3 goes with initq (an init_q=True decoder)")
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
     if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
@@ -351,6 +477,16 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
         elif pix.numel() * pix.element_size() < pneed or pix.dtype != torch.float32 or not pix.is_contiguous() \
                 or pix.device != feat.device:
             raise ValueError(f"pix must be a contiguous fp32 buffer of >= {pneed} bytes on feat's device")
+        if initq_x3 is not None:
+            _require_cuda(initq_x3, "init_q split image")
+            with torch.cuda.device(feat.device):
+                stream = torch.cuda.current_stream().cuda_stream
+                st = lib.diinn_decode_initq_x3(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                               C.c_void_p(initq.data_ptr()), C.c_void_p(initq_x3.data_ptr()),
+                                               C.c_void_p(pix.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               b, h, w, hu, wu, y0, y1, int(sin_mode))
+            _native.check(st, "diinn_decode_initq_x3")
+            return out
         with torch.cuda.device(feat.device):
             stream = torch.cuda.current_stream().cuda_stream
             st = lib.diinn_decode_initq(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
@@ -700,21 +836,30 @@ class ImplicitDecoder(nn.Module):
     into INFERENCE on the HIP path (fp32; ``decode_features_initq``: the per-pixel modulation chain of modes 1/2, mode 4's tap form
     on the pixel planes).  With it unset those decoders refuse exactly as before.  With it set they still
     refuse autograd (``hip_autograd`` / ``hip_autograd_mode4`` do not open it), the bf16 arithmetics, ``DIINN(graphs=True)`` and the
-    sharded forward; it changes nothing for mode 3 or ``init_q=False``."""
+    sharded forward; it changes nothing for mode 3 or ``init_q=False``.
+
+    ``hip_initq_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, INFERENCE
+    into ``compute="bf16x3"``, the split-bf16 arithmetic (``initq_planes_x3_kernel`` and the init_q form of ``decode_bf16x3_kernel``;
+    DESIGN.md 3.6d).  With it unset every ``compute`` other than ``"f32"`` refuses as before.  With it set only ``"bf16x3"`` opens:
+    ``"bf16"`` / ``"bf16_full"``, autograd, ``init_q`` with modes 1/2/4, ``DIINN(graphs=True)`` and the sharded forward keep
+    refusing with their messages, and ``compute="f32"`` gives the fp32 bits.  ``DIINN.set_split_bf16()`` does not set it: on an
+    ``init_q`` model the user sets both."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
     hip_initq_modes = False
+    hip_initq_split_bf16 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
-                 hip_autograd_mode4: bool = False, hip_initq_modes: bool = False):
+                 hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
         self.hip_autograd = bool(hip_autograd)
         self.hip_autograd_mode4 = bool(hip_autograd_mode4)
         self.hip_initq_modes = bool(hip_initq_modes)
+        self.hip_initq_split_bf16 = bool(hip_initq_split_bf16)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -745,6 +890,7 @@ class ImplicitDecoder(nn.Module):
         self._tap_workspaces: "Dict[tuple, torch.Tensor]" = {}
         # init_q (mode 3): the first-layer / Q.0 image (cached with the body image) and the pixel-plane workspaces
         self._packed_initq: Optional[torch.Tensor] = None
+        self._packed_initq_x3: Optional[torch.Tensor] = None     # the split image (bf16x3), packed and cached with them
         self._pix_workspaces: "Dict[tuple, torch.Tensor]" = {}
 
     _MAX_WORKSPACES = 4
@@ -767,6 +913,7 @@ class ImplicitDecoder(nn.Module):
             self._packed = pack_state_dict(initq_body_state_dict(sd) if self.init_q else sd, mode=self.mode).to(device)
             self._packed_head = pack_head3x3(sd).to(device) if self.mode == 4 else None
             self._packed_initq = pack_initq(sd).to(device) if self.init_q else None
+            self._packed_initq_x3 = pack_initq_x3(sd).to(device) if self.init_q else None
             self._packed_key = key
         return self._packed
 
@@ -783,6 +930,13 @@ class ImplicitDecoder(nn.Module):
             raise ValueError("only init_q=True has an init_q image")
         self.packed_weights(device)
         return self._packed_initq
+
+    def packed_initq_x3(self, device) -> torch.Tensor:
+        """``init_q=True``: the init_q split image on ``device`` (packed and cached together with the body image)."""
+        if not self.init_q:
+            raise ValueError("only init_q=True has an init_q split image")
+        self.packed_weights(device)
+        return self._packed_initq_x3
 
     def _initq_modes(self) -> bool:
         """``init_q=True`` with mode 1, 2 or 4 and the opt-in set: the paths of ``decode_features_initq``."""
@@ -840,7 +994,8 @@ class ImplicitDecoder(nn.Module):
                 "torch.no_grad() (mode 4 in fp32 with init_q=False trains once ImplicitDecoder.hip_autograd_mode4 is set)")
         if wants_grad and mode4_grad and (int(size[0]) < 2 or int(size[1]) < 2):
             raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {int(size[0])} x {int(size[1])}")
-        if self.init_q and self.compute != "f32":
+        initq_x3 = bool(self.init_q and self.mode == 3 and self.hip_initq_split_bf16 and self.compute == "bf16x3")   # the opt-in
+        if self.init_q and self.compute != "f32" and not initq_x3:
             raise ValueError("init_q=True runs in fp32 only")
         _require_cuda(x, "x")
         if wants_grad:
@@ -902,7 +1057,8 @@ class ImplicitDecoder(nn.Module):
                 out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
                 for y0 in range(0, hu, chunk):
                     decode_features(x, packed, (hu, wu), out=out, rows=(y0, min(hu, y0 + chunk)), sin_mode=self.sin_mode,
-                                    initq=self._packed_initq, pix=pix)
+                                    initq=self._packed_initq, pix=pix, compute="bf16x3" if initq_x3 else "f32",
+                                    initq_x3=self._packed_initq_x3 if initq_x3 else None)
                 return out
         workspace = cached(self._workspaces, need)
         with torch.no_grad():

@@ -325,6 +325,34 @@ int    diinn_decode_initq(void* stream, const float* feat_dev, const float* pack
                           float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                           int sin_mode);
 
+/* ---- decoder init_q=True, mode 3, in split-bf16 arithmetic (inference, every sine_mode) -------------------------------
+ * The same network and the same PIXEL PLANES record (fp32, 1280 floats per HR pixel, diinn_initq_pix_bytes), with both
+ * per-pixel GEMMs and the layers 1..3 in the arithmetic of DIINN_COMPUTE_BF16X3: every operand v carried as hi = bf16(v),
+ * lo = bf16(v - hi), a product formed as w_lo.x_hi + w_hi.x_lo + w_hi.x_hi on the bf16 MFMA with fp32 accumulation.  E, the
+ * product x' = E * X, biases, sines and the head stay fp32.
+ *
+ * IMAGES.  The body image and the init_q image as above (the body image's derived sections WPX / WLX / BQR are read, F from
+ * the init_q image), and a third, diinn_pack_initq_x3(Q0w [256][576], Q0b [256]) of diinn_initq_x3_packed_floats() floats:
+ *     [og 4][group 4][tap 9][M-tile 2][hi, lo][lane 64][j 8] bf16   v = fp32(Q0w[ 64 og + 32 mt + (lane & 31) ][ c * 9 + tap ]
+ *                * fp32(1/(2 pi))), c = 16 group + 8 (lane >> 5) + j; hi = bf16(v), lo = bf16(v - hi)   (section WPX's order)
+ *     [256]      Q0b / (2 pi),  then the image's validity word DIINN_INITQ_X3_MAGIC (without it every output is NaN).
+ *
+ * diinn_initq_planes_x3:      feat_dev [B,64,H,W] -> pix_dev for rows [y0,y1).
+ * diinn_decode_initq_band_x3: pix_dev of rows [y0,y1) -> out_dev[b, :, y0:y1, :] of a contiguous [B,3,Hu,Wu] tensor.
+ * diinn_decode_initq_x3:      both in order; diinn_decode_initq's argument conventions.  Bands are BIT-IDENTICAL to the same
+ *   rows of a whole-image decode. */
+#define DIINN_INITQ_X3_MAGIC 0x44495833u   /* "DIX3" */
+size_t diinn_initq_x3_packed_floats(void);
+int    diinn_pack_initq_x3(const float* Q0w, const float* Q0b, float* packed);
+int    diinn_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                             int sin_mode);
+int    diinn_decode_initq_band_x3(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                             const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                             int y0, int y1, int sin_mode);
+
 /* ---- decoder init_q=True with modes 1, 2 and 4 (diinn.py:112-147; inference, fp32, every sine_mode) -------------------
  * The same images as above (body image: diinn_pack_weights of the mode's tensors with a zero Q0 table, mode 1's K.1..3
  * widened with zero feature columns, mode 4's with a zero 1x1 head; the init_q image; for mode 4 the head image of
