@@ -51,10 +51,11 @@ struct TagCoopT { static constexpr bool value = true; };
 // INITQ rides in the first template argument, SIN_X = sine mode | DECODE_INITQ: the kernel keeps its four parameters, so every
 // instantiation that existed before keeps its symbol name (and its instructions); the new ones are decode_kernel<SIN | DECODE_INITQ>.
 //
-// init_q with the other modes (inference only):
+// init_q with the other modes:
 //   * modes 1/2, decode_kernel<SIN | DECODE_INITQ, KPART = false>: pixel_chain_kernel has written k_1..3 over channels 256..1023 of
-//     the pixel's record, which the layers read as the multiplier exactly as they read the per-cell chain in P otherwise;
-//   * mode 4, decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS>: the tap form (HEAD3) reading the pixel's own record.  The tap form of
+//     the pixel's record, which the layers read as the multiplier exactly as they read the per-cell chain in P otherwise; with SAVE
+//     (the training forward, diinn_decode_initq_train_fwd_qonly) it saves those k_i and the sine arguments in radians;
+//   * mode 4, decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS> (inference only): the tap form (HEAD3) reading the pixel's own record.  The tap form of
 //     init_q rides in SIN_X too, NOT in the fourth template argument: the three decode_kernel<SIN, true, false, true> symbols stay
 //     the only ones of that spelling (what picks mode 4's tap kernels out of the library by name keeps finding exactly those).
 constexpr int DECODE_INITQ = 4;
@@ -67,8 +68,9 @@ __global__ __launch_bounds__(256, 1) void decode_kernel(const DecodeParams p) {
     static_assert(SIN_X >= 0 && SIN_X < 2 * DECODE_TAPS && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | DECODE_INITQ | DECODE_TAPS");
     static_assert(!(SIN_X & DECODE_TAPS) || (INITQ && !HEAD3_ARG), "DECODE_TAPS: the tap form of init_q only");
     static_assert(!(HEAD3 && SAVE), "mode 4 is inference only");
-    // init_q: mode 3 (with SAVE: the planes are in radians, INITQ_RAD of initq_planes_kernel); modes 1/2 and mode 4, inference only
-    static_assert(!INITQ || (KPART && !HEAD3) || (!SAVE && KPART == HEAD3), "init_q: mode 3, or modes 1/2 / mode 4 without SAVE");
+    // init_q: mode 3 and modes 1/2 (with SAVE: the planes are in radians, INITQ_RAD of initq_planes_kernel; modes 1/2 save the k_i
+    // pixel_chain_kernel left in the record); mode 4's tap form is inference only (its training forward is mode 3's with SAVE)
+    static_assert(!INITQ || !HEAD3 || (!SAVE && KPART), "init_q: modes 1-3, or mode 4's tap form without SAVE");
     // The small tables of layer 0 and of the head go through LDS: a vector-memory instruction blocks its wave for
     // ~60 cycles (stamps), and a wave reading them straight from the packed image issued 128 + 96
     // of those per tile.  Rows: Q0h, Q0w, t = fma(Q0r, ratio, bQ0) (the pixel-independent part of the sine
@@ -1318,8 +1320,11 @@ int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed
 
 // init_q (mode 3) under autograd: the pixel planes of the WHOLE image in radians (initq_planes_kernel<SIN | INITQ_RAD> on the init_q
 // training image), then decode_kernel<SIN | DECODE_INITQ, true, SAVE>: acts in diinn_decode_train_fwd's layout, s_0 in radians.
-int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
-                                 float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+// chain: 0 = mode 3; 1 / 2 = modes 1/2 (pixel_chain_kernel over all Hu rows between the planes and the layers, KPART = false),
+// 2 with the chain's layers 1..3 seeded from bK_i of the body image (diinn_pixel_chain's bk_seeds)
+static int initq_train_fwd_impl(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode,
+                                int chain) {
     if (!feat_dev || !packed_dev || !train_image_dev || !pix_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -1330,8 +1335,14 @@ int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const floa
     st = check_npix(npix);
     if (st) return st;
     if ((((size_t)packed_dev) | ((size_t)train_image_dev) | ((size_t)pix_dev)) & 15) return DIINN_ERR_INVALID_ARG;   // 16-byte pieces and seeds
+    // (what the two launches in front of decode_kernel would refuse: checked before the first of them)
+    if (B > 65535 || (Hu + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
     st = launch_initq_planes(stream, feat_dev, packed_dev, train_image_dev, pix_dev, B, H, W, Hu, Wu, 0, Hu, sin_mode, true);
     if (st) return st;
+    if (chain) {
+        st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, Hu, chain == 2);
+        if (st) return st;
+    }
     const dim3 grid((unsigned)((npix + 4 * PLANE_TILE - 1) / (4 * PLANE_TILE)));
     DecodeParams p;
     p.P = pix_dev; p.Wt = packed_dev; p.out = out_dev;
@@ -1347,6 +1358,15 @@ int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const floa
     const int small = diinn_uses_small_output_kernel(Hu, Wu);
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
+    if (chain) {
+        if (sin_mode == DIINN_SIN_HW)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (sin_mode == DIINN_SIN_HW_REDUCED)
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        return hip_status(hipGetLastError());
+    }
     if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
@@ -1354,6 +1374,20 @@ int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const floa
     else
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
+}
+
+int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                 float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    return initq_train_fwd_impl(stream, feat_dev, packed_dev, train_image_dev, pix_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, 0);
+}
+
+// init_q with modes 1/2 under autograd: the radians planes of the whole image, pixel_chain_kernel over all Hu rows, then
+// decode_kernel<SIN | DECODE_INITQ, false, SAVE>: k_i as the chain left it in the pixel record, s_i in radians.
+int diinn_decode_initq_train_fwd_qonly(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                       float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu,
+                                       int sin_mode, int bk_seeds) {
+    return initq_train_fwd_impl(stream, feat_dev, packed_dev, train_image_dev, pix_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode,
+                                bk_seeds ? 2 : 1);
 }
 
 int diinn_decode_train_fwd_qonly(void* stream, const float* chain_dev, const float* packed_dev, float* out_dev,

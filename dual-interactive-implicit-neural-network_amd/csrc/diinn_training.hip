@@ -521,6 +521,97 @@ __global__ __launch_bounds__(256, 1) void cell_chain_bwd_kernel(const ChainBwdPa
 }
 
 // ---------------------------------------------------------------------------------
+// pixel_chain_bwd_kernel (training backward, decoder modes 1 and 2 with init_q=True): with init_q the modulation chain runs per HR
+// pixel (pixel_chain_kernel), so its backward does too -- cell_chain_bwd_kernel's recurrence with the HR pixels in place of LR cells:
+//     g_a,3 = g^_a,3,      g_a,i-1 = [k_{i-1} > 0] (Kk_i^T g_a,i) + g^_a,i-1      (i = 3, 2, 1)
+// where g^_a,i = g_q,i sin(s_i) [k_i > 0] is what bwd_layer_kernel<., KPART=false> left in rows 0..255 of G_i.  A wave owns one plane
+// tile of 32 consecutive flattened pixels, keeps their 256-channel g_a,i in registers as the MFMA B operand and streams Kk_i^T
+// (part 0 of section WLT of the body image).  The mask is the sign of rows 0..255 of acts[i-1] (the saved k_{i-1}); g^_a,i-1 is read
+// from rows 0..255 of G_{i-1} and g_a,i-1 written over them (a wave reads a row of its tile before it writes it; no other wave
+// touches the tile).  G_3 and the g_s rows 256..511 of every group are not touched.  Lanes of a ragged last tile's padding carry an
+// offset outside every descriptor: their loads return zeros, their stores are dropped, and a pixel is one column of the GEMM.
+// No atomics, no scratch, no LDS, fixed summation order.
+// The layer loop is cell_chain_bwd_kernel's line for line, with the tiled planes in place of the workspace record and of S / dP.  It is
+// NOT one __device__ function called from both kernels: under hipcc 7.2 every such form -- an I/O policy struct, the accesses
+// passed as lambdas, even cell_chain_bwd_kernel's own text moved verbatim behind one always-inline function -- changed that kernel's
+// instruction stream (40,100 -> 40,520 .. 41,724 bytes at the same register counts), and the modes-1/2 training
+// path that is already measured runs on it.
+// ---------------------------------------------------------------------------------
+struct PixChainBwdParams {
+    float* G;                // tiled [4][ntiles][512][32]; rows 0..255 of groups 0..2 are completed in place
+    const float* acts;       // tiled [4][ntiles][512][32]; rows 0..255 = k_i
+    const float* Wt;         // body image
+    long long npix, ntiles;
+};
+
+__global__ __launch_bounds__(256, 1) void pixel_chain_bwd_kernel(const PixChainBwdParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31;
+    const long long tile = (long long)blockIdx.x * 4 + wave;
+    if (tile >= p.ntiles) return;                                // wave-uniform
+    const bool valid = tile * PLANE_TILE + j < p.npix;
+    const size_t agroup = (size_t)p.ntiles * ACT_ROWS * PLANE_TILE;     // floats per layer of acts / G
+    // lanes past the end: offset outside the descriptor, loads return 0 and stores are dropped
+    const unsigned voff = valid ? 4u * j + 4u * h * PLANE_ROW_BYTES : 0xFFFFFFF0u;
+
+    float ga[128];
+    {
+        const __amdgpu_buffer_rsrc_t g3 = tile_rsrc(p.G + 3 * agroup, tile, ACT_ROWS);     // G_3 holds g_a,3 already
+#pragma unroll
+        for (int kk = 0; kk < 128; ++kk) {
+            const unsigned so = (unsigned)(32 * (kk >> 4) + (kk & 3) + 8 * ((kk & 15) >> 2)) * PLANE_ROW_BYTES;
+            ga[kk] = ld_plane(g3, voff, so);
+        }
+    }
+
+    constexpr int PF = DECODE_PREFETCH;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);   // reads past the end return 0
+    const int lane_off = lane * 16;
+#pragma unroll 1
+    for (int li = 3; li >= 1; --li) {
+        const int wp = (int)((OFF_WLT + (size_t)(li - 1) * WL_LAYER) * sizeof(float));
+        f32x4 rk[PF];
+#pragma unroll
+        for (int d = 0; d < PF; ++d) rk[d] = ld_piece(wrs, lane_off, wp + (2 * d) * PIECE_BYTES);
+        // this wave's tile of layer li-1; every row offset below is a constant under 256: the k rows of acts, the g_a rows of G
+        const __amdgpu_buffer_rsrc_t act = tile_rsrc(p.acts + (size_t)(li - 1) * agroup, tile, ACT_ROWS);
+        const __amdgpu_buffer_rsrc_t gl = tile_rsrc(p.G + (size_t)(li - 1) * agroup, tile, ACT_ROWS);
+        float gn[128];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            float kv[16], sv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const unsigned so = (unsigned)(32 * m + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES;
+                kv[r] = ld_plane(act, voff, so);                  // k_{li-1}: its sign is the mask
+                sv[r] = ld_plane(gl, voff, so);                   // g^_a,li-1
+            }
+            f32x16 ak;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ak[r] = 0.0f;
+#pragma unroll
+            for (int kg = 0; kg < WL_KG; ++kg) {
+                const int s = m * WL_KG + kg;
+                const f32x4 wk = rk[s % PF];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ak = MFMA32(wk[e], ga[4 * kg + e], ak);
+                rk[s % PF] = ld_piece(wrs, lane_off, wp + (2 * (s + PF)) * PIECE_BYTES);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = (kv[r] > 0.0f ? ak[r] : 0.0f) + sv[r];
+                gn[16 * m + r] = v;
+                st_act(gl, voff, (unsigned)(32 * m + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES, v);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 128; ++i) ga[i] = gn[i];
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // unfold_tiled_kernel (training backward, weight gradient of the hoisted 3x3 conv): the reference's F.unfold(feat, 3, padding=1)
 // (diinn.py:168; row = c * 9 + ky * 3 + kx) written directly as a tiled plane group over the CELL axis,
 // [ceil(B H W / 32)][rows][32] with rows >= 576 (the rows past 576 zero: diinn_plane_gemm_nt wants M % 128 == 0) -- the B
@@ -872,6 +963,16 @@ int diinn_cell_chain_bwd(void* stream, const float* S_tiled_dev, const float* ch
     if ((ntiles + 3) / 4 > 2147483000LL) return DIINN_ERR_TOO_LARGE;
     ChainBwdParams p{S_tiled_dev, chain_dev, packed_dev, dP_dev, dP_tiled_dev, k_tiled_dev, cells, ntiles, H * W};
     hipLaunchKernelGGL(cell_chain_bwd_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+int diinn_pixel_chain_bwd(void* stream, float* G_dev, const float* acts_dev, const float* packed_dev, long long npix) {
+    if (!G_dev || !acts_dev || !packed_dev) return DIINN_ERR_INVALID_ARG;
+    const int stp = check_npix(npix);
+    if (stp) return stp;
+    if ((((size_t)G_dev) | ((size_t)acts_dev) | ((size_t)packed_dev)) & 15) return DIINN_ERR_INVALID_ARG;   // 16-byte weight pieces, 128-byte rows
+    PixChainBwdParams p{G_dev, acts_dev, packed_dev, npix, (npix + PLANE_TILE - 1) / PLANE_TILE};
+    hipLaunchKernelGGL(pixel_chain_bwd_kernel, dim3((unsigned)((p.ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }
 

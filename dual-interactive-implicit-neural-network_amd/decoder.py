@@ -835,7 +835,7 @@ class ImplicitDecoder(nn.Module):
     ``hip_initq_modes`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True`` with modes 1, 2 and 4
     into INFERENCE on the HIP path (fp32; ``decode_features_initq``: the per-pixel modulation chain of modes 1/2, mode 4's tap form
     on the pixel planes).  With it unset those decoders refuse exactly as before.  With it set they still
-    refuse autograd (``hip_autograd`` / ``hip_autograd_mode4`` do not open it), the bf16 arithmetics, ``DIINN(graphs=True)`` and the
+    refuse autograd (``hip_autograd`` / ``hip_autograd_mode4`` do not open it; ``hip_autograd_initq_modes``, below, does), the bf16 arithmetics, ``DIINN(graphs=True)`` and the
     sharded forward; it changes nothing for mode 3 or ``init_q=False``.
 
     ``hip_initq_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, INFERENCE
@@ -843,16 +843,27 @@ class ImplicitDecoder(nn.Module):
     DESIGN.md 3.6d).  With it unset every ``compute`` other than ``"f32"`` refuses as before.  With it set only ``"bf16x3"`` opens:
     ``"bf16"`` / ``"bf16_full"``, autograd, ``init_q`` with modes 1/2/4, ``DIINN(graphs=True)`` and the sharded forward keep
     refusing with their messages, and ``compute="f32"`` gives the fp32 bits.  ``DIINN.set_split_bf16()`` does not set it: on an
-    ``init_q`` model the user sets both."""
+    ``init_q`` model the user sets both.
+
+    ``hip_autograd_initq_modes`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True`` with modes 1, 2
+    and 4 into TRAINING, and acts only together with ``hip_initq_modes``, in fp32: with both set, ``forward(x, size, None)`` under
+    autograd runs ``initq_modes_training.DecodeInitqModesFunction`` (modes 1/2: the per-pixel modulation chain forwards and, on
+    pixel_chain_bwd_kernel, backwards; mode 4: mode 3's ``init_q`` training forward, the 3x3 head from its saved planes, the output
+    at least 2 x 2; ROCm GPU only).  With ``bsize`` given or under ``no_grad`` the call is ``hip_initq_modes``'
+    inference path, bit for bit.  Set alone it changes nothing; with it unset every call refuses as before (``hip_autograd`` and
+    ``hip_autograd_mode4`` still do not open these combinations); the bf16 arithmetics, ``DIINN(graphs=True)`` and the sharded
+    forward keep refusing."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
     hip_initq_modes = False
     hip_initq_split_bf16 = False
+    hip_autograd_initq_modes = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
-                 hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False):
+                 hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False,
+                 hip_autograd_initq_modes: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
@@ -860,6 +871,7 @@ class ImplicitDecoder(nn.Module):
         self.hip_autograd_mode4 = bool(hip_autograd_mode4)
         self.hip_initq_modes = bool(hip_initq_modes)
         self.hip_initq_split_bf16 = bool(hip_initq_split_bf16)
+        self.hip_autograd_initq_modes = bool(hip_autograd_initq_modes)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -974,10 +986,20 @@ class ImplicitDecoder(nn.Module):
         ``init_q=True`` with modes 1, 2, 4 (``hip_initq_modes`` set; fp32, inference only): the same chunks of HR rows; mode 4
         computes the planes and the taps of a chunk's rows plus one row each way, clipped to the image, and it is those
         ``initq_chunk_rows`` rows that stay within the cap (a chunk is two output rows shorter).  Chunks change no bit,
-        ``bsize`` is ignored, and mode 4 reproduces ``bsize=None`` as it does without ``init_q``."""
+        ``bsize`` is ignored, and mode 4 reproduces ``bsize=None`` as it does without ``init_q``.  Under autograd with ``bsize=None``
+        it raises unless ``hip_autograd_initq_modes`` is set as well (then: ``initq_modes_training.DecodeInitqModesFunction``, the
+        whole image at once)."""
         self._check_supported()
         wants_grad = bsize is None and torch.is_grad_enabled() and (
             x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        # the opt-in (initq_modes_training.py): acts only together with hip_initq_modes, in fp32
+        initq_modes_grad = bool(self._initq_modes() and self.hip_autograd_initq_modes and self.compute == "f32")
+        if wants_grad and initq_modes_grad:
+            if self.mode == 4 and (int(size[0]) < 2 or int(size[1]) < 2):
+                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {int(size[0])} x {int(size[1])}")
+            _require_cuda(x, "x")
+            from .initq_modes_training import decode_with_grad as decode_initq_modes_with_grad
+            return decode_initq_modes_with_grad(self, x, size)
         if wants_grad and self._initq_modes():
             raise NotImplementedError(
                 f"diinn_amd: init_q=True with mode {self.mode} (ImplicitDecoder.hip_initq_modes) is inference only: autograd "

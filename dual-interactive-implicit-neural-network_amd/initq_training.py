@@ -237,7 +237,8 @@ def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torc
 # the HIP path
 # ---------------------------------------------------------------------------
 def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, packed: torch.Tensor, image: torch.Tensor,
-                         size: Sequence[int], need_feat_grad: bool = True) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+                         size: Sequence[int], need_feat_grad: bool = True, qonly: bool = False,
+                         head: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """The same gradients as ``backward_from_saved_initq``, on the HIP kernels throughout:
       diinn_backward_data     3 x bwd_layer_kernel: the per-pixel chain of mode 3, unchanged; leaves G_i = (g_a,i ; g_s,i) and q_i
       diinn_plane_gemm_nt     [dWq_i ; dQw_i | bias sums] = G_i . q_{i-1}^T (i = 1..3), as in mode 3
@@ -246,7 +247,14 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
       diinn_plane_gemm_nt     dWx_i^T [640 x 256] = x' . g_a,i^T (i = 0..3) and dQ0^T = E . g_s,0^T
       diinn_plane_rowdot      (dFw | dbF) = da . (rel_h, rel_w, ratio, 1)^T
       diinn_cell_sum_rows, diinn_fold3x3    dfeat = fold3x3(per-cell sums of U)
-    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward, ``packed`` / ``image`` the two images it ran on."""
+    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward, ``packed`` / ``image`` the two images it ran on.
+
+    The other decoder modes with ``init_q`` (initq_modes_training.py) change the CHAIN -- the first two lines above -- and nothing behind it:
+      ``qonly`` (modes 1/2, K.1..3 in mode 2's shape)  diinn_backward_data_qonly, then diinn_pixel_chain_bwd completes g_a,i in place over
+                rows 0..255 of G_i; [dKk_i | dbK_i] = g_a,i . k_{i-1}^T (rows 0..255 of ``acts[i-1]``) and [dQw_i | dbQ_i] = g_s,i . q_{i-1}^T
+                are two 256-row plane GEMMs per layer in place of the stacked 512-row one;
+      ``head``  (mode 4: the 3x3 head image; ``packed`` is the body image with a zero 1x1 head)  diinn_backward_data_head3x3, and
+                d last_layer.weight [3,256,3,3] from q_3 against the seven 4-row groups of dT, as in ``training.backward_fused``."""
     lib = _native.load()
     b, _, h, w = feat.shape
     hu, wu = int(size[0]), int(size[1])
@@ -261,32 +269,53 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
     gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
     g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), **f32)
     q = torch.empty((4, t, HIDDEN, PLANE_TILE), **f32)
-    gout_t = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))     # 4-row right-hand side of the head product
+    if qonly and head is not None:
+        raise ValueError("qonly (modes 1/2) and head (mode 4) exclude each other")
+    if head is None:
+        heads = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))[None]     # 4-row right-hand side of the head product
+    else:
+        # dT as seven 4-row groups (row 27 zero), written by bwd_head3x3_kernel; the rowdot reads whole tiles: a ragged last tile's padding is zeroed here
+        heads = (torch.empty if n % PLANE_TILE == 0 else torch.zeros)((7, t, 4, PLANE_TILE), **f32)
     u_t = torch.empty((t, UNFOLD, PLANE_TILE), **f32)
     da_t = torch.empty((t, UNFOLD, PLANE_TILE), **f32)
     xp_t = torch.empty((t, PAD_ROWS, PLANE_TILE), **f32)
     e_t = torch.empty((t, PAD_ROWS, PLANE_TILE), **f32)
-    ksplit = max(1, min(WGRAD_KSPLIT, t))
+    # (qonly: the weight-gradient GEMMs have 256 rows = 2 output blocks; twice the splits make one workgroup per CU, as in backward_fused_modes12)
+    ksplit = max(1, min(2 * WGRAD_KSPLIT if qonly else WGRAD_KSPLIT, t))
     xsplit = max(1, min(WGRAD_X_KSPLIT, t))
     rsplit = max(1, min(ROWDOT_SPLITS, t))
-    part = torch.empty((3, ksplit, 2 * HIDDEN, HIDDEN + 1), **f32)
+    part = torch.empty((6, ksplit, HIDDEN, HIDDEN + 1) if qonly else (3, ksplit, 2 * HIDDEN, HIDDEN + 1), **f32)
     partx = torch.empty((5, xsplit, PAD_ROWS, HIDDEN), **f32)
     part0 = torch.empty((rsplit, 2 * HIDDEN, 4), **f32)
-    partl = torch.empty((rsplit, HIDDEN, 4), **f32)
+    partl = torch.empty((len(heads), rsplit, HIDDEN, 4), **f32)
     partf = torch.empty((rsplit, 2 * HIDDEN, 4), **f32)           # (dFw | dbF): the rowdot takes at most 512 rows per launch --
     partg = torch.empty((rsplit, UNFOLD - 2 * HIDDEN, 4), **f32)   # rows 0..511, then rows 512..575
     ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     d_feat = None
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n), "diinn_backward_data")
-        for i in (3, 2, 1):
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(q[i - 1]), HIDDEN, 0,
-                                                  ptr(part[i - 1]), 2 * HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
+        if qonly:
+            _native.check(lib.diinn_backward_data_qonly(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n), "diinn_backward_data_qonly")
+            _native.check(lib.diinn_pixel_chain_bwd(stream, ptr(g), ptr(acts), ptr(packed), n), "diinn_pixel_chain_bwd")
+            for i in (3, 2, 1):                                  # [dKk_i | dbK_i] = g_a,i . k_{i-1}^T, then [dQw_i | dbQ_i] = g_s,i . q_{i-1}^T
+                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(acts[i - 1]), 2 * HIDDEN, 0,
+                                                      ptr(part[2 * (i - 1)]), HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
+                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, HIDDEN, ptr(q[i - 1]), HIDDEN, 0,
+                                                      ptr(part[2 * (i - 1) + 1]), HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
+        else:
+            if head is None:
+                _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n), "diinn_backward_data")
+            else:
+                _native.check(lib.diinn_backward_data_head3x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(head), ptr(g), ptr(q), ptr(heads),
+                                                              b, hu, wu), "diinn_backward_data_head3x3")
+            for i in (3, 2, 1):
+                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(q[i - 1]), HIDDEN, 0,
+                                                      ptr(part[i - 1]), 2 * HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
         _native.check(lib.diinn_plane_rowdot(stream, ptr(g[0]), 2 * HIDDEN, ptr(syn_t), ptr(part0), 2 * HIDDEN, n, rsplit),
                       "diinn_plane_rowdot")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(gout_t), ptr(partl), HIDDEN, n, rsplit),
-                      "diinn_plane_rowdot")
+        for i in range(len(heads)):
+            _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(heads[i]), ptr(partl[i]), HIDDEN, n, rsplit),
+                          "diinn_plane_rowdot")
         _native.check(lib.diinn_initq_backward(stream, ptr(feat), ptr(g), ptr(image), ptr(u_t), ptr(da_t), ptr(xp_t), ptr(e_t),
                                                b, h, w, hu, wu), "diinn_initq_backward")
         for i in range(4):                                       # dWx_i^T [640 x 256] = x' . g_a,i^T
@@ -304,10 +333,14 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
                           "diinn_cell_sum_rows")
             _native.check(lib.diinn_fold3x3(stream, ptr(d_unf), ptr(d_feat), b, IN_CHANNELS, h, w), "diinn_fold3x3")
     grads: Dict[str, torch.Tensor] = {}
-    dl = _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: q_3 . (g_out ; 0)^T
-    grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
+    dl = _sum_parts(partl.view(len(heads), rsplit, -1)).view(len(heads), HIDDEN, 4)   # group i: q_3 . (rows 4 i .. 4 i + 3 of the right-hand side)^T
+    if head is None:                                             # [256, 4]: q_3 . (g_out ; 0)^T
+        grads["last_layer.weight"] = dl[0, :, :3].t().reshape(3, HIDDEN, 1, 1)
+    else:                                                        # [256, r = 3 (3 ky + kx) + c] -> [c, ch, ky, kx]
+        grads["last_layer.weight"] = dl.permute(1, 0, 2).reshape(HIDDEN, 28)[:, :27].t().reshape(3, 3, 3, HIDDEN).permute(2, 3, 0, 1).contiguous()
     grads["last_layer.bias"] = gp.sum(1)
-    dws = _sum_parts(part.view(3, ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)   # [3, 512, 257]: [dWq_i ; dQw_i | bias sums]
+    # [3, 512, 257]: [dWq_i ; dQw_i | bias sums] (qonly: the two 256-row products of a layer are neighbours in ``part``: the same view)
+    dws = _sum_parts(part.view(part.shape[0], ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)
     dxs = _sum_parts(partx.view(5, xsplit, -1)).view(5, PAD_ROWS, HIDDEN)[:, :UNFOLD].transpose(1, 2)   # [5, 256, 576]: dWx_0..3, dQ0
     d0 = _sum_parts(part0.view(1, rsplit, -1)).view(2 * HIDDEN, 4)   # column 3: (dbK_0 ; dbQ0)
     df = torch.cat([_sum_parts(partf.view(1, rsplit, -1)).view(2 * HIDDEN, 4),

@@ -431,6 +431,27 @@ int    diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const f
                                     int sin_mode);
 int    diinn_initq_backward(void* stream, const float* feat_dev, const float* G_dev, const float* train_image_dev,
                             float* U_dev, float* dA_dev, float* XP_dev, float* E_dev, int B, int H, int W, int Hu, int Wu);
+
+/* ---- decoder init_q=True with modes 1 and 2 under autograd (diinn.py:113-131 recorded by autograd).  Mode 4 with init_q needs no
+ * entry of its own: diinn_decode_initq_train_fwd on a body image with a zero 1x1 head, diinn_head3x3_from_planes,
+ * diinn_backward_data_head3x3, then mode 3's init_q backward. ----------------------------------------------------------------
+ * diinn_decode_initq_train_fwd_qonly: diinn_decode_initq_train_fwd with the per-pixel modulation chain (diinn_pixel_chain over all
+ *   Hu rows; bk_seeds as there) between the planes and the layers, which then run without their modulation GEMM: acts_dev holds
+ *   k_i as the chain left it in the pixel record and s_i in radians, in diinn_decode_train_fwd's layout.  A mode-1 decoder takes
+ *   this entry with K.1..3 widened by zero feature columns in both images (the slots then hold bK_i exactly; bk_seeds gives the
+ *   same bits).  Validates every argument before the first of its three launches.
+ * diinn_pixel_chain_bwd: the chain's backward per HR pixel, after diinn_backward_data_qonly on the same buffers.  With
+ *   g^_a,i = rows 0..255 of G_i as that call left them and k_i = rows 0..255 of group i of acts_dev,
+ *       g_a,3 = g^_a,3,     g_a,i-1 = [k_{i-1} > 0] (Kk_i^T g_a,i) + g^_a,i-1     (i = 3, 2, 1;  Kk_i = K.i.weight[:, :256])
+ *   written IN PLACE over rows 0..255 of G_2, G_1, G_0.  G_3, the g_s rows 256..511 of every group and the padding of a ragged last
+ *   tile are neither written nor (the padding) read as data.  Reads section 8 of the packed image.  fp32 MFMA, one kernel, no
+ *   atomics; G_dev, acts_dev and packed_dev 16-byte aligned, npix within DIINN_TRAIN_MAX_PIXELS.
+ *   From the completed G: diinn_initq_backward, dKk_i = g_a,i k_{i-1}^T and dbK_i (diinn_plane_gemm_nt on rows 0..255 of G_i against
+ *   rows 0..255 of group i-1 of acts_dev, with_rowsum), [dQw_i | dbQ_i] on rows 256..511 against q_{i-1}. */
+int    diinn_decode_initq_train_fwd_qonly(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                          float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu,
+                                          int sin_mode, int bk_seeds);
+int    diinn_pixel_chain_bwd(void* stream, float* G_dev, const float* acts_dev, const float* packed_dev, long long npix);
 int    diinn_cell_sum_rows(void* stream, const float* group_dev, int rows, int R, const int32_t* seg_h_dev,
                            const int32_t* seg_w_dev, float* out_dev, int B, int H, int W, int Hu, int Wu);
 int    diinn_fold3x3(void* stream, const float* dxunf_dev, float* dfeat_dev, int B, int C, int H, int W);
