@@ -207,6 +207,13 @@ SIGNATURES = {
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_backward_data_qonly": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_longlong]),
+    "diinn_split_train_floats": (C.c_size_t, []),
+    "diinn_pack_split_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diinn_pack_split_train_host": (C.c_int, [_f, _f]),
+    "diinn_decode_train_fwd_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_backward_data_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_longlong]),
     "diinn_head3x3_from_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int]),
     "diinn_backward_data_head3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -56,12 +56,28 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 // flag rides in the template argument, SIN_X = sine mode | X3_INITQ, as DECODE_INITQ does in decode_kernel: the instantiations that
 // existed before keep their symbol names and their instructions.  The one-block form only: the persistent form's gain is the next
 // block's layer 0 (table reads and fmas) under the last layer, and with init_q layer 0 is 64 loads and 256 sines.
+//
+// SAVE (mode 3 under autograd, behind ImplicitDecoder.hip_autograd_split_bf16; SIN_X = sine mode | X3_SAVE, carried like X3_INITQ so
+// that every instantiation that existed before keeps its symbol and its instructions): decode_kernel<SAVE>'s contract on this
+// kernel's arithmetic.  A wave owns one PLANE TILE -- 32 consecutive flattened pixels (b, y, x) -- and writes every layer's rectified
+// modulation k_i and sine argument s_i, fp32 and in RADIANS, to the tiled planes p.acts with non-temporal st_act stores (a ragged
+// last tile's padding is never written).  It therefore works in radians throughout: dsin<SIN_MODE>, the Q0 table and the biases
+// from the radians sections (Q0, BQ) of the gathered training image p.Wt, and the weight stream from the FORWARD HALF of the split
+// training image p.split (diinn_layout.h: section WLX's piece layout without the division by 2 pi).  Layer 0, P, the seeds, the
+// sine and the head stay fp32 as in inference.  The one-block form only.
 constexpr int X3_INITQ = 4;
+constexpr int X3_SAVE = 8;
 template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParams p) {
     constexpr int SIN_MODE = SIN_X & (X3_INITQ - 1);
     constexpr bool INITQ = (SIN_X & X3_INITQ) != 0;
-    static_assert(SIN_X >= 0 && SIN_X < 2 * X3_INITQ && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ");
+    constexpr bool SAVE = (SIN_X & X3_SAVE) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * X3_SAVE && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ | X3_SAVE");
+    static_assert(!(INITQ && SAVE), "the SAVE form covers init_q=False only");
+    constexpr size_t S_Q0 = SAVE ? OFF_Q0 : OFF_Q0R, S_BQ = SAVE ? OFF_BQ : OFF_BQR;
+    auto sine = [](float v) {
+        if constexpr (SAVE) return dsin<SIN_MODE>(v); else return dsin_rev<SIN_MODE>(v);
+    };
     __shared__ __attribute__((aligned(16))) bf16x8 park[4][2][16][64];     // [wave][hi, lo][fragment][lane] = 128 KiB
     __shared__ __attribute__((aligned(16))) float tab[6 * HID + 4];        // Q0h, Q0w (revolutions), t, L[3], bL | validity
     const int lane = threadIdx.x & 63;
@@ -69,7 +85,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     const int h = lane >> 5, j = lane & 31;
     const float* __restrict__ Wt = p.Wt;
     {   // the tables every pixel shares (as decode_kernel): t = fma(Q0r, ratio, bQ0) once per workgroup
-        const float* __restrict__ Q0s = Wt + OFF_Q0R + 4 * lane;
+        const float* __restrict__ Q0s = Wt + S_Q0 + 4 * lane;
         if (wave == 0) {
             if constexpr (!INITQ) {
                 *(f32x4*)(tab + 0 * HID + 4 * lane) = *(const f32x4*)(Q0s + 0 * HID);
@@ -90,13 +106,25 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
             *(f32x4*)(tab + 5 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 2 * HID + 4 * lane);
             if (lane == 0) {                                     // bL + the image's validity word (an image without the
                 const f32x4 bl = *(const f32x4*)(Wt + OFF_BL);   // derived sections decodes to NaN)
-                *(f32x4*)(tab + 6 * HID) = or_bits(bl, derived_nan_mask(Wt));
+                *(f32x4*)(tab + 6 * HID) = or_bits(bl, SAVE ? 0u : derived_nan_mask(Wt));   // (SAVE reads no derived section)
             }
         }
     }
-    const int x = p.x0 + blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
-    const int y = p.y0 + blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
-    const int b = blockIdx.z;
+    int x, y, b;
+    const long long ptile = (long long)blockIdx.x * 4 + wave;   // SAVE: plane tile of this wave
+    if constexpr (SAVE) {                                        // 32 consecutive flattened pixels, as decode_kernel<SAVE>
+        const long long pix = ptile * PLANE_TILE + j;
+        const long long pc = pix < p.npix ? pix : p.npix - 1;    // lanes past the end compute on the last pixel
+        const int hw = p.Hu * p.Wu;
+        b = (int)(pc / hw);
+        const int rem = (int)(pc - (long long)b * hw);
+        y = rem / p.Wu;
+        x = pix < p.npix ? rem - y * p.Wu : p.Wu;                // ... and are marked invalid below
+    } else {
+        x = p.x0 + blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
+        y = p.y0 + blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
+        b = blockIdx.z;
+    }
     const bool valid = (x < p.x1) && (y < p.y1);
     __syncthreads();
     if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
@@ -108,6 +136,13 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     axis_eval(p.aw, xc, ix, relw);
     const float* __restrict__ Pc = INITQ ? p.P + (((size_t)b * p.Prows + (yc - p.Prow0)) * p.Wu + xc) * PIX_CH + 4 * h
                                          : p.P + (((size_t)b * p.Prows + (iy - p.Prow0)) * p.W + ix) * PCH + 4 * h;
+    // saved planes (SAVE): one descriptor per layer over this wave's plane tile; a lane's offset is its pixel in the row of channel
+    // 4h, the channel row a compile-time scalar offset; lanes past the end carry an offset outside the descriptor: the store is dropped
+    const long long act_tiles = SAVE ? (p.npix + PLANE_TILE - 1) / PLANE_TILE : 0;
+    const unsigned act_voff = (SAVE && valid) ? 4u * j + 4u * h * PLANE_ROW_BYTES : 0xFFFFFFF0u;
+    auto act_rsrc = [&](int layer) {
+        return tile_rsrc(p.acts + (size_t)layer * act_tiles * ACT_ROWS * PLANE_TILE, ptile, ACT_ROWS);
+    };
 
     // ---- layer 0 (fp32), split into hi/lo fragments: register r = 4g+e of tile m -> q[2m + (r>>3)][r&7]
     bf16x8 qh[16], ql[16];
@@ -135,7 +170,15 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                         a = __builtin_fmaf(wh[e], relh, a);
                     }
                     __bf16 vh, vl;
-                    split_bf16(relu0(pv[e]) * dsin_rev<SIN_MODE>(a), vh, vl);
+                    if constexpr (SAVE) {
+                        const float kv = relu0(pv[e]);
+                        const __amdgpu_buffer_rsrc_t ar0 = act_rsrc(0);
+                        st_act(ar0, act_voff, (unsigned)(c0 + e) * PLANE_ROW_BYTES, kv);
+                        st_act(ar0, act_voff, (unsigned)(HID + c0 + e) * PLANE_ROW_BYTES, a);
+                        split_bf16(kv * sine(a), vh, vl);
+                    } else {
+                        split_bf16(relu0(pv[e]) * dsin_rev<SIN_MODE>(a), vh, vl);
+                    }
                     qh[2 * m + (g >> 1)][4 * (g & 1) + e] = vh;
                     ql[2 * m + (g >> 1)][4 * (g & 1) + e] = vl;
                 }
@@ -146,8 +189,9 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     constexpr int PF = DECODE_BF16X3_PREFETCH;
     static_assert(16 % PF == 0, "ring index must be static");
     constexpr int KS_BYTES = (int)(WLX_KSTEP * sizeof(float));
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
+    // (SAVE: the split training image, forward half first; the ring's four k-steps past that half's end land in the backward half)
+    const __amdgpu_buffer_rsrc_t wrs = SAVE ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.split + ST_OFF_FWD), 0, (int)(ST_FLOATS * sizeof(float)), 0x00020000)
+                                            : __builtin_amdgcn_make_buffer_rsrc((void*)Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
     const int lane_off = lane * 16;
     // the four pieces of a k-step by immediate offsets from one scalar offset
     auto ld_kstep = [&](f32x4& kh, f32x4& qhi, f32x4& kl, f32x4& qlo, const int soff) {
@@ -156,7 +200,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         kl = ld_piece(wrs, lane_off + 2 * PIECE_BYTES, soff);
         qlo = ld_piece(wrs, lane_off + 3 * PIECE_BYTES, soff);
     };
-    int wp = (int)(OFF_WLX * sizeof(float));
+    int wp = SAVE ? 0 : (int)(OFF_WLX * sizeof(float));
     f32x4 rkh[PF], rkl[PF], rqh[PF], rql[PF];
 #pragma unroll
     for (int d = 0; d < PF; ++d) ld_kstep(rkh[d], rqh[d], rkl[d], rql[d], wp + d * KS_BYTES);
@@ -164,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         sk[g] = *(const f32x4*)(Pc + HID + 8 * g);
-        sq[g] = *(const f32x4*)(Wt + OFF_BQR + 4 * h + 8 * g);
+        sq[g] = *(const f32x4*)(Wt + S_BQ + 4 * h + 8 * g);
     }
     float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
     bf16x8 (*mine)[16][64] = park[wave];
@@ -176,10 +220,24 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         const bool LAST = layer == 2;
         const int nl = layer < 2 ? layer + 1 : 2;
         const float* __restrict__ Pl = Pc + (layer + 1) * HID;
-        const float* __restrict__ Bq = Wt + OFF_BQR + layer * HID + 4 * h;
+        const float* __restrict__ Bq = Wt + S_BQ + layer * HID + 4 * h;
         const float* __restrict__ Pn = Pc + (nl + 1) * HID;
-        const float* __restrict__ Bn = Wt + OFF_BQR + nl * HID + 4 * h;
+        const float* __restrict__ Bn = Wt + S_BQ + nl * HID + 4 * h;
         const float* __restrict__ L = tab + 3 * HID + 4 * h;
+        const __amdgpu_buffer_rsrc_t arl = act_rsrc(layer + 1);
+        (void)arl;
+        // SAVE: k and s of accumulator register r of tile mt (channel 32 mt + (r&3) + 8 (r>>2) + 4h) leave as they are finished
+        auto act_value = [&](const int mt, const int r, const float kraw, const float sv) -> float {
+            if constexpr (SAVE) {
+                const float kv = relu0(kraw);
+                const unsigned so = (unsigned)(32 * mt + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES;
+                st_act(arl, act_voff, so, kv);
+                st_act(arl, act_voff, so + HID * PLANE_ROW_BYTES, sv);
+                return kv * sine(sv);
+            } else {
+                return relu0(kraw) * dsin_rev<SIN_MODE>(sv);
+            }
+        };
         f32x16 pk, ps;
         bf16x8 fh, fl;
         f32x4 l0[4], l1[4], l2[4];
@@ -223,7 +281,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                     }
                 }
                 if (m > 0) {                                      // one epilogue element of tile m-1 per k-step
-                    float v = relu0(pk[ks]) * dsin_rev<SIN_MODE>(ps[ks]);
+                    float v = act_value(m - 1, ks, pk[ks], ps[ks]);
                     asm volatile("" : "+v"(v));                   // the element stays behind its k-step (see decode_bf16x2_kernel)
                     if (LAST) {
                         o0 = __builtin_fmaf(l0[ks >> 2][ks & 3], v, o0);
@@ -255,7 +313,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float v = relu0(pk[r]) * dsin_rev<SIN_MODE>(ps[r]);
+            const float v = act_value(7, r, pk[r], ps[r]);
             if (LAST) {
                 o0 = __builtin_fmaf(l0[r >> 2][r & 3], v, o0);
                 o1 = __builtin_fmaf(l1[r >> 2][r & 3], v, o1);
@@ -694,5 +752,17 @@ int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int 
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+// mode 3 under autograd (diinn_decode_train_fwd_x3): one workgroup per four plane tiles; p.split = the split training image
+int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned blocks, int sin_mode) {
+    const dim3 grid(blocks);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }

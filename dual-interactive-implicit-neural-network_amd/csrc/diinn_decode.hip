@@ -1269,8 +1269,10 @@ int diinn_decode_tile_win(void* stream, const float* P_win_dev, int p_row0, int 
 }
 
 // The training forward, KPART = true (mode 3) or false (modes 1/2: P_dev holds the per-cell chain, diinn_cell_chain)
+// split_dev (mode 3 only): the split training image -- the per-pixel layers run on decode_bf16x3_kernel<SIN | X3_SAVE>
 static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
-                          float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode, bool kpart) {
+                          float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode, bool kpart,
+                          const float* split_dev = nullptr) {
     if (!P_dev || !packed_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -1295,6 +1297,10 @@ static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_
     const int small = diinn_uses_small_output_kernel(Hu, Wu);
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
+    if (split_dev) {
+        p.split = split_dev;
+        return launch_decode_bf16x3_save(stream, p, grid.x, sin_mode);
+    }
     if (!kpart) {
         if (sin_mode == DIINN_SIN_HW)
             hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -1316,6 +1322,12 @@ static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_
 int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
                            float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
     return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true);
+}
+
+int diinn_decode_train_fwd_x3(void* stream, const float* P_dev, const float* packed_dev, const float* split_dev, float* out_dev,
+                              float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    if (!split_dev || (((size_t)split_dev) & 15)) return DIINN_ERR_INVALID_ARG;     // 16-byte weight pieces
+    return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true, split_dev);
 }
 
 // init_q (mode 3) under autograd: the pixel planes of the WHOLE image in radians (initq_planes_kernel<SIN | INITQ_RAD> on the init_q

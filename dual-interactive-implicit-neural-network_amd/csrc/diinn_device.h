@@ -138,7 +138,10 @@ struct DecodeParams {
     long long o_bs, o_ps, o_rs;
     int seed_cols;         // decode_bf16_coop_kernel: LR columns of a block's footprint (row length of its LDS seed slab)
     int xcd_runs;          // decode_bf16_coop8_kernel: walk the blocks XCD by XCD (set when neighbouring blocks share P rows)
-    int pg[6];             // decode_bf16_coop8p_kernel: block grid (x, y, z), super-tile grid (x, y), super-tiles per XCD
+    union {                // (8-byte aligned at offset 112 either way: the layout every other kernel sees is unchanged)
+        int pg[6];         // decode_bf16_coop8p_kernel: block grid (x, y, z), super-tile grid (x, y), super-tiles per XCD
+        const float* split;   // decode_bf16x3_kernel<SIN | X3_SAVE> only: the split training image (diinn_pack_split_train)
+    };
     float ratio;           // fp32(H*W / (Hu*Wu))   (diinn.py:166)
     Axis ah, aw;
     union {
@@ -379,6 +382,9 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
 // diinn_bf16x3.hip: the same arithmetic from the pixel planes of init_q (decode_bf16x3_kernel<SIN | X3_INITQ>)
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+// diinn_bf16x3.hip: the training forward in that arithmetic (decode_bf16x3_kernel<SIN | X3_SAVE>; `blocks` workgroups of four plane tiles)
+__attribute__((visibility("hidden")))
+int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned blocks, int sin_mode);
 // diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1)
 __attribute__((visibility("hidden")))
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,

@@ -505,6 +505,36 @@ int diinn_pack_initq_x3(const float* Q0w, const float* Q0b, float* packed) {
     return DIINN_OK;
 }
 
+// ---- mode 3 under autograd in split-bf16 arithmetic: the split training image (diinn_layout.h "the SPLIT TRAINING image") ------
+// The host twin of diinn_pack_split_train (diinn_split_training.hip): the same two halves from a HOST image's sections WL and WLT.
+size_t diinn_split_train_floats(void) { return ST_FLOATS; }
+
+// one half: src [layer 3][m 8][kg 32][part 2][lane 64][e 4] fp32 -> dst [layer 3][m 8][ks 16][k_hi, q_hi, k_lo, q_lo][lane 64][j 8] bf16
+static void split_train_half(const float* src, uint16_t* dst) {
+    for (int i = 0; i < 3; ++i)
+        for (int m = 0; m < 8; ++m)
+            for (int ks = 0; ks < 16; ++ks)
+                for (int part = 0; part < 2; ++part) {
+                    uint16_t* xhi = dst + ((((size_t)i * 8 + m) * 16 + ks) * 4 + part) * (64 * 8);
+                    uint16_t* xlo = xhi + 2 * (64 * 8);
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int kg = 2 * ks + (j >> 2), e = j & 3;
+                            const float w = src[(size_t)i * WL_LAYER + (((size_t)m * WL_KG + kg) * 2 + part) * WL_PIECE + lane * 4 + e];
+                            const uint16_t hi = f32_to_bf16(w);
+                            xhi[lane * 8 + j] = hi;
+                            xlo[lane * 8 + j] = f32_to_bf16(w - bf16_to_f32(hi));   // exact difference, then one rounding
+                        }
+                }
+}
+
+int diinn_pack_split_train_host(const float* image, float* split) {
+    if (!image || !split) return DIINN_ERR_INVALID_ARG;
+    split_train_half(image + OFF_WL, reinterpret_cast<uint16_t*>(split + ST_OFF_FWD));
+    split_train_half(image + OFF_WLT, reinterpret_cast<uint16_t*>(split + ST_OFF_BWD));
+    return DIINN_OK;
+}
+
 // ---- decoder init_q=True under autograd: the training image (diinn_layout.h "the init_q TRAINING image") -----------
 size_t diinn_initq_train_packed_floats(void) { return IQT_FLOATS; }
 

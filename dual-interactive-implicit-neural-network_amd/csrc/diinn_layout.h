@@ -178,6 +178,19 @@ constexpr size_t IQT_OFF_WT   = IQ_FLOATS;                      // 150,020 (16-b
 constexpr size_t IQT_SZ_WT    = 4 * IQT_WAVE;                   // 819,200 floats
 constexpr size_t IQT_FLOATS   = IQT_OFF_WT + IQT_SZ_WT;         // 969,220
 
+// ---- mode 3 under autograd in split-bf16 arithmetic: the SPLIT TRAINING image (diinn_pack_split_train) ----
+// A separate image beside the (gathered) training image, two halves of SZ_WLX floats, both in section WLX's piece layout
+// [layer 3][m 8][ks 16][piece 4: k_hi, q_hi, k_lo, q_lo][lane 64][j 8] bf16, hi = bf16(w), lo = bf16(w - hi), round to nearest even:
+//   forward half  (ST_OFF_FWD): the per-pixel layers in RADIANS, w = W_part[ out = 32m + (lane&31) ][ in = chan_of_bf16(ks, lane>>5, j) ]
+//       -- section WL's values.  The modulation pieces are section WLX's bit for bit, the synthesis pieces lack its division by 2 pi.
+//   backward half (ST_OFF_BWD, "WLTX"): the transposed layers, w = W_part[ out = chan_of_bf16(ks, lane>>5, j) ][ in = 32m + (lane&31) ]
+//       -- section WLT's values: for output tile m and k-step ks the hi/lo pieces of Wq_i^T and Qw_i^T.
+// chan_of_bf16(ks, h, j) = chan_of(8 ks + j, h), so element (m, ks, part, lane, j) of either half is element
+// (m, kg = 2 ks + (j >> 2), part, lane, e = j & 3) of WL / WLT: the same lane, two 16-byte runs -- the device packer is one copy.
+constexpr size_t ST_OFF_FWD   = 0;
+constexpr size_t ST_OFF_BWD   = SZ_WLX;
+constexpr size_t ST_FLOATS    = 2 * SZ_WLX;                     // 786,432 floats = 3 MiB
+
 // channel held by activation register (m, r) of lane-half h
 DIINN_HD int chan_of(int kk /* = 16*m + r */, int h) {
     const int m = kk >> 4, r = kk & 15;

@@ -852,18 +852,28 @@ class ImplicitDecoder(nn.Module):
     at least 2 x 2; ROCm GPU only).  With ``bsize`` given or under ``no_grad`` the call is ``hip_initq_modes``'
     inference path, bit for bit.  Set alone it changes nothing; with it unset every call refuses as before (``hip_autograd`` and
     ``hip_autograd_mode4`` still do not open these combinations); the bf16 arithmetics, ``DIINN(graphs=True)`` and the sharded
-    forward keep refusing."""
+    forward keep refusing.
+
+    ``hip_autograd_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts mode 3, ``init_q=False``,
+    ``compute="bf16x3"`` into TRAINING: with it set, ``forward(x, size, None)`` under autograd runs
+    ``split_training.DecodeMode3SplitFunction`` -- the per-pixel chain in split-bf16 arithmetic forwards
+    (``decode_bf16x3_kernel<SAVE>``) and backwards (``bwd_layer_x3_kernel``), everything else of the step the fp32 kernels
+    (ROCm GPU only).  It acts for no other combination: with it unset every call refuses or runs exactly as
+    before; with it set modes 1, 2, 4 and ``init_q=True`` with ``compute="bf16x3"`` under autograd, ``"bf16"`` and
+    ``"bf16_full"`` under autograd, ``DIINN(graphs=True)`` and the sharded forward keep refusing, and ``compute="f32"`` trains in
+    fp32 as always.  ``DIINN.set_split_bf16()`` does not set it: a user who wants to train in the split arithmetic sets both."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
     hip_initq_modes = False
     hip_initq_split_bf16 = False
     hip_autograd_initq_modes = False
+    hip_autograd_split_bf16 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
                  hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False,
-                 hip_autograd_initq_modes: bool = False):
+                 hip_autograd_initq_modes: bool = False, hip_autograd_split_bf16: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
@@ -872,6 +882,7 @@ class ImplicitDecoder(nn.Module):
         self.hip_initq_modes = bool(hip_initq_modes)
         self.hip_initq_split_bf16 = bool(hip_initq_split_bf16)
         self.hip_autograd_initq_modes = bool(hip_autograd_initq_modes)
+        self.hip_autograd_split_bf16 = bool(hip_autograd_split_bf16)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -1009,7 +1020,9 @@ class ImplicitDecoder(nn.Module):
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
         initq_grad = self.init_q and self.hip_autograd and self.mode == 3 and self.compute == "f32"     # the opt-in (initq_training.py)
         mode4_grad = self.mode == 4 and self.hip_autograd_mode4 and not self.init_q and self.compute == "f32"   # the opt-in (mode4_training.py)
-        if wants_grad and not mode4_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
+        # the opt-in (split_training.py): mode 3, init_q=False, the split-bf16 arithmetic both ways
+        split_grad = bool(self.hip_autograd_split_bf16 and self.mode == 3 and not self.init_q and self.compute == "bf16x3")
+        if wants_grad and not mode4_grad and not split_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
             raise NotImplementedError(
                 "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
                 "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
@@ -1021,6 +1034,9 @@ class ImplicitDecoder(nn.Module):
             raise ValueError("init_q=True runs in fp32 only")
         _require_cuda(x, "x")
         if wants_grad:
+            if split_grad:
+                from .split_training import decode_with_grad as decode_split_with_grad
+                return decode_split_with_grad(self, x, size)
             if self.init_q:
                 from .initq_training import decode_with_grad as decode_initq_with_grad
                 return decode_initq_with_grad(self, x, size)

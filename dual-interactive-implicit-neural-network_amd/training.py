@@ -237,7 +237,7 @@ def _cell_sum(g: torch.Tensor, b: int, hu: int, wu: int, h: int, w: int,
 
 def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor,
                         params: Sequence[torch.Tensor], size: Sequence[int],
-                        need_feat_grad: bool = True, head=None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+                        need_feat_grad: bool = True, head=None, chain=None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """Gradients of the mode-3 decoder given d(loss)/d(out).
 
     gout [B,3,Hu,Wu]; feat [B,64,H,W]; acts [4,2,256,N] plain planes k_i, s_i (``untile_planes`` of the
@@ -251,7 +251,9 @@ def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tens
         dP_i[cell] = sum over the cell's pixels of g_a,i;  P = conv3x3(feat; Wx) + bK.
     Computed in the dtype of ``acts`` (fp32 from the kernels; float64 planes give the formulas' own ground truth).
     ``head`` (decoder mode 4, mode4_training.backward_from_saved_mode4): (g_q,3 [256,N], d last_layer.weight, d last_layer.bias) of
-    another head than the 1x1 one; ``params``' own ``last_layer`` tensors are then not read."""
+    another head than the 1x1 one; ``params``' own ``last_layer`` tensors are then not read.
+    ``chain`` (split_training.split_chain_backward_reference): a callable (Wq_i^T, g_a,i, Qw_i^T, g_s,i) -> g_q,i-1 that forms the
+    chain product in another arithmetic; None: the two matrix products and their sum in ``acts``' dtype, as always."""
     dt = acts.dtype
     p = {name: t.to(dt) for name, t in zip(PARAM_NAMES, params)}
     feat = feat.to(dt)
@@ -287,7 +289,7 @@ def backward_from_saved(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tens
         grads[f"Q.{i}.0.weight"] = (g_s @ q_prev.t()).reshape(HIDDEN, HIDDEN, 1, 1)
         grads[f"Q.{i}.0.bias"] = g_s.sum(1)
         d_p[i] = _cell_sum(g_a, b, hu, wu, h, w, idx_h, idx_w)
-        g_q = wfull[:, :HIDDEN].t() @ g_a + qw.t() @ g_s
+        g_q = wfull[:, :HIDDEN].t() @ g_a + qw.t() @ g_s if chain is None else chain(wfull[:, :HIDDEN].t(), g_a, qw.t(), g_s)
         del g_a, g_s, q_prev
     k, s = acts[0, 0], acts[0, 1]
     g_a = g_q * torch.sin(s) * (k > 0)
@@ -453,7 +455,7 @@ def _sum_parts(part: torch.Tensor) -> torch.Tensor:
 
 def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, params: Sequence[torch.Tensor],
                    packed: torch.Tensor, size: Sequence[int],
-                   need_feat_grad: bool = True, head: Optional[torch.Tensor] = None
+                   need_feat_grad: bool = True, head: Optional[torch.Tensor] = None, split: Optional[torch.Tensor] = None
                    ) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """The same gradients as ``backward_from_saved``, on the HIP kernels throughout:
       diinn_backward_data   3 x bwd_layer_kernel (the head's gates inside layer 3's): the per-pixel chain; leaves the
@@ -466,7 +468,12 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     ``head`` (decoder mode 4): the 3x3 head image (mode4_training.pack_head3x3_on_device); ``packed`` is then the body image with a
     zero 1x1 head.  Three things change, the rest is the same code: the chain starts with diinn_backward_data_head3x3 (the head's
     adjoint dT and layer 3's gates in bwd_head3x3_kernel, then layers 3, 2, 1); d last_layer.weight [3,256,3,3] is q_3 against the
-    seven 4-row groups of dT (7 x diinn_plane_rowdot, diinn_sum_parts); d last_layer.bias is the sum of g as before."""
+    seven 4-row groups of dT (7 x diinn_plane_rowdot, diinn_sum_parts); d last_layer.bias is the sum of g as before.
+    ``split`` (mode 3 only; split_training.pack_split_on_device): the split training image -- the chain then runs on
+    diinn_backward_data_x3 (3 x bwd_layer_x3_kernel, split-bf16 arithmetic) in place of diinn_backward_data; the planes it leaves
+    have the same layout and everything behind them is the same code.  None: today's fp32 chain."""
+    if split is not None and head is not None:
+        raise ValueError("the split-bf16 chain covers mode 3 only (no 3x3 head)")
     lib = _native.load()
     p = dict(zip(PARAM_NAMES, params))
     b, _, h, w = feat.shape
@@ -500,7 +507,10 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if head is None:
+        if split is not None:
+            _native.check(lib.diinn_backward_data_x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(split), ptr(g), ptr(q), n),
+                          "diinn_backward_data_x3")
+        elif head is None:
             _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
                           "diinn_backward_data")
         else:

@@ -498,6 +498,32 @@ int diinn_decode_train_fwd_qonly(void* stream, const float* chain_dev, const flo
 int diinn_backward_data(void* stream, const float* gout_planes_dev, const float* acts_dev,
                         const float* packed_dev, float* G_dev, float* Q_dev, long long npix);
 
+/* ---- Training, mode 3, the per-pixel chain in split-bf16 arithmetic (opt-in: ImplicitDecoder.hip_autograd_split_bf16) -------------
+ * The three per-pixel layers of the training forward and of the backward pass on v_mfma_f32_32x32x16_bf16: every operand of the
+ * 256 x 256 products is carried as hi = bf16(v), lo = bf16(v - hi) and a product is lo.hi + hi.lo + hi.hi with fp32 accumulation
+ * (DIINN_COMPUTE_BF16X3's rule).  Everything else -- the hoisted conv, layer 0, the sines, the head, the gates, every plane and
+ * every parameter-gradient kernel -- is fp32 and unchanged; the planes keep diinn_decode_train_fwd's / diinn_backward_data's
+ * contract, so the two forwards and the two backwards can be mixed freely.
+ * THE SPLIT TRAINING IMAGE: diinn_split_train_floats() = 2 x 393,216 floats, a buffer of its own (not a section of the packed image):
+ *   forward half : the layers in section 14's (WLX) piece layout [layer 3][m 8][ks 16][k_hi, q_hi, k_lo, q_lo][lane 64][j 8] bf16, from
+ *                  the RADIANS weights of section 0 (WL): modulation pieces bit-identical to section 14, synthesis pieces without
+ *                  its division by 2 pi;
+ *   backward half: the same layout from the transposed layers (section 8, WLT): for output tile m and k-step ks the hi/lo pieces of
+ *                  Wq_i^T and Qw_i^T.
+ * diinn_pack_split_train fills it on the device from any image that holds sections 0 and 8 (a host-packed image or the gathered
+ * training image; one kernel, both pointers 16-byte aligned); diinn_pack_split_train_host is its host twin, bit-identical.
+ * diinn_decode_train_fwd_x3: diinn_decode_train_fwd with the layers in that arithmetic (P_dev from diinn_precompute_P_wpu as there;
+ *   packed_dev supplies the radians tables: sections 3, 4, 5, 6).  Same outputs, same layouts, same status codes.  One kernel.
+ * diinn_backward_data_x3: diinn_backward_data with the chain products in that arithmetic: same inputs, outputs, checks and status
+ *   codes; packed_dev supplies the head rows (section 5), split_dev the transposed layers.  3 kernels. */
+size_t diinn_split_train_floats(void);
+int diinn_pack_split_train(void* stream, const float* image_dev, float* split_dev);
+int diinn_pack_split_train_host(const float* image, float* split);
+int diinn_decode_train_fwd_x3(void* stream, const float* P_dev, const float* packed_dev, const float* split_dev, float* out_dev,
+                              float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode);
+int diinn_backward_data_x3(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
+                           const float* split_dev, float* G_dev, float* Q_dev, long long npix);
+
 /* The same for decoder modes 1 and 2 (autograd's backward through diinn.py:116-131, the per-pixel part): the modulation branch
  * does not see q there, so g_q,i-1 = Qw_i^T g_s,i alone (half the MFMAs and half the weight stream of diinn_backward_data).
  * Same buffers and layouts; acts_dev from diinn_decode_train_fwd_qonly.  Rows 0..255 of G_i hold g_q,i sin(s_i) [k_i > 0], the
