@@ -44,6 +44,17 @@
         __builtin_amdgcn_sched_barrier(0);                                            \
     } while (0)
 
+// the Q-only form (X3_QONLY below): three MFMAs and two weight loads per k-step, the same epilogue VALU spread over the three
+#define X3_KSTEP_ORDER_Q()                                                            \
+    do {                                                                              \
+        _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) {                            \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
+            if (i_ < 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);            \
+            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);                        \
+        }                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                            \
+    } while (0)
+
 __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
     hi = (__bf16)v;
     lo = (__bf16)(v - (float)hi);               // exact difference: v and hi share sign and exponent range
@@ -65,21 +76,42 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 // from the radians sections (Q0, BQ) of the gathered training image p.Wt, and the weight stream from the FORWARD HALF of the split
 // training image p.split (diinn_layout.h: section WLX's piece layout without the division by 2 pi).  Layer 0, P, the seeds, the
 // sine and the head stay fp32 as in inference.  The one-block form only.
+//
+// QONLY (decoder modes 1/2, init_q=False, inference, behind ImplicitDecoder.hip_modes_split_bf16; SIN_X = sine mode | X3_QONLY):
+// decode_kernel<SIN, KPART = false>'s contract on this kernel's arithmetic.  cell_chain_kernel (fp32) has left the rectified
+// modulation k_i of the pixel's LR cell in slot i of P; it seeds the modulation accumulator, which no MFMA touches, and the
+// epilogue rectifies it again (idempotent) as the multiplier of the sine.  A k-step is the three synthesis MFMAs (q_lo.q_hi,
+// q_hi.q_lo, q_hi.q_hi, in that order, on ONE accumulator: the synthesis sums have the bits of the full form's) and loads only
+// pieces 1 and 3 of section WLX's k-step through a ring of those two.  Everything else is the code below as it is.
+//
+// TAPS (decoder mode 4, init_q=False, inference, the same switch; SIN_X = sine mode | X3_TAPS): layers 0..3 are the full form's, bit
+// for bit; the last layer's epilogue leaves the unsplit q_3 (fp32) in the wave's LDS slab, which nothing occupies then (32 KiB =
+// 128 floats x 64 lanes; a lane re-reads only what it wrote: no barrier), and decode_kernel<HEAD3>'s head follows: 27 sums in
+// the (m, g, e) order of the 1x1 head, the lane halves added by __shfl_xor, seven 16-byte stores into the tap buffer p.out =
+// [B][p.Orows rows from p.Orow0][Wu][TAP_STRIDE].  The head table (27 x 256 floats from p.head3) sits behind the Q0 rows of
+// `tab`; mode 4's bias and both validity words belong to head3x3_reflect_kernel, which follows unchanged.
+// Both flags ride in SIN_X like X3_INITQ and X3_SAVE; both are one-block forms only.
 constexpr int X3_INITQ = 4;
 constexpr int X3_SAVE = 8;
+constexpr int X3_QONLY = 16;
+constexpr int X3_TAPS = 32;
+typedef f32x4 __attribute__((may_alias)) f32x4_lds;
 template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParams p) {
     constexpr int SIN_MODE = SIN_X & (X3_INITQ - 1);
     constexpr bool INITQ = (SIN_X & X3_INITQ) != 0;
     constexpr bool SAVE = (SIN_X & X3_SAVE) != 0;
-    static_assert(SIN_X >= 0 && SIN_X < 2 * X3_SAVE && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ | X3_SAVE");
+    constexpr bool QONLY = (SIN_X & X3_QONLY) != 0;
+    constexpr bool TAPF = (SIN_X & X3_TAPS) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * X3_TAPS && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ | X3_SAVE | X3_QONLY | X3_TAPS");
     static_assert(!(INITQ && SAVE), "the SAVE form covers init_q=False only");
+    static_assert(!((QONLY || TAPF) && (INITQ || SAVE)) && !(QONLY && TAPF), "the Q-only and the tap form: init_q=False, inference, one at a time");
     constexpr size_t S_Q0 = SAVE ? OFF_Q0 : OFF_Q0R, S_BQ = SAVE ? OFF_BQ : OFF_BQR;
     auto sine = [](float v) {
         if constexpr (SAVE) return dsin<SIN_MODE>(v); else return dsin_rev<SIN_MODE>(v);
     };
     __shared__ __attribute__((aligned(16))) bf16x8 park[4][2][16][64];     // [wave][hi, lo][fragment][lane] = 128 KiB
-    __shared__ __attribute__((aligned(16))) float tab[6 * HID + 4];        // Q0h, Q0w (revolutions), t, L[3], bL | validity
+    __shared__ __attribute__((aligned(16))) float tab[(TAPF ? 3 + TAPS : 6) * HID + 4];   // Q0h, Q0w (revolutions), t, L[3], bL | validity (TAPF: the 27 head rows)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31;
@@ -99,6 +131,8 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                 for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(wr[e], p.ratio, bq[e]);
                 *(f32x4*)(tab + 2 * HID + 4 * lane) = t;
             }
+        } else if constexpr (TAPF) {
+            // (the 27 head rows are loaded by all four waves below)
         } else if (wave == 2) {
             *(f32x4*)(tab + 3 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 0 * HID + 4 * lane);
             *(f32x4*)(tab + 4 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 1 * HID + 4 * lane);
@@ -108,6 +142,11 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                 const f32x4 bl = *(const f32x4*)(Wt + OFF_BL);   // derived sections decodes to NaN)
                 *(f32x4*)(tab + 6 * HID) = or_bits(bl, SAVE ? 0u : derived_nan_mask(Wt));   // (SAVE reads no derived section)
             }
+        }
+        if constexpr (TAPF) {
+#pragma unroll
+            for (int v = threadIdx.x; v < TAPS * HID / 4; v += 256)
+                *(f32x4*)(tab + 3 * HID + 4 * v) = *(const f32x4*)(p.head3 + 4 * v);
         }
     }
     int x, y, b;
@@ -200,10 +239,18 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         kl = ld_piece(wrs, lane_off + 2 * PIECE_BYTES, soff);
         qlo = ld_piece(wrs, lane_off + 3 * PIECE_BYTES, soff);
     };
+    // QONLY: the two synthesis pieces alone
+    auto ld_kstep_q = [&](f32x4& qhi, f32x4& qlo, const int soff) {
+        qhi = ld_piece(wrs, lane_off + 1 * PIECE_BYTES, soff);
+        qlo = ld_piece(wrs, lane_off + 3 * PIECE_BYTES, soff);
+    };
     int wp = SAVE ? 0 : (int)(OFF_WLX * sizeof(float));
     f32x4 rkh[PF], rkl[PF], rqh[PF], rql[PF];
 #pragma unroll
-    for (int d = 0; d < PF; ++d) ld_kstep(rkh[d], rqh[d], rkl[d], rql[d], wp + d * KS_BYTES);
+    for (int d = 0; d < PF; ++d) {
+        if constexpr (QONLY) ld_kstep_q(rqh[d], rql[d], wp + d * KS_BYTES);
+        else ld_kstep(rkh[d], rqh[d], rkl[d], rql[d], wp + d * KS_BYTES);
+    }
     f32x4 sk[4], sq[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -212,6 +259,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     }
     float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
     bf16x8 (*mine)[16][64] = park[wave];
+    f32x4_lds (*q3s)[64] = (f32x4_lds (*)[64])park[wave];         // TAPF: q_3 in fp32, element 16 m + r of a lane at [4 m + (r >> 2)][lane][r & 3]
 
     // the layer loop is fully unrolled: LAST is a compile-time constant per copy and fuses the RGB head
     // (diinn.py:138) into the epilogue, on the unsplit activation
@@ -240,6 +288,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         };
         f32x16 pk, ps;
         bf16x8 fh, fl;
+        f32x4 fq;
         f32x4 l0[4], l1[4], l2[4];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -252,7 +301,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                     as[4 * g + e] = sq[g][e];
                 }
             }
-            if (LAST && m > 0) {                                  // head rows of the tile being finished
+            if (LAST && !TAPF && m > 0) {                         // head rows of the tile being finished
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     l0[g] = *(const f32x4*)(L + 0 * HID + 32 * (m - 1) + 8 * g);
@@ -263,16 +312,23 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) {
                 const int s = m * 16 + ks;
-                const bf16x8 wkh = __builtin_bit_cast(bf16x8, rkh[s % PF]);
                 const bf16x8 wqh = __builtin_bit_cast(bf16x8, rqh[s % PF]);
                 // the two small products first, the leading one last (the order the oracle's emulation adds them in)
-                ak = MFMA_BF16(__builtin_bit_cast(bf16x8, rkl[s % PF]), qh[ks], ak);
-                as = MFMA_BF16(__builtin_bit_cast(bf16x8, rql[s % PF]), qh[ks], as);
-                ak = MFMA_BF16(wkh, ql[ks], ak);
-                as = MFMA_BF16(wqh, ql[ks], as);
-                ak = MFMA_BF16(wkh, qh[ks], ak);
-                as = MFMA_BF16(wqh, qh[ks], as);
-                ld_kstep(rkh[s % PF], rqh[s % PF], rkl[s % PF], rql[s % PF], wp + (s + PF) * KS_BYTES);
+                if constexpr (QONLY) {
+                    as = MFMA_BF16(__builtin_bit_cast(bf16x8, rql[s % PF]), qh[ks], as);
+                    as = MFMA_BF16(wqh, ql[ks], as);
+                    as = MFMA_BF16(wqh, qh[ks], as);
+                    ld_kstep_q(rqh[s % PF], rql[s % PF], wp + (s + PF) * KS_BYTES);
+                } else {
+                    const bf16x8 wkh = __builtin_bit_cast(bf16x8, rkh[s % PF]);
+                    ak = MFMA_BF16(__builtin_bit_cast(bf16x8, rkl[s % PF]), qh[ks], ak);
+                    as = MFMA_BF16(__builtin_bit_cast(bf16x8, rql[s % PF]), qh[ks], as);
+                    ak = MFMA_BF16(wkh, ql[ks], ak);
+                    as = MFMA_BF16(wqh, ql[ks], as);
+                    ak = MFMA_BF16(wkh, qh[ks], ak);
+                    as = MFMA_BF16(wqh, qh[ks], as);
+                    ld_kstep(rkh[s % PF], rqh[s % PF], rkl[s % PF], rql[s % PF], wp + (s + PF) * KS_BYTES);
+                }
                 if (ks == 2) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
@@ -283,7 +339,10 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                 if (m > 0) {                                      // one epilogue element of tile m-1 per k-step
                     float v = act_value(m - 1, ks, pk[ks], ps[ks]);
                     asm volatile("" : "+v"(v));                   // the element stays behind its k-step (see decode_bf16x2_kernel)
-                    if (LAST) {
+                    if (LAST && TAPF) {
+                        fq[ks & 3] = v;
+                        if ((ks & 3) == 3) q3s[4 * (m - 1) + (ks >> 2)][lane] = fq;
+                    } else if (LAST) {
                         o0 = __builtin_fmaf(l0[ks >> 2][ks & 3], v, o0);
                         o1 = __builtin_fmaf(l1[ks >> 2][ks & 3], v, o1);
                         o2 = __builtin_fmaf(l2[ks >> 2][ks & 3], v, o2);
@@ -298,12 +357,12 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
                         }
                     }
                 }
-                X3_KSTEP_ORDER();
+                if constexpr (QONLY) X3_KSTEP_ORDER_Q(); else X3_KSTEP_ORDER();
             }
             pk = ak;
             ps = as;
         }
-        if (LAST) {
+        if (LAST && !TAPF) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 l0[g] = *(const f32x4*)(L + 0 * HID + 32 * 7 + 8 * g);
@@ -314,7 +373,10 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float v = act_value(7, r, pk[r], ps[r]);
-            if (LAST) {
+            if (LAST && TAPF) {
+                fq[r & 3] = v;
+                if ((r & 3) == 3) q3s[4 * 7 + (r >> 2)][lane] = fq;
+            } else if (LAST) {
                 o0 = __builtin_fmaf(l0[r >> 2][r & 3], v, o0);
                 o1 = __builtin_fmaf(l1[r >> 2][r & 3], v, o1);
                 o2 = __builtin_fmaf(l2[r >> 2][r & 3], v, o2);
@@ -339,6 +401,36 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
         wp += (int)(WLX_LAYER * sizeof(float));
     }
 
+    if constexpr (TAPF) {
+        // ---- mode 4: the 27 tap values T[k][c] = Lw[c][:][ky][kx] . q3 of this pixel, decode_kernel<HEAD3>'s sums in its order
+        float o[TAPS];
+#pragma unroll
+        for (int r = 0; r < TAPS; ++r) o[r] = 0.0f;
+        const float* __restrict__ L = tab + 3 * HID + 4 * h;
+#pragma unroll 1
+        for (int m = 0; m < 8; ++m) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c0 = 32 * m + 8 * g;
+                const f32x4 qv = q3s[4 * m + g][lane];
+#pragma unroll
+                for (int r = 0; r < TAPS; ++r) {
+                    const f32x4 l = *(const f32x4*)(L + r * HID + c0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[r] = __builtin_fmaf(l[e], qv[e], o[r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TAPS; ++r) o[r] += __shfl_xor(o[r], 32);
+        if (valid && h == 0) {
+            float* t = p.out + (((long long)b * p.Orows + (y - p.Orow0)) * p.Wu + x) * TAP_STRIDE;
+#pragma unroll
+            for (int v = 0; v < TAP_STRIDE / 4; ++v)
+                *(f32x4*)(t + 4 * v) = f32x4{o[4 * v], o[4 * v + 1], o[4 * v + 2], 4 * v + 3 < TAPS ? o[(4 * v + 3) % TAPS] : 0.0f};
+        }
+        return;
+    }
     o0 += __shfl_xor(o0, 32);
     o1 += __shfl_xor(o1, 32);
     o2 += __shfl_xor(o2, 32);
@@ -764,5 +856,29 @@ int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned bloc
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+// modes 1/2 in split bf16 (diinn_decode_qonly_x3*): P holds the per-cell chain (cell_chain_kernel); the one-block form only
+int launch_decode_bf16x3_qonly(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
+    const dim3 grid(gx, gy, gz);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+// mode 4 in split bf16 (diinn_decode_mode4_x3*): the tap form; p.out = the tap buffer, p.head3 = the head image; the one-block form only
+int launch_decode_bf16x3_taps(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
+    const dim3 grid(gx, gy, gz);
+    if (sin_mode == DIINN_SIN_HW)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (sin_mode == DIINN_SIN_HW_REDUCED)
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }

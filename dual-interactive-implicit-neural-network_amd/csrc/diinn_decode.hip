@@ -770,7 +770,8 @@ static F32Choice f32_kernel_choice(int B, int y0, int y1, int x0, int x1) {
 
 static int decode_tile_impl(void* stream, const float* P_dev, const float* packed_dev,
                             float* out_dev, int B, int H, int W, int Hu, int Wu,
-                            int y0, int y1, int x0, int x1, int sin_mode, int compute, RowWin pw, OutView ov) {
+                            int y0, int y1, int x0, int x1, int sin_mode, int compute, RowWin pw, OutView ov,
+                            bool x3q = false) {
     if (!compute_ok(compute))
         return DIINN_ERR_UNSUPPORTED;
     if (!P_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
@@ -815,6 +816,8 @@ static int decode_tile_impl(void* stream, const float* P_dev, const float* packe
         return launch_decode_bf16(stream, p, gx, gy, gz, sin_mode);
     if (compute == DIINN_COMPUTE_BF16X3)
         return launch_decode_bf16x3(stream, p, gx, gy, gz, sin_mode);
+    if (compute == DIINN_COMPUTE_F32_QONLY && x3q)              // modes 1/2, the synthesis branch in split bf16: decode_bf16x3_kernel<SIN | X3_QONLY>
+        return launch_decode_bf16x3_qonly(stream, p, gx, gy, gz, sin_mode);
     if (compute == DIINN_COMPUTE_F32_QONLY) {
         if (sin_mode == DIINN_SIN_HW)
             hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, false>), grid, dim3(blk), 0, (hipStream_t)stream, p);
@@ -846,16 +849,16 @@ static int decode_tile_impl(void* stream, const float* P_dev, const float* packe
 
 static int decode_band_impl(void* stream, const float* P_dev, const float* packed_dev,
                             float* out_dev, int B, int H, int W, int Hu, int Wu,
-                            int y0, int y1, int sin_mode, int compute, RowWin pw, RowWin ow) {
+                            int y0, int y1, int sin_mode, int compute, RowWin pw, RowWin ow, bool x3q = false) {
     if (Wu <= 0) return DIINN_ERR_INVALID_ARG;
     return decode_tile_impl(stream, P_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, 0, Wu, sin_mode, compute, pw,
-                            contig(ow, Wu));
+                            contig(ow, Wu), x3q);
 }
 
 static int decode_impl(void* stream, const float* feat_dev, const float* packed_dev,
                        float* workspace_dev, float* out_dev,
                        int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, int compute,
-                       RowWin fw, RowWin pw, RowWin ow) {
+                       RowWin fw, RowWin pw, RowWin ow, bool x3q = false) {
     if (!workspace_dev) return DIINN_ERR_INVALID_ARG;
 
     int r0, r1;
@@ -871,7 +874,7 @@ static int decode_impl(void* stream, const float* feat_dev, const float* packed_
         if (st) return st;
     }
     return decode_band_impl(stream, workspace_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
-                            compute, pw, ow);
+                            compute, pw, ow, x3q);
 }
 
 // ---------------------------------------------------------------------------------
@@ -927,10 +930,11 @@ __global__ __launch_bounds__(256) void head3x3_reflect_kernel(const Head3Params 
 }
 
 // Mode 4, HR rows [y0,y1) of the image from P: the tap form of decode_kernel over the extended rows [ty0,ty1), then the gather.
-// `ow`: the rows `out_dev` holds.  fp32 only, the throughput kernel only (no 16-pixel latency twin).
+// `ow`: the rows `out_dev` holds.  fp32: the throughput kernel only (no 16-pixel latency twin); x3: the tap form of the split-bf16
+// kernel, decode_bf16x3_kernel<SIN | X3_TAPS>, in its place (the same tap buffer, the same gather).
 static int decode_mode4_band_impl(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
                                   float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                                  int sin_mode, RowWin pw, RowWin ow) {
+                                  int sin_mode, RowWin pw, RowWin ow, bool x3 = false) {
     if (!P_dev || !packed_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
     int st = check_dims(B, H, W);
     if (st) return st;
@@ -962,7 +966,10 @@ static int decode_mode4_band_impl(void* stream, const float* P_dev, const float*
     p.ah = make_axis(H, Hu, small);
     p.aw = make_axis(W, Wu, small);
     const dim3 grid(gx, gy, B);
-    if (sin_mode == DIINN_SIN_HW)
+    if (x3) {
+        st = launch_decode_bf16x3_taps(stream, p, gx, gy, B, sin_mode);
+        if (st) return st;
+    } else if (sin_mode == DIINN_SIN_HW)
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else if (sin_mode == DIINN_SIN_HW_REDUCED)
         hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -1206,6 +1213,61 @@ int diinn_decode_mode4(void* stream, const float* feat_dev, const float* packed_
     if (st) return st;
     return decode_mode4_band_impl(stream, workspace_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1,
                                   sin_mode, full, RowWin{0, Hu});
+}
+
+// ---- decoder modes 1, 2 and 4 in split-bf16 arithmetic (include/diinn_hip.h; opt-in: ImplicitDecoder.hip_modes_split_bf16) ----
+// what every launch of these entry points would refuse, checked before the first of them
+static int modes_x3_args_ok(const void* a, const void* b, const void* c, const void* d, int B, int H, int W, int Hu, int Wu,
+                            int y0, int y1, int sin_mode) {
+    if (!a || !b || !c || !d) return DIINN_ERR_INVALID_ARG;
+    const int st = check_dims(B, H, W);
+    if (st) return st;
+    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
+    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
+    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    return DIINN_OK;
+}
+
+int diinn_decode_qonly_x3_band(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
+                               int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    return decode_band_impl(stream, P_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, DIINN_COMPUTE_F32_QONLY,
+                            RowWin{0, H}, RowWin{0, Hu}, true);
+}
+
+int diinn_decode_qonly_x3(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev, float* out_dev,
+                          int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    const int st = modes_x3_args_ok(feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    if ((y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y) > 65535) return DIINN_ERR_TOO_LARGE;
+    // P and the per-cell chain in fp32 (DIINN_COMPUTE_F32_QONLY's), the per-pixel layers on decode_bf16x3_kernel<SIN | X3_QONLY>
+    return decode_impl(stream, feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
+                       DIINN_COMPUTE_F32_QONLY, RowWin{0, H}, RowWin{0, H}, RowWin{0, Hu}, true);
+}
+
+int diinn_decode_mode4_x3_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
+                               float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                               int sin_mode) {
+    return decode_mode4_band_impl(stream, P_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
+                                  RowWin{0, H}, RowWin{0, Hu}, true);
+}
+
+int diinn_decode_mode4_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
+                          float* workspace_dev, float* taps_dev, float* out_dev,
+                          int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!head_dev || !taps_dev) return DIINN_ERR_INVALID_ARG;
+    int st = modes_x3_args_ok(feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (st) return st;
+    int ty0, ty1, r0, r1;
+    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
+    if (st) return st;
+    if ((ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y) > 65535 || (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H > 65535)
+        return DIINN_ERR_TOO_LARGE;
+    const RowWin full{0, H};
+    // the hoisted conv as DIINN_COMPUTE_BF16X3 runs it for mode 3 (split bf16 on large maps, the fp32 Winograd form below)
+    st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, r0, r1, 16, p_arith(DIINN_COMPUTE_BF16X3), &full, &full, true);
+    if (st) return st;
+    return decode_mode4_band_impl(stream, workspace_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1,
+                                  sin_mode, full, RowWin{0, Hu}, true);
 }
 
 int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B, int H, int W, int r0, int r1) {

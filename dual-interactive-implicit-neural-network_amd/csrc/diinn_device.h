@@ -13,6 +13,7 @@
 //   diinn_bf16.hip             decode_bf16_kernel, decode_bf16x2_kernel, decode_bf16_coop_kernel (4 waves),
 //                              decode_bf16_coop8_kernel (8 waves), decode_bf16_coop8p_kernel (8 waves, persistent)
 //   diinn_bf16x3.hip           decode_bf16x3h_kernel (persistent, hi weight pieces through LDS), decode_bf16x3_kernel: split bf16
+//                              (the latter also init_q's form, the training forward, the Q-only form of modes 1/2, mode 4's tap form)
 //   diinn_training.hip         backward pass: bwd_head / bwd_head3x3 (mode 4) / bwd_layer (<KPART=false>: modes 1/2), cell_chain_bwd (modes 1/2), plane_gemm, plane_rowdot, cell_sum
 //   diinn_mode4_training.hip   head3x3_taps_from_planes_kernel (mode 4 under autograd: the 3x3 head's tap values from the saved planes)
 //   diinn_enc_training.hip     the encoder's dense blocks under autograd: conv_wgrad (weight-gradient GEMM over the pixel axis), relu_gate
@@ -385,6 +386,12 @@ int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int 
 // diinn_bf16x3.hip: the training forward in that arithmetic (decode_bf16x3_kernel<SIN | X3_SAVE>; `blocks` workgroups of four plane tiles)
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned blocks, int sin_mode);
+// diinn_bf16x3.hip: decoder modes 1/2 in that arithmetic (decode_bf16x3_kernel<SIN | X3_QONLY>; P holds the per-cell chain) and
+// mode 4's tap form (decode_bf16x3_kernel<SIN | X3_TAPS>; p.out = the tap buffer, p.head3 = the head image)
+__attribute__((visibility("hidden")))
+int launch_decode_bf16x3_qonly(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+__attribute__((visibility("hidden")))
+int launch_decode_bf16x3_taps(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
 // diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1)
 __attribute__((visibility("hidden")))
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,

@@ -377,6 +377,86 @@ def initq_modes_forward_reference(sd, feat, size, mode: int, dtype=torch.float64
     return out
 
 
+def modes_x3_forward_reference(sd, feat, size, mode: int, prefix: str = "") -> torch.Tensor:
+    """The EMULATION sheet of the split-bf16 arithmetic of decoder modes 1, 2 and 4 with ``init_q=False``
+    (``decode_features(..., compute="bf16x3", modes_x3=True)``), in fp32 torch algebra on any device; beside
+    ``initq_forward_reference(..., split_bf16=True)``, which states mode 3 with ``init_q=True``.
+
+    What is split: the three synthesis products ``Q_i . q_{i-1}``, i = 1..3, of every mode, and for mode 4 the three modulation
+    products ``K_i[:, :256] . q_{i-1}`` as well.  Every operand of such a product is carried as hi = bf16(v), lo = bf16(v - hi) and
+    the product formed as ``(w_lo.q_hi + w_hi.q_lo) + w_hi.q_hi`` in fp32 (``_mm_split``: torch matmuls, not the MFMA's summation
+    order).  The synthesis branch runs in REVOLUTIONS: Q_0..3 and their biases are multiplied by fp32(1/(2 pi)) in fp32 before the
+    split, as the body image holds them, and every sine is taken of revolutions in float64 (``_sin_rev``).
+
+    What stays fp32: the hoisted conv ``P = Wx . unfold3x3(feat) + bK`` (mode 1: ``P_i = bK_i`` for i >= 1), the per-cell
+    modulation chain of modes 1/2, ``k_0 = relu(P_0)``, ``k_i = relu(K_i[:, :256] . k_{i-1} + P_i)`` (``cell_chain_kernel``), layer
+    0 with the kernels' fma sequence ``a = fma(Q0_h, rel_h, fma(Q0_w, rel_w, fma(Q0_r, ratio, bQ0)))``, the seeds and biases, and
+    the head on the unsplit ``q_3``: ``L . q_3 + bL`` (modes 1/2), or the 27 tap values per pixel and the reflect-padded 9-point
+    gather (mode 4)."""
+    if mode not in (1, 2, 4):
+        raise ValueError(f"modes_x3_forward_reference states modes 1, 2 and 4, got {mode}")
+    f32 = torch.float32
+    dev = feat.device
+
+    def get(name, shape):
+        t = sd[prefix + name]
+        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
+        return t.to(device=dev, dtype=f32).reshape(shape)
+
+    def fma(a_, b_, c_):                                      # one rounding: the fp32 product is exact in float64
+        return (a_.double() * b_.double() + c_.double()).to(f32)
+
+    inv = torch.tensor(INV_2PI_F32, dtype=f32, device=dev)
+    hu, wu = int(size[0]), int(size[1])
+    x = feat.to(f32)
+    b, c, h, w = x.shape
+    n = hu * wu
+    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
+    iy, rel_h = axis_tables(h, hu, small)
+    ix, rel_w = axis_tables(w, wu, small)
+    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
+    relh = torch.from_numpy(rel_h).to(dev, f32)[:, None].expand(hu, wu).reshape(1, n)
+    relw = torch.from_numpy(rel_w).to(dev, f32)[None, :].expand(hu, wu).reshape(1, n)
+    ratio = torch.tensor(np.float32((h * w) / (hu * wu)), dtype=f32, device=dev)
+    kin = HIDDEN if mode == 1 else HIDDEN + 576
+    kw = [get(f"K.{i}.0.weight", (HIDDEN, kin)) for i in (1, 2, 3)]
+    bk = [get(f"K.{i}.0.bias", (HIDDEN, 1)) for i in range(4)]
+    unf = torch.nn.functional.unfold(x, 3, padding=1)                                   # [b, 576, h*w], fp32
+    P = [get("K.0.0.weight", (HIDDEN, 576)) @ unf + bk[0]]
+    for i in (1, 2, 3):
+        P.append(bk[i].expand(b, HIDDEN, h * w) if mode == 1 else kw[i - 1][:, HIDDEN:] @ unf + bk[i])
+    cell = (iy_t[:, None] * w + ix_t[None, :]).reshape(n)                               # LR cell of every HR pixel
+    if mode != 4:                                                                       # the per-cell chain, fp32
+        kc = [torch.relu(P[0])]
+        for i in (1, 2, 3):
+            kc.append(torch.relu(kw[i - 1][:, :HIDDEN] @ kc[-1] + P[i]))
+    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 3)) * inv, get("Q.0.0.bias", (HIDDEN, 1)) * inv
+    a = fma(q0w[:, 2:3], ratio, q0b)
+    a = fma(q0w[:, 1:2], relw, a)
+    a = fma(q0w[:, 0:1], relh, a)
+    q = torch.relu(P[0][:, :, cell]) * _sin_rev(a)[None]                                # [b, 256, n]
+    for i in (1, 2, 3):
+        s = _mm_split(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) * inv, q) + get(f"Q.{i}.0.bias", (HIDDEN, 1)) * inv
+        if mode == 4:
+            k = torch.relu(_mm_split(kw[i - 1][:, :HIDDEN], q) + P[i][:, :, cell])
+        else:
+            k = kc[i][:, :, cell]
+        q = k * _sin_rev(s)
+    if mode != 4:
+        return (get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))).reshape(b, 3, hu, wu)
+    lw = get("last_layer.weight", (3, HIDDEN, 3, 3))
+    taps = torch.einsum("chyx,bhn->byxcn", lw, q).reshape(b, 3, 3, 3, hu, wu)           # T[ky][kx][c] per pixel
+    ry = torch.arange(-1, hu + 1, device=dev).abs()
+    ry = torch.where(ry >= hu, 2 * (hu - 1) - ry, ry)                                    # 'reflect': -1 -> 1, Hu -> Hu - 2
+    rx = torch.arange(-1, wu + 1, device=dev).abs()
+    rx = torch.where(rx >= wu, 2 * (wu - 1) - rx, rx)
+    out = get("last_layer.bias", (1, 3, 1, 1)).expand(b, 3, hu, wu).clone()
+    for ky in range(3):
+        for kx in range(3):
+            out = out + taps[:, ky, kx][:, :, ry[ky:ky + hu]][:, :, :, rx[kx:kx + wu]]
+    return out
+
+
 def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     """((ty0, ty1), (r0, r1)): the HR rows whose tap values mode 4 needs for output rows [y0,y1) (one more row each way,
     clipped to the image) and the LR rows those read (C ABI ``diinn_mode4_rows``)."""
@@ -422,7 +502,8 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
                     rows: Optional[Tuple[int, int]] = None, sin_mode: int = _native.SIN_DEFAULT,
                     compute: str = "f32", mode: int = 3, head: Optional[torch.Tensor] = None,
                     taps: Optional[torch.Tensor] = None, initq: Optional[torch.Tensor] = None,
-                    pix: Optional[torch.Tensor] = None, initq_x3: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    pix: Optional[torch.Tensor] = None, initq_x3: Optional[torch.Tensor] = None,
+                    modes_x3: bool = False) -> torch.Tensor:
     """Decode encoder features ``feat`` [B,64,H,W] to RGB [B,3,Hu,Wu].
 
     ``rows=(y0,y1)`` computes only that HR row band (tile sharding across GPUs);
@@ -440,6 +521,12 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
     whole-image decode.  ``initq_x3`` (with ``initq``, mode 3, ``compute="bf16x3"`` only): the init_q split image (``pack_initq_x3``)
     opens the split-bf16 arithmetic for such a decoder (``initq_planes_x3_kernel``, ``decode_bf16x3_kernel<SIN | X3_INITQ>``; the
     same ``pix``); without it ``compute="bf16x3"`` refuses like the other bf16 arithmetics.
+    ``modes_x3`` (default False; modes 1, 2 and 4 with ``compute="bf16x3"`` only): opens the split-bf16 arithmetic for those modes --
+    the Q-only form of ``decode_bf16x3_kernel`` behind the fp32 P and per-cell chain (modes 1/2: C ABI ``diinn_decode_qonly_x3``), its
+    tap form behind mode 3's ``"bf16x3"`` P and in front of the unchanged gather (mode 4: ``diinn_decode_mode4_x3``); the same images,
+    ``rows``, ``out``, ``workspace`` and ``taps``, bands bit-identical to the same rows of a whole-image decode.
+    Without it these modes refuse every ``compute`` but ``"f32"`` as before; with it ``"bf16"`` and ``"bf16_full"`` still refuse, and
+    mode 3 and ``"f32"`` are what they are without it.
     Enqueues two kernels (three for modes 1/2: + the per-cell modulation chain; three for mode 4: + the 9-point
     gather) on the current stream; never synchronises."""
     lib = _native.load()
@@ -502,7 +589,8 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
         raise ValueError(f"workspace must be a contiguous buffer of >= {need} bytes on feat's device")
     if mode not in (1, 2, 3, 4):
         raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-4")
-    if mode != 3 and compute != "f32":
+    x3 = bool(modes_x3) and mode != 3 and compute == "bf16x3"     # the opt-in: split bf16 for modes 1, 2 and 4
+    if mode != 3 and compute != "f32" and not x3:
         raise ValueError("modes 1, 2 and 4 run in fp32 only")
     if mode == 4:
         if head is None:
@@ -517,17 +605,24 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
             taps = torch.empty(tneed // 4, dtype=torch.float32, device=feat.device)
         elif taps.numel() * taps.element_size() < tneed or not taps.is_contiguous() or taps.device != feat.device:
             raise ValueError(f"taps must be a contiguous buffer of >= {tneed} bytes on feat's device")
+        name = "diinn_decode_mode4_x3" if x3 else "diinn_decode_mode4"
         with torch.cuda.device(feat.device):
             stream = torch.cuda.current_stream().cuda_stream
-            st = lib.diinn_decode_mode4(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                        C.c_void_p(head.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                        C.c_void_p(taps.data_ptr()), C.c_void_p(out.data_ptr()),
-                                        b, h, w, hu, wu, y0, y1, int(sin_mode))
-        _native.check(st, "diinn_decode_mode4")
+            st = getattr(lib, name)(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                    C.c_void_p(head.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                    C.c_void_p(taps.data_ptr()), C.c_void_p(out.data_ptr()),
+                                    b, h, w, hu, wu, y0, y1, int(sin_mode))
+        _native.check(st, name)
         return out
     comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
     with torch.cuda.device(feat.device):
         stream = torch.cuda.current_stream().cuda_stream
+        if x3:
+            st = lib.diinn_decode_qonly_x3(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
+                                           C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()),
+                                           b, h, w, hu, wu, y0, y1, int(sin_mode))
+            _native.check(st, "diinn_decode_qonly_x3")
+            return out
         st = lib.diinn_decode_ex(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
                                  C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()),
                                  b, h, w, hu, wu, y0, y1, int(sin_mode), comp)
@@ -861,7 +956,16 @@ class ImplicitDecoder(nn.Module):
     (ROCm GPU only).  It acts for no other combination: with it unset every call refuses or runs exactly as
     before; with it set modes 1, 2, 4 and ``init_q=True`` with ``compute="bf16x3"`` under autograd, ``"bf16"`` and
     ``"bf16_full"`` under autograd, ``DIINN(graphs=True)`` and the sharded forward keep refusing, and ``compute="f32"`` trains in
-    fp32 as always.  ``DIINN.set_split_bf16()`` does not set it: a user who wants to train in the split arithmetic sets both."""
+    fp32 as always.  ``DIINN.set_split_bf16()`` does not set it: a user who wants to train in the split arithmetic sets both.
+
+    ``hip_modes_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts modes 1, 2 and 4, ``init_q=False``,
+    INFERENCE into ``compute="bf16x3"``: with it set, ``forward`` under ``no_grad`` (or with ``bsize`` given) runs
+    ``decode_features(..., compute="bf16x3", modes_x3=True)`` -- the Q-only form of ``decode_bf16x3_kernel`` for modes 1/2, its tap
+    form for mode 4 (chunked by ``MODE4_CHUNK_ROWS`` like the fp32 path; ``DIINN(graphs=True)`` replays it) -- DESIGN.md 3.5b.  With
+    it unset these modes refuse every ``compute`` but ``"f32"`` as before.  With it set the following keep refusing with their
+    messages: autograd through these modes with ``"bf16x3"``; ``init_q=True`` with modes 1/2/4 in any bf16 arithmetic;
+    ``DIINN.forward_sharded``; ``"bf16"`` and ``"bf16_full"``.  It changes nothing for mode 3 or for ``compute="f32"``.
+    ``DIINN.set_split_bf16()`` does not set it: on such a model the user sets both."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
@@ -869,11 +973,13 @@ class ImplicitDecoder(nn.Module):
     hip_initq_split_bf16 = False
     hip_autograd_initq_modes = False
     hip_autograd_split_bf16 = False
+    hip_modes_split_bf16 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
                  hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False,
-                 hip_autograd_initq_modes: bool = False, hip_autograd_split_bf16: bool = False):
+                 hip_autograd_initq_modes: bool = False, hip_autograd_split_bf16: bool = False,
+                 hip_modes_split_bf16: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
@@ -883,6 +989,7 @@ class ImplicitDecoder(nn.Module):
         self.hip_initq_split_bf16 = bool(hip_initq_split_bf16)
         self.hip_autograd_initq_modes = bool(hip_autograd_initq_modes)
         self.hip_autograd_split_bf16 = bool(hip_autograd_split_bf16)
+        self.hip_modes_split_bf16 = bool(hip_modes_split_bf16)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -1099,12 +1206,13 @@ class ImplicitDecoder(nn.Module):
                                     initq_x3=self._packed_initq_x3 if initq_x3 else None)
                 return out
         workspace = cached(self._workspaces, need)
+        modes_x3 = bool(self.hip_modes_split_bf16 and self.mode in (1, 2, 4) and self.compute == "bf16x3")      # the opt-in
         with torch.no_grad():
             packed = self.packed_weights(x.device)
             if self.mode != 4:
                 return decode_features(x, packed, size, workspace=workspace, sin_mode=self.sin_mode,
-                                       compute=self.compute, mode=self.mode)
-            if self.compute != "f32":
+                                       compute=self.compute, mode=self.mode, modes_x3=modes_x3)
+            if self.compute != "f32" and not modes_x3:
                 raise ValueError("mode 4 runs in fp32 only")
             hu, wu = size
             hu, wu = int(hu), int(wu)
@@ -1116,5 +1224,6 @@ class ImplicitDecoder(nn.Module):
             out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
             for y0 in range(0, hu, chunk):
                 decode_features(x, packed, (hu, wu), out=out, workspace=workspace, rows=(y0, min(hu, y0 + chunk)),
-                                sin_mode=self.sin_mode, mode=4, head=self._packed_head, taps=taps)
+                                sin_mode=self.sin_mode, mode=4, head=self._packed_head, taps=taps,
+                                compute="bf16x3" if modes_x3 else "f32", modes_x3=modes_x3)
             return out

@@ -279,7 +279,8 @@ class _GraphReplay:
                 tuple((p.data_ptr(), p._version) for p in self.parameters()),
                 getattr(dec, "sin_mode", None), getattr(dec, "compute", None), getattr(dec, "mode", None),
                 getattr(enc, "hip_trunk_max_pixels", None), getattr(enc, "hip_winograd", None),
-                getattr(enc, "hip_split_bf16", None), getattr(enc, "hip_winograd4", None))
+                getattr(enc, "hip_split_bf16", None), getattr(enc, "hip_winograd4", None),
+                getattr(dec, "hip_modes_split_bf16", None))
 
     def _forward_graphed(self, x, size, bsize):
         key = self._graph_key(x, size)
@@ -354,6 +355,9 @@ class DIINN(nn.Module, _GraphReplay):
         if self.decoder.init_q and self.decoder.mode != 3 and self.decoder.hip_initq_modes:
             raise NotImplementedError("forward_sharded does not cover init_q=True with modes 1 and 2 (hip_initq_modes: the per-pixel "
                                       "chain has no band-sized form); use forward, which decodes in row chunks on one GPU")
+        if self.decoder.mode in (1, 2) and self.decoder.compute == "bf16x3" and self.decoder.hip_modes_split_bf16:
+            raise NotImplementedError("forward_sharded does not cover the split-bf16 arithmetic of modes 1 and 2 "
+                                      "(hip_modes_split_bf16: no window or tile form); use forward")
         if not dist.is_initialized() or dist.get_world_size(group) == 1:
             out = self._forward_eager(x, size, None)
             return out if gather_to is not None else (out, (0, int(size[0])))

@@ -286,6 +286,38 @@ int    diinn_decode_mode4(void* stream, const float* feat_dev, const float* pack
                           float* workspace_dev, float* taps_dev, float* out_dev,
                           int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
 
+/* ---- decoder modes 1, 2 and 4 in split-bf16 arithmetic (optional; inference, init_q=False, every sin_mode) -------------
+ * The arithmetic of DIINN_COMPUTE_BF16X3 for the decoders that mode covers not: every operand of a per-pixel 256 x 256 product
+ * carried as hi = bf16(v), lo = bf16(v - hi), the product formed as w_lo.q_hi + w_hi.q_lo + w_hi.q_hi on the bf16 MFMA with fp32
+ * accumulation, from section WLX of the SAME body image (diinn_pack_weights fills it for every mode: no new image).  Held to
+ * the fp32 contract, 1e-4 x max(1, max|ref|), on the reference fixtures (one documented exception: tests/test_decoder_modes_x3.py).
+ * DIINN_COMPUTE_BF16X3 through diinn_decode_ex / diinn_decode_mode4 keeps meaning what it meant; these are entry points of their own.
+ *
+ * MODES 1/2 (cf. DIINN_COMPUTE_F32_QONLY).  P and the per-cell modulation chain (diinn_cell_chain) stay fp32; the per-pixel
+ * kernel forms the three synthesis products alone (pieces q_hi, q_lo of a WLX k-step: 3 MFMAs, 2 loads) and reads k_i of the
+ * pixel's cell from slot i of P as the multiplier.  Layer 0, seeds, biases, sines and the 1x1 head in fp32.
+ * diinn_decode_qonly_x3_band: P_dev [B,H,W,1024] AFTER diinn_cell_chain -> out_dev[b, :, y0:y1, :] of a contiguous [B,3,Hu,Wu]
+ *   tensor (diinn_decode_band_ex's arguments and status codes).  One kernel.
+ * diinn_decode_qonly_x3: diinn_precompute_P (fp32), diinn_cell_chain, then the band (diinn_decode_ex's arguments).
+ *
+ * MODE 4 (cf. "decoder mode 4" above: the same images, rows, tap buffer and gather).  Layers 0..3 are DIINN_COMPUTE_BF16X3's for
+ * mode 3, bit for bit; the 27 tap values per pixel are formed in fp32 on the unsplit q_3 in the order of the fp32 tap form.
+ * diinn_decode_mode4_x3_band: diinn_decode_mode4_band's arguments and status codes.  Two kernels.
+ * diinn_decode_mode4_x3: the hoisted conv as DIINN_COMPUTE_BF16X3 runs it (split bf16 on maps of >= 32,768 cells, the fp32
+ *   Winograd form below), then the band (diinn_decode_mode4's arguments).
+ * Bands are BIT-IDENTICAL to the same rows of a whole-image decode.  Every argument is validated before the first launch; none
+ * of the four allocates or synchronises. */
+int    diinn_decode_qonly_x3_band(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
+                                  int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_qonly_x3(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev, float* out_dev,
+                             int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_mode4_x3_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
+                                  float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
+                                  int sin_mode);
+int    diinn_decode_mode4_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
+                             float* workspace_dev, float* taps_dev, float* out_dev,
+                             int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+
 /* ---- decoder init_q=True, mode 3: the per-pixel sine embedding (diinn.py:48-51,113-115) -----------------------
  * With init_q the synthesis input (rel_h, rel_w, ratio) first goes through first_layer = Conv2d(3, 576, 1) + sin, the
  * result multiplies the unfolded features of the pixel's LR cell, and Q.0 is 256 x 576 and reads the embedding:
