@@ -17,7 +17,7 @@ backward is library GEMMs over those (training.py).
 from __future__ import annotations
 
 import ctypes as C
-import math
+import importlib
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -25,10 +25,11 @@ import torch
 import torch.nn as nn
 
 from . import _native
+# the formula sheets live in sheets.py; tests, tools and the documents cite them under this module's name
+from .sheets import (HIDDEN, INV_2PI_F32, P_CHANNELS, axis_tables, initq_forward_reference,  # noqa: F401
+                     initq_modes_forward_reference, initq_planes_reference, modes_x3_forward_reference)
 
 IN_CHANNELS = 64
-HIDDEN = 256
-P_CHANNELS = 1024
 
 
 class SineAct(nn.Module):
@@ -117,9 +118,6 @@ def pack_initq(sd, prefix: str = "") -> torch.Tensor:
     return torch.from_numpy(packed)
 
 
-INV_2PI_F32 = float(np.float32(0.15915494309189533577))     # fp32(1 / (2 pi)): the factor the host packers multiply by
-
-
 def pack_initq_x3(sd, prefix: str = "") -> torch.Tensor:
     """``init_q=True`` in split-bf16 arithmetic: ``Q.0.0.weight`` [256,576,1,1] and ``Q.0.0.bias`` [256] -> the init_q SPLIT image
     (1-D fp32 CPU tensor; C ABI ``diinn_pack_initq_x3``: Q.0 / (2 pi) as hi / lo bf16 A operands in the piece order of the body
@@ -147,316 +145,6 @@ def initq_chunk_rows(b: int, wu: int, cap_bytes: int) -> int:
     return max(8, (int(cap_bytes) // per_row) // 8 * 8)
 
 
-def _split_bf16(v: torch.Tensor):
-    """hi = bf16(v), lo = bf16(v - hi) (round to nearest even), both back in v's dtype."""
-    hi = v.to(torch.bfloat16).to(v.dtype)
-    return hi, (v - hi).to(torch.bfloat16).to(v.dtype)
-
-
-def _mm_split(w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """The split-bf16 product of DESIGN.md 3.5: (w_lo . x_hi + w_hi . x_lo) + w_hi . x_hi, accumulated in the operands' dtype."""
-    wh, wl = _split_bf16(w)
-    xh, xl = _split_bf16(x)
-    return (wl @ xh + wh @ xl) + wh @ xh
-
-
-def _sin_rev(a: torch.Tensor) -> torch.Tensor:
-    """sin of an argument in revolutions, taken in float64 and rounded to the argument's dtype."""
-    return torch.sin(a.double() * (2.0 * math.pi)).to(a.dtype)
-
-
-def initq_planes_reference(sd, feat, size, arith: str = "split", prefix: str = "") -> torch.Tensor:
-    """The pixel planes of the split-bf16 ``init_q`` path, [B, Hu*Wu, 1280] (channels 1024.. in REVOLUTIONS), as
-    ``initq_planes_x3_kernel`` forms them: everything that feeds a sine divided by fp32(1/(2 pi)) in fp32, ``E`` by the kernel's
-    fp32 fma sequence (ratio, rel_w, rel_h) with the sine taken in float64, ``x' = E * X`` in fp32.  ``arith`` = "split": both GEMMs
-    as ``_mm_split`` in fp32 (torch matmuls, not the MFMA's summation order); "f64": the float64 products of the same fp32
-    operands, the yardstick of the planes test."""
-    if arith not in ("split", "f64"):
-        raise ValueError(f"arith must be 'split' or 'f64', got {arith!r}")
-    f32 = torch.float32
-    dev = feat.device
-
-    def get(name, shape):
-        t = sd[prefix + name]
-        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
-        return t.to(device=dev, dtype=f32).reshape(shape)
-
-    inv = torch.tensor(INV_2PI_F32, dtype=f32, device=dev)
-    hu, wu = int(size[0]), int(size[1])
-    x = feat.to(f32)
-    b, c, h, w = x.shape
-    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
-    iy, rel_h = axis_tables(h, hu, small)
-    ix, rel_w = axis_tables(w, wu, small)
-    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
-    n = hu * wu
-    relh = torch.from_numpy(rel_h).to(dev, f32)[:, None].expand(hu, wu).reshape(1, n)
-    relw = torch.from_numpy(rel_w).to(dev, f32)[None, :].expand(hu, wu).reshape(1, n)
-    ratio = torch.tensor(np.float32((h * w) / (hu * wu)), dtype=f32, device=dev)
-    fw, fb = get("first_layer.0.weight", (576, 3)) * inv, get("first_layer.0.bias", (576, 1)) * inv
-
-    def fma(a_, b_, c_):                                      # one rounding: the fp32 product is exact in float64
-        return (a_.double() * b_.double() + c_.double()).to(f32)
-
-    a = fma(fw[:, 2:3], ratio, fb)
-    a = fma(fw[:, 1:2], relw, a)
-    a = fma(fw[:, 0:1], relh, a)
-    e = _sin_rev(a)                                           # [576, n]
-    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
-    xc = unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)
-    xp = e[None] * xc                                         # [b, 576, n], fp32
-    wx = torch.cat([get("K.0.0.weight", (HIDDEN, 576))] +
-                   [get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, HIDDEN:] for i in (1, 2, 3)], 0)
-    bk = torch.cat([get(f"K.{i}.0.bias", (HIDDEN,)) for i in range(4)])[None, :, None]
-    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 576)) * inv, get("Q.0.0.bias", (HIDDEN, 1)) * inv
-    if arith == "f64":
-        pk = wx.double() @ xp.double() + bk.double()
-        a0 = q0w.double() @ e.double() + q0b.double()
-    else:
-        pk = _mm_split(wx, xp) + bk
-        a0 = _mm_split(q0w, e) + q0b
-    return torch.cat([pk, a0[None].expand(b, HIDDEN, n)], 1).transpose(1, 2).contiguous()
-
-
-def _initq_forward_split(sd, feat, size, dtype, prefix: str) -> torch.Tensor:
-    """``initq_forward_reference(..., split_bf16=True)``: the three split stages -- both planes GEMMs (``initq_planes_reference``),
-    and the two 256 x 256 products of layers 1..3 -- with every sine taken of revolutions in float64."""
-    dev = feat.device
-
-    def get(name, shape):
-        t = sd[prefix + name]
-        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
-        return t.to(device=dev, dtype=torch.float32).reshape(shape)
-
-    inv = torch.tensor(INV_2PI_F32, dtype=torch.float32, device=dev)
-    hu, wu = int(size[0]), int(size[1])
-    pix = initq_planes_reference(sd, feat, size, "split", prefix).transpose(1, 2)      # [b, 1280, n]
-    b = pix.shape[0]
-    q = torch.relu(pix[:, :HIDDEN]) * _sin_rev(pix[:, P_CHANNELS:])
-    for i in (1, 2, 3):
-        k = torch.relu(_mm_split(get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, :HIDDEN], q) + pix[:, HIDDEN * i:HIDDEN * (i + 1)])
-        s = _mm_split(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) * inv, q) + get(f"Q.{i}.0.bias", (HIDDEN, 1)) * inv
-        q = k * _sin_rev(s)
-    out = get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))
-    return out.reshape(b, 3, hu, wu).to(dtype)
-
-
-def initq_forward_reference(sd, feat, size, dtype=torch.float64, prefix: str = "", planes: Optional[list] = None,
-                            split_bf16: bool = False) -> torch.Tensor:
-    """The formula sheet of the ``init_q=True``, mode-3 path in tensor algebra, in the RESTRUCTURED form the kernels run
-    (any device, any float dtype; the tests' one restatement, as ``encoder_training.rdb_backward_reference`` is for its path).
-
-    Reference (diinn.py:113-115,132-139,163-173), per HR pixel with LR cell (iy, ix)::
-
-        E  = sin(Fw . (rel_h, rel_w, ratio) + Fb)                576 values      first_layer
-        x' = E * X[:, iy, ix]                                     X = unfold3x3(feat), index c * 9 + 3 ky + kx, zero padded
-        k0 = relu(K0 . x' + bK0);            q0 = k0 * sin(Q0 . E + bQ0)
-        k_i = relu(K_i . [q_{i-1}; x'] + bK_i);  q_i = k_i * sin(Q_i . q_{i-1} + bQ_i),  i = 1..3;   out = L . q3 + bL
-
-    Restructured: the feature columns of K_0..3 are stacked into Wx [1024,576], so ``PIX[0:1024] = Wx . x' + bK`` and
-    ``PIX[1024:1280] = Q0 . E + bQ0`` are two GEMMs per pixel (``initq_planes_kernel``), and the layers read their seeds
-    there: ``k_i = relu(K_i[:, :256] . q_{i-1} + PIX[256 i : 256 i + 256])`` (``decode_kernel<SIN | DECODE_INITQ>``).  E depends on the
-    pixel only, not on the batch item.  Coordinates: the fp32 tables of ``axis_tables`` (the reference computes them in fp32
-    whatever the module's dtype); ``ratio`` is the Python double rounded to ``dtype``, as ``x.new_tensor`` does.
-    ``planes`` (a list): receives every layer's (k_i, s_i), each [B,256,Hu*Wu] -- what the training forward saves.
-    ``split_bf16`` (with ``dtype=torch.float32``): the EMULATION of the split-bf16 path (``hip_initq_split_bf16``) -- the two planes
-    GEMMs, the ``Q0 . E`` sine argument and layers 1..3 with every operand carried as hi + lo bf16 and a product formed as
-    ``(w_lo.x_hi + w_hi.x_lo) + w_hi.x_hi`` in fp32 torch matmuls; sine arguments in revolutions (weights and biases divided by
-    fp32(1/(2 pi)) in fp32 before the split, as the images hold them), the sines taken in float64."""
-    if split_bf16:
-        if dtype != torch.float32 or planes is not None:
-            raise ValueError("split_bf16=True emulates fp32 accumulation: dtype=torch.float32, and no planes")
-        return _initq_forward_split(sd, feat, size, dtype, prefix)
-
-    def get(name, shape):
-        t = sd[prefix + name]
-        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
-        return t.to(device=feat.device, dtype=dtype).reshape(shape)
-
-    hu, wu = int(size[0]), int(size[1])
-    x = feat.to(dtype)
-    b, c, h, w = x.shape
-    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
-    iy, rel_h = axis_tables(h, hu, small)
-    ix, rel_w = axis_tables(w, wu, small)
-    dev = feat.device
-    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
-    syn = torch.empty((3, hu, wu), dtype=dtype, device=dev)
-    syn[0] = torch.from_numpy(rel_h).to(dev, dtype)[:, None]
-    syn[1] = torch.from_numpy(rel_w).to(dev, dtype)[None, :]
-    syn[2] = torch.tensor((h * w) / (hu * wu), dtype=dtype, device=dev)
-    n = hu * wu
-    e = torch.sin(get("first_layer.0.weight", (576, 3)) @ syn.reshape(3, n) + get("first_layer.0.bias", (576, 1)))   # [576, n]
-    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
-    xc = unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)
-    xp = e[None] * xc                                                                                              # [b, 576, n]
-    wx = torch.cat([get("K.0.0.weight", (HIDDEN, 576))] +
-                   [get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, HIDDEN:] for i in (1, 2, 3)], 0)          # [1024, 576]
-    bk = torch.cat([get(f"K.{i}.0.bias", (HIDDEN,)) for i in range(4)])[None, :, None]
-    pix = wx @ xp + bk                                                                                             # [b, 1024, n]
-    a0 = get("Q.0.0.weight", (HIDDEN, 576)) @ e + get("Q.0.0.bias", (HIDDEN, 1))                                   # [256, n]
-    q = torch.relu(pix[:, :HIDDEN]) * torch.sin(a0)[None]
-    if planes is not None:
-        planes.append((torch.relu(pix[:, :HIDDEN]), a0[None].expand(b, HIDDEN, n)))
-    for i in (1, 2, 3):
-        k = torch.relu(get(f"K.{i}.0.weight", (HIDDEN, HIDDEN + 576))[:, :HIDDEN] @ q + pix[:, HIDDEN * i:HIDDEN * (i + 1)])
-        s = get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1))
-        if planes is not None:
-            planes.append((k, s))
-        q = k * torch.sin(s)
-    out = get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))
-    return out.reshape(b, 3, hu, wu)
-
-
-def initq_modes_forward_reference(sd, feat, size, mode: int, dtype=torch.float64, prefix: str = "") -> torch.Tensor:
-    """The formula sheet of ``init_q=True`` with modes 1, 2 and 4 in tensor algebra, in the RESTRUCTURED form the kernels run (any
-    device, any float dtype), beside ``initq_forward_reference`` (mode 3).
-
-    Reference (diinn.py:112-147), per HR pixel: ``E`` and ``x' = E * X[cell]`` as for mode 3, ``k0 = relu(K0 . x' + bK0)``,
-    ``q0 = k0 * sin(Q0 . E + bQ0)``, ``q_i = k_i * sin(Q_i . q_{i-1} + bQ_i)`` and
-
-        mode 1   k_i = relu(K_i . k_{i-1} + bK_i)            K_i [256,256]
-        mode 2   k_i = relu(K_i . [k_{i-1}; x'] + bK_i)      K_i [256,832]
-        mode 4   k_i = relu(K_i . [q_{i-1}; x'] + bK_i),     then Conv2d(256, 3, 3, padding=1, 'reflect') over the HR grid
-
-    Restructured, with the pixel record ``PIX`` of ``initq_forward_reference``:
-
-        modes 1/2  PIX[0:256] = K0 . x' + bK0, PIX[1024:1280] = Q0 . E + bQ0 (mode 1: these 512 rows are the whole GEMM,
-                   ``initq_planes_kernel<SIN | INITQ_ROWS512>``); PIX[256 i : 256 i + 256] = K_i[:, 256:] . x' + bK_i (mode 2) or the seed
-                   is bK_i itself (mode 1).  The chain ``k_i = relu(K_i[:, :256] . k_{i-1} + seed_i)`` runs per pixel on its own
-                   (``pixel_chain_kernel``) and the layers read it as the multiplier (``decode_kernel<SIN | DECODE_INITQ, KPART=false>``).
-        mode 4     mode 3's layers from the 1280-row record, the head as 27 tap values per pixel, T[3 ky + kx][c] =
-                   Lw[c, :, ky, kx] . q3 (``decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS>``), and the reflect-padded 9-point gather
-                   over the image (``head3x3_reflect_kernel``).
-    Coordinates and ``ratio`` as in ``initq_forward_reference``."""
-    if mode not in (1, 2, 4):
-        raise ValueError(f"initq_modes_forward_reference states modes 1, 2 and 4 (mode 3: initq_forward_reference), got {mode}")
-
-    def get(name, shape):
-        t = sd[prefix + name]
-        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
-        return t.to(device=feat.device, dtype=dtype).reshape(shape)
-
-    hu, wu = int(size[0]), int(size[1])
-    x = feat.to(dtype)
-    b, c, h, w = x.shape
-    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
-    iy, rel_h = axis_tables(h, hu, small)
-    ix, rel_w = axis_tables(w, wu, small)
-    dev = feat.device
-    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
-    syn = torch.empty((3, hu, wu), dtype=dtype, device=dev)
-    syn[0] = torch.from_numpy(rel_h).to(dev, dtype)[:, None]
-    syn[1] = torch.from_numpy(rel_w).to(dev, dtype)[None, :]
-    syn[2] = torch.tensor((h * w) / (hu * wu), dtype=dtype, device=dev)
-    n = hu * wu
-    e = torch.sin(get("first_layer.0.weight", (576, 3)) @ syn.reshape(3, n) + get("first_layer.0.bias", (576, 1)))   # [576, n]
-    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
-    xp = e[None] * unf[:, :, iy_t][:, :, :, ix_t].reshape(b, c * 9, n)                                               # [b, 576, n]
-    kin = HIDDEN if mode == 1 else HIDDEN + 576
-    kw = [get(f"K.{i}.0.weight", (HIDDEN, kin)) for i in (1, 2, 3)]
-    bk = [get(f"K.{i}.0.bias", (HIDDEN, 1)) for i in range(4)]
-    k = torch.relu(get("K.0.0.weight", (HIDDEN, 576)) @ xp + bk[0])                                                 # PIX[0:256]
-    q = k * torch.sin(get("Q.0.0.weight", (HIDDEN, 576)) @ e + get("Q.0.0.bias", (HIDDEN, 1)))[None]              # PIX[1024:1280]
-    for i in (1, 2, 3):
-        seed = bk[i] if mode == 1 else kw[i - 1][:, HIDDEN:] @ xp + bk[i]                                         # PIX[256 i : 256 i + 256]
-        k = torch.relu(kw[i - 1][:, :HIDDEN] @ (q if mode == 4 else k) + seed)
-        q = k * torch.sin(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) @ q + get(f"Q.{i}.0.bias", (HIDDEN, 1)))
-    if mode != 4:
-        return (get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))).reshape(b, 3, hu, wu)
-    lw = get("last_layer.weight", (3, HIDDEN, 3, 3))
-    taps = torch.einsum("chyx,bhn->byxcn", lw, q).reshape(b, 3, 3, 3, hu, wu)                                     # T[ky][kx][c] per pixel
-    ry = torch.arange(-1, hu + 1, device=dev).abs()
-    ry = torch.where(ry >= hu, 2 * (hu - 1) - ry, ry)                                                              # 'reflect': -1 -> 1, Hu -> Hu - 2
-    rx = torch.arange(-1, wu + 1, device=dev).abs()
-    rx = torch.where(rx >= wu, 2 * (wu - 1) - rx, rx)
-    out = get("last_layer.bias", (1, 3, 1, 1)).expand(b, 3, hu, wu).clone()
-    for ky in range(3):
-        for kx in range(3):
-            out = out + taps[:, ky, kx][:, :, ry[ky:ky + hu]][:, :, :, rx[kx:kx + wu]]
-    return out
-
-
-def modes_x3_forward_reference(sd, feat, size, mode: int, prefix: str = "") -> torch.Tensor:
-    """The EMULATION sheet of the split-bf16 arithmetic of decoder modes 1, 2 and 4 with ``init_q=False``
-    (``decode_features(..., compute="bf16x3", modes_x3=True)``), in fp32 torch algebra on any device; beside
-    ``initq_forward_reference(..., split_bf16=True)``, which states mode 3 with ``init_q=True``.
-
-    What is split: the three synthesis products ``Q_i . q_{i-1}``, i = 1..3, of every mode, and for mode 4 the three modulation
-    products ``K_i[:, :256] . q_{i-1}`` as well.  Every operand of such a product is carried as hi = bf16(v), lo = bf16(v - hi) and
-    the product formed as ``(w_lo.q_hi + w_hi.q_lo) + w_hi.q_hi`` in fp32 (``_mm_split``: torch matmuls, not the MFMA's summation
-    order).  The synthesis branch runs in REVOLUTIONS: Q_0..3 and their biases are multiplied by fp32(1/(2 pi)) in fp32 before the
-    split, as the body image holds them, and every sine is taken of revolutions in float64 (``_sin_rev``).
-
-    What stays fp32: the hoisted conv ``P = Wx . unfold3x3(feat) + bK`` (mode 1: ``P_i = bK_i`` for i >= 1), the per-cell
-    modulation chain of modes 1/2, ``k_0 = relu(P_0)``, ``k_i = relu(K_i[:, :256] . k_{i-1} + P_i)`` (``cell_chain_kernel``), layer
-    0 with the kernels' fma sequence ``a = fma(Q0_h, rel_h, fma(Q0_w, rel_w, fma(Q0_r, ratio, bQ0)))``, the seeds and biases, and
-    the head on the unsplit ``q_3``: ``L . q_3 + bL`` (modes 1/2), or the 27 tap values per pixel and the reflect-padded 9-point
-    gather (mode 4)."""
-    if mode not in (1, 2, 4):
-        raise ValueError(f"modes_x3_forward_reference states modes 1, 2 and 4, got {mode}")
-    f32 = torch.float32
-    dev = feat.device
-
-    def get(name, shape):
-        t = sd[prefix + name]
-        t = t.detach() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
-        return t.to(device=dev, dtype=f32).reshape(shape)
-
-    def fma(a_, b_, c_):                                      # one rounding: the fp32 product is exact in float64
-        return (a_.double() * b_.double() + c_.double()).to(f32)
-
-    inv = torch.tensor(INV_2PI_F32, dtype=f32, device=dev)
-    hu, wu = int(size[0]), int(size[1])
-    x = feat.to(f32)
-    b, c, h, w = x.shape
-    n = hu * wu
-    small = bool(_native.load().diinn_uses_small_output_kernel(hu, wu))
-    iy, rel_h = axis_tables(h, hu, small)
-    ix, rel_w = axis_tables(w, wu, small)
-    iy_t, ix_t = torch.from_numpy(iy.astype(np.int64)).to(dev), torch.from_numpy(ix.astype(np.int64)).to(dev)
-    relh = torch.from_numpy(rel_h).to(dev, f32)[:, None].expand(hu, wu).reshape(1, n)
-    relw = torch.from_numpy(rel_w).to(dev, f32)[None, :].expand(hu, wu).reshape(1, n)
-    ratio = torch.tensor(np.float32((h * w) / (hu * wu)), dtype=f32, device=dev)
-    kin = HIDDEN if mode == 1 else HIDDEN + 576
-    kw = [get(f"K.{i}.0.weight", (HIDDEN, kin)) for i in (1, 2, 3)]
-    bk = [get(f"K.{i}.0.bias", (HIDDEN, 1)) for i in range(4)]
-    unf = torch.nn.functional.unfold(x, 3, padding=1)                                   # [b, 576, h*w], fp32
-    P = [get("K.0.0.weight", (HIDDEN, 576)) @ unf + bk[0]]
-    for i in (1, 2, 3):
-        P.append(bk[i].expand(b, HIDDEN, h * w) if mode == 1 else kw[i - 1][:, HIDDEN:] @ unf + bk[i])
-    cell = (iy_t[:, None] * w + ix_t[None, :]).reshape(n)                               # LR cell of every HR pixel
-    if mode != 4:                                                                       # the per-cell chain, fp32
-        kc = [torch.relu(P[0])]
-        for i in (1, 2, 3):
-            kc.append(torch.relu(kw[i - 1][:, :HIDDEN] @ kc[-1] + P[i]))
-    q0w, q0b = get("Q.0.0.weight", (HIDDEN, 3)) * inv, get("Q.0.0.bias", (HIDDEN, 1)) * inv
-    a = fma(q0w[:, 2:3], ratio, q0b)
-    a = fma(q0w[:, 1:2], relw, a)
-    a = fma(q0w[:, 0:1], relh, a)
-    q = torch.relu(P[0][:, :, cell]) * _sin_rev(a)[None]                                # [b, 256, n]
-    for i in (1, 2, 3):
-        s = _mm_split(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) * inv, q) + get(f"Q.{i}.0.bias", (HIDDEN, 1)) * inv
-        if mode == 4:
-            k = torch.relu(_mm_split(kw[i - 1][:, :HIDDEN], q) + P[i][:, :, cell])
-        else:
-            k = kc[i][:, :, cell]
-        q = k * _sin_rev(s)
-    if mode != 4:
-        return (get("last_layer.weight", (3, HIDDEN)) @ q + get("last_layer.bias", (3, 1))).reshape(b, 3, hu, wu)
-    lw = get("last_layer.weight", (3, HIDDEN, 3, 3))
-    taps = torch.einsum("chyx,bhn->byxcn", lw, q).reshape(b, 3, 3, 3, hu, wu)           # T[ky][kx][c] per pixel
-    ry = torch.arange(-1, hu + 1, device=dev).abs()
-    ry = torch.where(ry >= hu, 2 * (hu - 1) - ry, ry)                                    # 'reflect': -1 -> 1, Hu -> Hu - 2
-    rx = torch.arange(-1, wu + 1, device=dev).abs()
-    rx = torch.where(rx >= wu, 2 * (wu - 1) - rx, rx)
-    out = get("last_layer.bias", (1, 3, 1, 1)).expand(b, 3, hu, wu).clone()
-    for ky in range(3):
-        for kx in range(3):
-            out = out + taps[:, ky, kx][:, :, ry[ky:ky + hu]][:, :, :, rx[kx:kx + wu]]
-    return out
-
-
 def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     """((ty0, ty1), (r0, r1)): the HR rows whose tap values mode 4 needs for output rows [y0,y1) (one more row each way,
     clipped to the image) and the LR rows those read (C ABI ``diinn_mode4_rows``)."""
@@ -465,17 +153,6 @@ def mode4_rows(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[Tuple[int, i
     _native.check(lib.diinn_mode4_rows(h, hu, wu, y0, y1, C.byref(a), C.byref(b), C.byref(r0), C.byref(r1)),
                   "diinn_mode4_rows")
     return (a.value, b.value), (r0.value, r1.value)
-
-
-def axis_tables(n_in: int, n_out: int, small_output: bool = False) -> Tuple[np.ndarray, np.ndarray]:
-    """Host tables (idx int32, rel fp32) from the C ABI ``diinn_make_axis_tables``."""
-    lib = _native.load()
-    idx = np.empty(n_out, np.int32)
-    rel = np.empty(n_out, np.float32)
-    st = lib.diinn_make_axis_tables(n_in, n_out, int(small_output),
-                                    idx.ctypes.data_as(_native._i32), _native.fptr(rel))
-    _native.check(st, "diinn_make_axis_tables")
-    return idx, rel
 
 
 def lr_rows_for_band(h: int, hu: int, wu: int, y0: int, y1: int) -> Tuple[int, int]:
@@ -495,6 +172,62 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
         raise RuntimeError(
             f"diinn_amd: {what} must live on a ROCm GPU (got device {t.device}); the MI355X decode "
             f"path has no CPU implementation")
+
+
+def require_2x2(hu: int, wu: int) -> None:
+    """Mode 4's one size rule (nn.Conv2d's 'reflect' padding asks the same)."""
+    if hu < 2 or wu < 2:
+        raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+
+
+def _checked_feat(feat: torch.Tensor):
+    """(``feat`` contiguous, (B, H, W)) of fp32 encoder features [B,64,H,W]."""
+    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
+        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
+    b, _, h, w = feat.shape
+    return feat.contiguous(), (b, h, w)
+
+
+def _checked_out(out: Optional[torch.Tensor], shape, device, what: str = "out", dims: str = "[B,3,Hu,Wu]", owner: str = "feat"):
+    """``out`` if it is a contiguous fp32 tensor of ``shape`` on ``device`` (a new one if None)."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what} must be a contiguous fp32 {dims} tensor on {owner}'s device")
+    return out
+
+
+def _checked_buffer(buf: Optional[torch.Tensor], need_bytes: int, device, what: str, fp32_required: bool, owner: str = "feat",
+                    unit: str = "bytes"):
+    """``buf`` if it is a contiguous buffer of at least ``need_bytes`` on ``device`` (a new fp32 one if None).  ``fp32_required``:
+    ``pix`` and ``p_win`` must be fp32; ``workspace`` and ``taps`` are taken by their size alone."""
+    if buf is None:
+        return torch.empty(need_bytes // 4, dtype=torch.float32, device=device)
+    if buf.numel() * buf.element_size() < need_bytes or (fp32_required and buf.dtype != torch.float32) or not buf.is_contiguous() \
+            or buf.device != device:
+        raise ValueError(f"{what} must be a contiguous {'fp32 ' if fp32_required else ''}buffer of >= "
+                         f"{need_bytes if unit == 'bytes' else need_bytes // 4} {unit} on {owner}'s device")
+    return buf
+
+
+def _checked_head(head: Optional[torch.Tensor], hu: int, wu: int) -> None:
+    if head is None:
+        raise ValueError("mode 4 needs its 3x3 head image: head=pack_head3x3(state_dict) on feat's device")
+    _require_cuda(head, "head image")
+    require_2x2(hu, wu)
+
+
+def _not_a_band(y0: int, y1: int, hu: int) -> ValueError:
+    return ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
+
+
+def _launch(name: str, device, *args) -> None:
+    """Enqueue the library's ``name`` on the current stream of ``device``: tensors go as their addresses, integers as they are."""
+    lib = _native.load()
+    with torch.cuda.device(device):
+        st = getattr(lib, name)(C.c_void_p(torch.cuda.current_stream().cuda_stream),
+                                *[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args])
+    _native.check(st, name)
 
 
 def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
@@ -541,92 +274,43 @@ def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int
         raise ValueError("initq_x3 goes with initq (an init_q=True decoder)")
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
-    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
-        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
+    feat, (b, h, w) = _checked_feat(feat)
     hu, wu = size  # same unpack as the reference (diinn.py:96): raises unless len(size) == 2
     hu, wu = int(hu), int(wu)
-    feat = feat.contiguous()
-    b, _, h, w = feat.shape
     y0, y1 = (0, hu) if rows is None else (int(rows[0]), int(rows[1]))
-    if out is None:
-        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
-    else:
-        if out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
-                or out.device != feat.device:
-            raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
+    dev = feat.device
+    out = _checked_out(out, (b, 3, hu, wu), dev)
+    geometry = (b, h, w, hu, wu, y0, y1, int(sin_mode))
     if initq is not None:
         _require_cuda(initq, "init_q image")
         pneed = lib.diinn_initq_pix_bytes(b, wu, y1 - y0)
         if pneed == 0 or y0 < 0 or y1 > hu:
-            raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
-        if pix is None:
-            pix = torch.empty(pneed // 4, dtype=torch.float32, device=feat.device)
-        elif pix.numel() * pix.element_size() < pneed or pix.dtype != torch.float32 or not pix.is_contiguous() \
-                or pix.device != feat.device:
-            raise ValueError(f"pix must be a contiguous fp32 buffer of >= {pneed} bytes on feat's device")
+            raise _not_a_band(y0, y1, hu)
+        pix = _checked_buffer(pix, pneed, dev, "pix", True)
         if initq_x3 is not None:
             _require_cuda(initq_x3, "init_q split image")
-            with torch.cuda.device(feat.device):
-                stream = torch.cuda.current_stream().cuda_stream
-                st = lib.diinn_decode_initq_x3(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                               C.c_void_p(initq.data_ptr()), C.c_void_p(initq_x3.data_ptr()),
-                                               C.c_void_p(pix.data_ptr()), C.c_void_p(out.data_ptr()),
-                                               b, h, w, hu, wu, y0, y1, int(sin_mode))
-            _native.check(st, "diinn_decode_initq_x3")
-            return out
-        with torch.cuda.device(feat.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            st = lib.diinn_decode_initq(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                        C.c_void_p(initq.data_ptr()), C.c_void_p(pix.data_ptr()), C.c_void_p(out.data_ptr()),
-                                        b, h, w, hu, wu, y0, y1, int(sin_mode))
-        _native.check(st, "diinn_decode_initq")
+            _launch("diinn_decode_initq_x3", dev, feat, packed, initq, initq_x3, pix, out, *geometry)
+        else:
+            _launch("diinn_decode_initq", dev, feat, packed, initq, pix, out, *geometry)
         return out
-    need = lib.diinn_workspace_bytes(b, h, w)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
-    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous() \
-            or workspace.device != feat.device:
-        raise ValueError(f"workspace must be a contiguous buffer of >= {need} bytes on feat's device")
+    workspace = _checked_buffer(workspace, lib.diinn_workspace_bytes(b, h, w), dev, "workspace", False)
     if mode not in (1, 2, 3, 4):
         raise NotImplementedError(f"mode {mode}: the HIP path covers modes 1-4")
     x3 = bool(modes_x3) and mode != 3 and compute == "bf16x3"     # the opt-in: split bf16 for modes 1, 2 and 4
     if mode != 3 and compute != "f32" and not x3:
         raise ValueError("modes 1, 2 and 4 run in fp32 only")
     if mode == 4:
-        if head is None:
-            raise ValueError("mode 4 needs its 3x3 head image: head=pack_head3x3(state_dict) on feat's device")
-        _require_cuda(head, "head image")
-        if hu < 2 or wu < 2:
-            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+        _checked_head(head, hu, wu)
         tneed = lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1)
         if tneed == 0:
-            raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
-        if taps is None:
-            taps = torch.empty(tneed // 4, dtype=torch.float32, device=feat.device)
-        elif taps.numel() * taps.element_size() < tneed or not taps.is_contiguous() or taps.device != feat.device:
-            raise ValueError(f"taps must be a contiguous buffer of >= {tneed} bytes on feat's device")
-        name = "diinn_decode_mode4_x3" if x3 else "diinn_decode_mode4"
-        with torch.cuda.device(feat.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            st = getattr(lib, name)(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                    C.c_void_p(head.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                    C.c_void_p(taps.data_ptr()), C.c_void_p(out.data_ptr()),
-                                    b, h, w, hu, wu, y0, y1, int(sin_mode))
-        _native.check(st, name)
-        return out
-    comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
-    with torch.cuda.device(feat.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        if x3:
-            st = lib.diinn_decode_qonly_x3(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                           C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()),
-                                           b, h, w, hu, wu, y0, y1, int(sin_mode))
-            _native.check(st, "diinn_decode_qonly_x3")
-            return out
-        st = lib.diinn_decode_ex(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                 C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()),
-                                 b, h, w, hu, wu, y0, y1, int(sin_mode), comp)
-    _native.check(st, "diinn_decode_ex")
+            raise _not_a_band(y0, y1, hu)
+        taps = _checked_buffer(taps, tneed, dev, "taps", False)
+        _launch("diinn_decode_mode4_x3" if x3 else "diinn_decode_mode4", dev, feat, packed, head, workspace, taps, out, *geometry)
+    elif x3:
+        _launch("diinn_decode_qonly_x3", dev, feat, packed, workspace, out, *geometry)
+    else:
+        _launch("diinn_decode_ex", dev, feat, packed, workspace, out, *geometry,
+                _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY)
     return out
 
 
@@ -653,49 +337,26 @@ def decode_features_initq(feat: torch.Tensor, packed: torch.Tensor, initq: torch
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
     _require_cuda(initq, "init_q image")
-    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
-        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
+    feat, (b, h, w) = _checked_feat(feat)
     hu, wu = size
     hu, wu = int(hu), int(wu)
-    feat = feat.contiguous()
-    b, _, h, w = feat.shape
     y0, y1 = (0, hu) if rows is None else (int(rows[0]), int(rows[1]))
+    dev = feat.device
     if mode == 4:
-        if head is None:
-            raise ValueError("mode 4 needs its 3x3 head image: head=pack_head3x3(state_dict) on feat's device")
-        _require_cuda(head, "head image")
-        if hu < 2 or wu < 2:
-            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
-    if out is None:
-        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
-    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feat.device:
-        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
+        _checked_head(head, hu, wu)
+    out = _checked_out(out, (b, 3, hu, wu), dev)
     pneed = lib.diinn_initq_mode4_pix_bytes(b, hu, wu, y0, y1) if mode == 4 else \
         (lib.diinn_initq_pix_bytes(b, wu, y1 - y0) if 0 <= y0 < y1 <= hu else 0)
     if pneed == 0:
-        raise ValueError(f"rows {(y0, y1)} are not a band of an image of {hu} rows")
-    if pix is None:
-        pix = torch.empty(pneed // 4, dtype=torch.float32, device=feat.device)
-    elif pix.numel() * pix.element_size() < pneed or pix.dtype != torch.float32 or not pix.is_contiguous() \
-            or pix.device != feat.device:
-        raise ValueError(f"pix must be a contiguous fp32 buffer of >= {pneed} bytes on feat's device")
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(feat.device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if mode == 4:
-            tneed = lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1)
-            if taps is None:
-                taps = torch.empty(tneed // 4, dtype=torch.float32, device=feat.device)
-            elif taps.numel() * taps.element_size() < tneed or not taps.is_contiguous() or taps.device != feat.device:
-                raise ValueError(f"taps must be a contiguous buffer of >= {tneed} bytes on feat's device")
-            name = "diinn_decode_initq_mode4"
-            st = lib.diinn_decode_initq_mode4(stream, ptr(feat), ptr(packed), ptr(initq), ptr(head), ptr(pix), ptr(taps), ptr(out),
-                                              b, h, w, hu, wu, y0, y1, int(sin_mode))
-        else:
-            name = "diinn_decode_initq_mode1" if mode == 1 and planes_rows != 1280 else "diinn_decode_initq_mode2"
-            st = getattr(lib, name)(stream, ptr(feat), ptr(packed), ptr(initq), ptr(pix), ptr(out),
-                                    b, h, w, hu, wu, y0, y1, int(sin_mode))
-    _native.check(st, name)
+        raise _not_a_band(y0, y1, hu)
+    pix = _checked_buffer(pix, pneed, dev, "pix", True)
+    geometry = (b, h, w, hu, wu, y0, y1, int(sin_mode))
+    if mode == 4:
+        taps = _checked_buffer(taps, lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1), dev, "taps", False)
+        _launch("diinn_decode_initq_mode4", dev, feat, packed, initq, head, pix, taps, out, *geometry)
+    else:
+        _launch("diinn_decode_initq_mode1" if mode == 1 and planes_rows != 1280 else "diinn_decode_initq_mode2", dev,
+                feat, packed, initq, pix, out, *geometry)
     return out
 
 
@@ -718,7 +379,6 @@ def decode_window(feat_win: torch.Tensor, feat_row0: int, full_h: int, packed: t
     cover the band's cells plus the 3x3 halo (``window_rows``).  ``p_win`` is a workspace of at least
     B*p_rows*W*1024 floats and ``out_win`` [B,3,y1-y0,Wu] the band of the output (both allocated if None).
     Bit-identical to the same rows of ``decode_features`` on the full map.  C ABI: ``diinn_decode_win``."""
-    lib = _native.load()
     _require_cuda(feat_win, "feat_win")
     _require_cuda(packed, "packed weights")
     if feat_win.dtype != torch.float32 or feat_win.dim() != 4 or feat_win.shape[1] != IN_CHANNELS \
@@ -729,32 +389,23 @@ def decode_window(feat_win: torch.Tensor, feat_row0: int, full_h: int, packed: t
     hu, wu = int(hu), int(wu)
     y0, y1 = int(rows[0]), int(rows[1])
     b, _, fr, w = feat_win.shape
+    dev = feat_win.device
     (_, _), (r0, rn) = window_rows(int(full_h), hu, wu, y0, y1)
-    need = b * rn * w * P_CHANNELS
-    if p_win is None:
-        p_win = torch.empty(need, dtype=torch.float32, device=feat_win.device)
-    elif p_win.numel() < need or p_win.dtype != torch.float32 or not p_win.is_contiguous() \
-            or p_win.device != feat_win.device:
-        raise ValueError(f"p_win must be a contiguous fp32 buffer of >= {need} floats on feat_win's device")
-    if out_win is None:
-        out_win = torch.empty((b, 3, y1 - y0, wu), dtype=torch.float32, device=feat_win.device)
-    elif out_win.shape != (b, 3, y1 - y0, wu) or out_win.dtype != torch.float32 or not out_win.is_contiguous() \
-            or out_win.device != feat_win.device:
-        raise ValueError("out_win must be a contiguous fp32 [B,3,y1-y0,Wu] tensor on feat_win's device")
+    p_win = _checked_buffer(p_win, b * rn * w * P_CHANNELS * 4, dev, "p_win", True, owner="feat_win", unit="floats")
+    out_win = _checked_out(out_win, (b, 3, y1 - y0, wu), dev, "out_win", "[B,3,y1-y0,Wu]", "feat_win")
+    _launch("diinn_decode_win", dev, feat_win, int(feat_row0), fr, packed, p_win, r0, rn, out_win, y0, y1 - y0,
+            b, int(full_h), w, hu, wu, y0, y1, int(sin_mode), _window_compute(mode, compute))
+    return out_win
+
+
+def _window_compute(mode: int, compute: str) -> int:
+    """The library's compute code of a window or tile decode: modes 1-3, modes 1 and 2 in fp32 only."""
     if mode not in (1, 2, 3):
         raise NotImplementedError(f"mode {mode}: windows and tiles cover modes 1-3 (mode 4's 3x3 head reads its "
                                   f"neighbours' rows and columns: decode it with decode_features(rows=...))")
     if mode != 3 and compute != "f32":
         raise ValueError("modes 1 and 2 run in fp32 only")
-    comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
-    with torch.cuda.device(feat_win.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        st = lib.diinn_decode_win(C.c_void_p(stream), C.c_void_p(feat_win.data_ptr()), int(feat_row0), fr,
-                                  C.c_void_p(packed.data_ptr()), C.c_void_p(p_win.data_ptr()), r0, rn,
-                                  C.c_void_p(out_win.data_ptr()), y0, y1 - y0,
-                                  b, int(full_h), w, hu, wu, y0, y1, int(sin_mode), comp)
-    _native.check(st, "diinn_decode_win")
-    return out_win
+    return _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
 
 
 def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: torch.Tensor, size: Sequence[int],
@@ -768,7 +419,6 @@ def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: 
 
     ``mode`` 1 / 2 (fp32 only): ``p_win`` must already hold the per-cell modulation chain in slots 1..3 of the rows the
     tile reads (``diinn_cell_chain`` after ``diinn_precompute_P_win``)."""
-    lib = _native.load()
     _require_cuda(p_win, "p_win")
     _require_cuda(packed, "packed weights")
     b, h, w = (int(v) for v in shape)
@@ -781,20 +431,8 @@ def decode_tile(p_win: torch.Tensor, p_row0: int, shape: Sequence[int], packed: 
         raise ValueError("out must have unit stride along x")
     if p_win.dtype != torch.float32 or not p_win.is_contiguous() or p_win.numel() % (b * w * P_CHANNELS):
         raise ValueError("p_win must be a contiguous fp32 buffer of B * rows * W * 1024 floats")
-    p_rows = p_win.numel() // (b * w * P_CHANNELS)
-    if mode not in (1, 2, 3):
-        raise NotImplementedError(f"mode {mode}: windows and tiles cover modes 1-3 (mode 4's 3x3 head reads its "
-                                  f"neighbours' rows and columns: decode it with decode_features(rows=...))")
-    if mode != 3 and compute != "f32":
-        raise ValueError("modes 1 and 2 run in fp32 only")
-    comp = _native.COMPUTE[compute] if mode == 3 else _native.COMPUTE_F32_QONLY
-    with torch.cuda.device(p_win.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        st = lib.diinn_decode_tile_win(C.c_void_p(stream), C.c_void_p(p_win.data_ptr()), int(p_row0), p_rows,
-                                       C.c_void_p(packed.data_ptr()), C.c_void_p(out.data_ptr()),
-                                       out.stride(2), out.stride(1), out.stride(0), b, h, w, hu, wu, y0, y1, x0, x1,
-                                       int(sin_mode), comp)
-    _native.check(st, "diinn_decode_tile_win")
+    _launch("diinn_decode_tile_win", p_win.device, p_win, int(p_row0), p_win.numel() // (b * w * P_CHANNELS), packed, out,
+            out.stride(2), out.stride(1), out.stride(0), b, h, w, hu, wu, y0, y1, x0, x1, int(sin_mode), _window_compute(mode, compute))
     return out
 
 
@@ -832,39 +470,27 @@ def liif_axis_tables(n_in: int, n_out: int, v: int) -> Tuple[np.ndarray, np.ndar
     return idx, rel, cell.value
 
 
-def _comparison_decode(fn, fn_name: str, workspace_bytes, feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
+def _comparison_decode(name: str, workspace_bytes, feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
                        out: Optional[torch.Tensor], workspace: Optional[torch.Tensor]) -> torch.Tensor:
-    """The LIIF / MetaSR decode of every HR pixel: ``fn`` (a library entry point with diinn_liif_decode's signature, ``fn_name`` for
-    the error message) with ``workspace_bytes(B, H, W)`` bytes of workspace; a ``workspace`` that is too small is replaced."""
+    """The LIIF / MetaSR decode of every HR pixel: the library's ``name`` (diinn_liif_decode's signature) with
+    ``workspace_bytes(B, H, W)`` bytes of workspace; a ``workspace`` that is too small is replaced."""
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
-    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != IN_CHANNELS:
-        raise ValueError(f"feat must be fp32 [B,{IN_CHANNELS},H,W], got {feat.dtype} {tuple(feat.shape)}")
+    feat, (b, h, w) = _checked_feat(feat)
     hu, wu = size
     hu, wu = int(hu), int(wu)
-    feat = feat.contiguous()
-    b, _, h, w = feat.shape
-    if out is None:
-        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat.device)
-    elif out.shape != (b, 3, hu, wu) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != feat.device:
-        raise ValueError("out must be a contiguous fp32 [B,3,Hu,Wu] tensor on feat's device")
+    out = _checked_out(out, (b, 3, hu, wu), feat.device)
     need = workspace_bytes(b, h, w)
     if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
-    with torch.cuda.device(feat.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        st = fn(C.c_void_p(stream), C.c_void_p(feat.data_ptr()), C.c_void_p(packed.data_ptr()),
-                C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()), b, h, w, hu, wu)
-    _native.check(st, fn_name)
+    _launch(name, feat.device, feat, packed, workspace, out, b, h, w, hu, wu)
     return out
 
 
 def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """LIIF query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (liif.py:59-127,148-155)."""
-    lib = _native.load()
-    return _comparison_decode(lib.diinn_liif_decode, "diinn_liif_decode", lib.diinn_workspace_bytes, feat, packed, size, out, workspace)
+    return _comparison_decode("diinn_liif_decode", _native.load().diinn_workspace_bytes, feat, packed, size, out, workspace)
 
 
 # ---------------------------------------------------------------------------
@@ -896,9 +522,7 @@ def metasr_axis_tables(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, f
 def metasr_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
                            out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """MetaSR query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (metasr.py:70-104,125-135)."""
-    lib = _native.load()
-    return _comparison_decode(lib.diinn_metasr_decode, "diinn_metasr_decode", lib.diinn_metasr_workspace_bytes, feat, packed, size, out,
-                              workspace)
+    return _comparison_decode("diinn_metasr_decode", _native.load().diinn_metasr_workspace_bytes, feat, packed, size, out, workspace)
 
 
 # ---------------------------------------------------------------------------
@@ -915,57 +539,37 @@ class ImplicitDecoder(nn.Module):
     for mode 3, inference, fp32; with modes 1, 2, 4 (unless ``hip_initq_modes`` is set, below) or under autograd ``forward`` raises
     ``NotImplementedError``.
 
-    ``hip_autograd`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, fp32 into
-    training: with it set, ``forward(x, size, None)`` under autograd runs ``initq_training.DecodeInitqFunction`` (the HIP kernels
-    saving the activations, the backward pass on the HIP kernels; ROCm GPU only).  With ``bsize`` given the call stays the no_grad
-    inference path, like the reference's ``batched_step``.  It changes nothing else: modes 1, 2 and 4 with ``init_q``, the bf16
-    arithmetics and every decoder with ``init_q=False`` behave as without it.
+    Seven opt-ins, each a plain attribute and a constructor keyword, default False.  Each opens exactly one more combination of
+    (mode, ``init_q``, ``compute``, inference or autograd) and changes nothing for any other; "autograd" is ``forward(x, size,
+    None)`` with grad enabled and something requiring it (``bsize`` given, or ``no_grad``, is the inference path, like the
+    reference's ``batched_step``).  ``_route`` is the rule -- one table, every supported combination, the flag that opens it and
+    the refusal everything else gets -- and ``tests/test_decoder_routes.py`` pins it for every setting of the seven.
 
-    ``hip_autograd_mode4`` (a plain attribute, also a constructor keyword; default False) opts mode 4, ``init_q=False``, fp32 into
-    training: with it set, ``forward(x, size, None)`` under autograd runs ``mode4_training.DecodeMode4Function`` (mode 3's training
-    forward for the saved activations, the 3x3 head from those planes, the backward pass on the HIP kernels; ROCm GPU only, the
-    output at least 2 x 2).  With ``bsize`` given the call stays the no_grad inference path.  It changes nothing else:
-    ``hip_autograd`` alone does not open mode 4, and mode 4 with ``init_q=True`` or a bf16 arithmetic keeps refusing.
+    ============================  ==========================================  ===========================  =============================
+    flag                          opens                                       needs beside it              what keeps refusing with it
+    ============================  ==========================================  ===========================  =============================
+    ``hip_autograd``              autograd, ``init_q``, mode 3, fp32          --                           init_q modes 1/2/4, mode 4,
+                                  (``initq_training``)                                                     every bf16 arithmetic
+    ``hip_autograd_mode4``        autograd, mode 4, ``init_q=False``, fp32    output >= 2 x 2              mode 4 with ``init_q`` or a
+                                  (``mode4_training``)                                                     bf16 arithmetic
+    ``hip_initq_modes``           inference, ``init_q``, modes 1/2/4, fp32    --                           autograd, bf16 arithmetics,
+                                  (``decode_features_initq``)                                 ``graphs=True``, sharded
+    ``hip_initq_split_bf16``      inference, ``init_q``, mode 3, "bf16x3"     ``compute="bf16x3"``         "bf16", "bf16_full", autograd,
+                                                                                           init_q modes 1/2/4, graphs,
+                                                                                                           sharded
+    ``hip_autograd_initq_modes``  autograd, ``init_q``, modes 1/2/4, fp32     ``hip_initq_modes``          bf16 arithmetics, graphs,
+                                  (``initq_modes_training``)     (alone it does nothing)      sharded
+    ``hip_autograd_split_bf16``   autograd, mode 3, ``init_q=False``,         ``compute="bf16x3"``         modes 1/2/4 and ``init_q``
+                                  "bf16x3" both ways (``split_training``;                                  in "bf16x3" under autograd,
+                                  DESIGN.md 3.7f)                                                          "bf16", "bf16_full", graphs,
+                                                                                                           sharded
+    ``hip_modes_split_bf16``      inference, modes 1/2/4, ``init_q=False``,   ``compute="bf16x3"``         autograd in "bf16x3", init_q
+                                  "bf16x3" (``decode_features(modes_x3=       (``graphs=True`` replays     modes 1/2/4 in any bf16,
+                                  True)``)                    it)                          "bf16", "bf16_full", sharded
+    ============================  ==========================================  ===========================  =============================
 
-    ``hip_initq_modes`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True`` with modes 1, 2 and 4
-    into INFERENCE on the HIP path (fp32; ``decode_features_initq``: the per-pixel modulation chain of modes 1/2, mode 4's tap form
-    on the pixel planes).  With it unset those decoders refuse exactly as before.  With it set they still
-    refuse autograd (``hip_autograd`` / ``hip_autograd_mode4`` do not open it; ``hip_autograd_initq_modes``, below, does), the bf16 arithmetics, ``DIINN(graphs=True)`` and the
-    sharded forward; it changes nothing for mode 3 or ``init_q=False``.
-
-    ``hip_initq_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True``, mode 3, INFERENCE
-    into ``compute="bf16x3"``, the split-bf16 arithmetic (``initq_planes_x3_kernel`` and the init_q form of ``decode_bf16x3_kernel``;
-    DESIGN.md 3.6d).  With it unset every ``compute`` other than ``"f32"`` refuses as before.  With it set only ``"bf16x3"`` opens:
-    ``"bf16"`` / ``"bf16_full"``, autograd, ``init_q`` with modes 1/2/4, ``DIINN(graphs=True)`` and the sharded forward keep
-    refusing with their messages, and ``compute="f32"`` gives the fp32 bits.  ``DIINN.set_split_bf16()`` does not set it: on an
-    ``init_q`` model the user sets both.
-
-    ``hip_autograd_initq_modes`` (a plain attribute, also a constructor keyword; default False) opts ``init_q=True`` with modes 1, 2
-    and 4 into TRAINING, and acts only together with ``hip_initq_modes``, in fp32: with both set, ``forward(x, size, None)`` under
-    autograd runs ``initq_modes_training.DecodeInitqModesFunction`` (modes 1/2: the per-pixel modulation chain forwards and, on
-    pixel_chain_bwd_kernel, backwards; mode 4: mode 3's ``init_q`` training forward, the 3x3 head from its saved planes, the output
-    at least 2 x 2; ROCm GPU only).  With ``bsize`` given or under ``no_grad`` the call is ``hip_initq_modes``'
-    inference path, bit for bit.  Set alone it changes nothing; with it unset every call refuses as before (``hip_autograd`` and
-    ``hip_autograd_mode4`` still do not open these combinations); the bf16 arithmetics, ``DIINN(graphs=True)`` and the sharded
-    forward keep refusing.
-
-    ``hip_autograd_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts mode 3, ``init_q=False``,
-    ``compute="bf16x3"`` into TRAINING: with it set, ``forward(x, size, None)`` under autograd runs
-    ``split_training.DecodeMode3SplitFunction`` -- the per-pixel chain in split-bf16 arithmetic forwards
-    (``decode_bf16x3_kernel<SAVE>``) and backwards (``bwd_layer_x3_kernel``), everything else of the step the fp32 kernels
-    (ROCm GPU only).  It acts for no other combination: with it unset every call refuses or runs exactly as
-    before; with it set modes 1, 2, 4 and ``init_q=True`` with ``compute="bf16x3"`` under autograd, ``"bf16"`` and
-    ``"bf16_full"`` under autograd, ``DIINN(graphs=True)`` and the sharded forward keep refusing, and ``compute="f32"`` trains in
-    fp32 as always.  ``DIINN.set_split_bf16()`` does not set it: a user who wants to train in the split arithmetic sets both.
-
-    ``hip_modes_split_bf16`` (a plain attribute, also a constructor keyword; default False) opts modes 1, 2 and 4, ``init_q=False``,
-    INFERENCE into ``compute="bf16x3"``: with it set, ``forward`` under ``no_grad`` (or with ``bsize`` given) runs
-    ``decode_features(..., compute="bf16x3", modes_x3=True)`` -- the Q-only form of ``decode_bf16x3_kernel`` for modes 1/2, its tap
-    form for mode 4 (chunked by ``MODE4_CHUNK_ROWS`` like the fp32 path; ``DIINN(graphs=True)`` replays it) -- DESIGN.md 3.5b.  With
-    it unset these modes refuse every ``compute`` but ``"f32"`` as before.  With it set the following keep refusing with their
-    messages: autograd through these modes with ``"bf16x3"``; ``init_q=True`` with modes 1/2/4 in any bf16 arithmetic;
-    ``DIINN.forward_sharded``; ``"bf16"`` and ``"bf16_full"``.  It changes nothing for mode 3 or for ``compute="f32"``.
-    ``DIINN.set_split_bf16()`` does not set it: on such a model the user sets both."""
+    ``compute="f32"`` gives the fp32 bits whatever is set.  ``DIINN.set_split_bf16()`` sets none of the three split flags: a user who
+    wants the split arithmetic on such a model sets both."""
 
     hip_autograd = False
     hip_autograd_mode4 = False
@@ -1068,12 +672,56 @@ class ImplicitDecoder(nn.Module):
         self.packed_weights(device)
         return self._packed_initq_x3
 
-    def _initq_modes(self) -> bool:
-        """``init_q=True`` with mode 1, 2 or 4 and the opt-in set: the paths of ``decode_features_initq``."""
-        return bool(self.init_q and self.hip_initq_modes and self.mode in (1, 2, 4))
+    # -- which combination runs where ---------------------------------------------
+    _NO_AUTOGRAD = (NotImplementedError,
+                    "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
+                    "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
+                    "torch.no_grad() (mode 4 in fp32 with init_q=False trains once ImplicitDecoder.hip_autograd_mode4 is set)")
+    _INFERENCE_ONLY = (NotImplementedError,
+                       "diinn_amd: init_q=True with mode {mode} (ImplicitDecoder.hip_initq_modes) is inference only: autograd "
+                       "through it is not covered, and hip_autograd / hip_autograd_mode4 do not open it; call it under "
+                       "torch.no_grad() or with bsize given")
+    _INITQ_FP32_ONLY = (ValueError, "init_q=True runs in fp32 only")
+    # Rows of (route or refusal, modes, init_q, compute, flags that must be set); None = any; the first row that matches decides.
+    # _check_supported has already refused init_q with modes 1/2/4 unless hip_initq_modes is set.
+    _INFERENCE_ROUTES = (
+        ("plain",           (1, 2, 3),    False, None,        ()),    # decode_features refuses modes 1/2 in a bf16 arithmetic
+        #                                                               (in "bf16x3": unless hip_modes_split_bf16 is set)
+        ("mode4",           (4,),         False, ("f32",),    ()),
+        ("mode4",           (4,),         False, ("bf16x3",), ("hip_modes_split_bf16",)),
+        ("mode4_fp32_only", (4,),         False, None,        ()),    # refused behind the device check: "mode 4 runs in fp32 only"
+        ("initq",           (3,),         True,  ("f32",),    ()),
+        ("initq",           (3,),         True,  ("bf16x3",), ("hip_initq_split_bf16",)),
+        ("initq_modes",     (1, 2, 4),    True,  ("f32",),    ("hip_initq_modes",)),
+        (_INITQ_FP32_ONLY,  (1, 2, 3, 4), True,  None,        ()),
+    )
+    _AUTOGRAD_ROUTES = (
+        ("grad",             (1, 2, 3),    False, ("f32",),    ()),
+        ("grad_split",       (3,),         False, ("bf16x3",), ("hip_autograd_split_bf16",)),
+        ("grad_mode4",       (4,),         False, ("f32",),    ("hip_autograd_mode4",)),
+        ("grad_initq",       (3,),         True,  ("f32",),    ("hip_autograd",)),
+        ("grad_initq_modes", (1, 2, 4),    True,  ("f32",),    ("hip_initq_modes", "hip_autograd_initq_modes")),
+        (_INFERENCE_ONLY,    (1, 2, 4),    True,  None,        ()),
+        (_NO_AUTOGRAD,       (1, 2, 3, 4), None,  None,        ()),
+    )
+    # the module whose decode_with_grad runs an autograd route
+    _GRAD_MODULES = {"grad": "training", "grad_split": "split_training", "grad_mode4": "mode4_training",
+                     "grad_initq": "initq_training", "grad_initq_modes": "initq_modes_training"}
+
+    def _route(self, wants_grad: bool) -> str:
+        """The path of this (mode, init_q, compute) with the flags as they are set, under autograd or not: a route name, or the
+        refusal raised.  Decides and nothing else; looks at no tensor."""
+        init_q = bool(self.init_q)
+        for route, modes, q, computes, flags in (self._AUTOGRAD_ROUTES if wants_grad else self._INFERENCE_ROUTES):
+            if self.mode in modes and (q is None or q == init_q) and (computes is None or self.compute in computes) \
+                    and all(getattr(self, flag) for flag in flags):
+                if isinstance(route, str):
+                    return route
+                raise route[0](route[1].format(mode=self.mode))
+        raise AssertionError("every supported (mode, init_q) has a closing row")
 
     def _check_supported(self):
-        if self.mode not in (1, 2, 3, 4) or (self.init_q and self.mode != 3 and not self._initq_modes()):
+        if self.mode not in (1, 2, 3, 4) or (self.init_q and self.mode != 3 and not self.hip_initq_modes):
             raise NotImplementedError(
                 f"diinn_amd HIP decode path implements modes 1-4 with init_q=False (mode 3 is the reference's "
                 f"final model) and init_q=True for mode 3, which is covered; got mode={self.mode}, init_q={self.init_q}")
@@ -1108,122 +756,79 @@ class ImplicitDecoder(nn.Module):
         it raises unless ``hip_autograd_initq_modes`` is set as well (then: ``initq_modes_training.DecodeInitqModesFunction``, the
         whole image at once)."""
         self._check_supported()
-        wants_grad = bsize is None and torch.is_grad_enabled() and (
-            x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        # the opt-in (initq_modes_training.py): acts only together with hip_initq_modes, in fp32
-        initq_modes_grad = bool(self._initq_modes() and self.hip_autograd_initq_modes and self.compute == "f32")
-        if wants_grad and initq_modes_grad:
-            if self.mode == 4 and (int(size[0]) < 2 or int(size[1]) < 2):
-                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {int(size[0])} x {int(size[1])}")
-            _require_cuda(x, "x")
-            from .initq_modes_training import decode_with_grad as decode_initq_modes_with_grad
-            return decode_initq_modes_with_grad(self, x, size)
-        if wants_grad and self._initq_modes():
-            raise NotImplementedError(
-                f"diinn_amd: init_q=True with mode {self.mode} (ImplicitDecoder.hip_initq_modes) is inference only: autograd "
-                "through it is not covered, and hip_autograd / hip_autograd_mode4 do not open it; call it under "
-                "torch.no_grad() or with bsize given")
         # reference: bsize=None runs step() under autograd (training, sr_module.py:128).  What this path cannot
         # differentiate is refused before anything looks at the tensor's device: the answer depends on no tensor data
-        initq_grad = self.init_q and self.hip_autograd and self.mode == 3 and self.compute == "f32"     # the opt-in (initq_training.py)
-        mode4_grad = self.mode == 4 and self.hip_autograd_mode4 and not self.init_q and self.compute == "f32"   # the opt-in (mode4_training.py)
-        # the opt-in (split_training.py): mode 3, init_q=False, the split-bf16 arithmetic both ways
-        split_grad = bool(self.hip_autograd_split_bf16 and self.mode == 3 and not self.init_q and self.compute == "bf16x3")
-        if wants_grad and not mode4_grad and not split_grad and (self.mode not in (1, 2, 3) or self.compute != "f32" or (self.init_q and not initq_grad)):
-            raise NotImplementedError(
-                "diinn_amd: autograd through the HIP decode path covers modes 1-3 in fp32 with init_q=False (mode 3 is the "
-                "reference's final model, modes 1/2 its ablations); call mode 4, init_q=True or the bf16 path under "
-                "torch.no_grad() (mode 4 in fp32 with init_q=False trains once ImplicitDecoder.hip_autograd_mode4 is set)")
-        if wants_grad and mode4_grad and (int(size[0]) < 2 or int(size[1]) < 2):
-            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {int(size[0])} x {int(size[1])}")
-        initq_x3 = bool(self.init_q and self.mode == 3 and self.hip_initq_split_bf16 and self.compute == "bf16x3")   # the opt-in
-        if self.init_q and self.compute != "f32" and not initq_x3:
-            raise ValueError("init_q=True runs in fp32 only")
-        _require_cuda(x, "x")
+        wants_grad = bsize is None and torch.is_grad_enabled() and (
+            x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        route = self._route(wants_grad)
         if wants_grad:
-            if split_grad:
-                from .split_training import decode_with_grad as decode_split_with_grad
-                return decode_split_with_grad(self, x, size)
-            if self.init_q:
-                from .initq_training import decode_with_grad as decode_initq_with_grad
-                return decode_initq_with_grad(self, x, size)
             if self.mode == 4:
-                from .mode4_training import decode_with_grad as decode_mode4_with_grad
-                return decode_mode4_with_grad(self, x, size)
-            from .training import decode_with_grad
-            return decode_with_grad(self, x, size)
-        b, c, h, w = x.shape
-        need = b * h * w * P_CHANNELS
-        capturing = torch.cuda.is_current_stream_capturing()
-        key = None if capturing else (str(x.device), torch.cuda.current_stream(x.device).cuda_stream)
-
-        def cached(cache, numel):
-            # hipGraph capture (modules._GraphReplay): the captured kernels keep the workspace pointer for the
-            # graph's lifetime, so it must come from the graph's private pool -- the cached workspace is
-            # replaced (and its block recycled) as soon as a larger input arrives
-            if capturing:
-                return torch.empty(numel, dtype=torch.float32, device=x.device)
-            ws = cache.get(key)
-            if ws is None or ws.numel() < numel:
-                cache.pop(key, None)
-                while len(cache) >= self._MAX_WORKSPACES:
-                    cache.pop(next(iter(cache)))
-                ws = cache[key] = torch.empty(numel, dtype=torch.float32, device=x.device)
-            return ws
-
-        if self._initq_modes():
-            hu, wu = size
-            hu, wu = int(hu), int(wu)
-            if self.mode == 4 and (hu < 2 or wu < 2):
-                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
-            # mode 4 computes the planes and the taps of one more row each way (clipped to the image): THOSE rows follow the chunk
-            # rule -- within the cap and a whole number of the kernels' 8-row blocks, as MODE4_CHUNK_ROWS = 254 does without
-            # init_q -- so a chunk is two output rows shorter (16 + 2 tap rows would start a third block row of both kernels:
-            # B = 16 of 48 x 48 x4 measured 22.8 ms that way against the eager sequence's 21.4)
-            halo = 2 if self.mode == 4 else 0
-            chunk = initq_chunk_rows(b, wu, self.INITQ_CHUNK_BYTES) - halo
-            pix = cached(self._pix_workspaces, b * min(chunk + halo, hu) * wu * (P_CHANNELS + HIDDEN))
-            taps = cached(self._tap_workspaces, _native.load().diinn_mode4_taps_bytes(b, hu, wu, 1, min(hu, chunk + 1)) // 4) \
-                if self.mode == 4 else None
+                require_2x2(int(size[0]), int(size[1]))
+            _require_cuda(x, "x")
+            return importlib.import_module("." + self._GRAD_MODULES[route], __package__).decode_with_grad(self, x, size)
+        _require_cuda(x, "x")
+        b, _, h, w = x.shape
+        x3 = self.compute == "bf16x3"                 # on a chunked route: the opt-in that opened it is set
+        if route == "plain":
+            workspace = self._workspace(self._workspaces, b * h * w * P_CHANNELS, x.device)
             with torch.no_grad():
-                packed = self.packed_weights(x.device)
-                out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
-                for y0 in range(0, hu, chunk):
-                    decode_features_initq(x, packed, self._packed_initq, (hu, wu), self.mode, head=self._packed_head, taps=taps,
-                                          pix=pix, rows=(y0, min(hu, y0 + chunk)), out=out, sin_mode=self.sin_mode)
-                return out
+                return decode_features(x, self.packed_weights(x.device), size, workspace=workspace, sin_mode=self.sin_mode,
+                                       compute=self.compute, mode=self.mode,
+                                       modes_x3=bool(self.hip_modes_split_bf16 and self.mode != 3 and x3))
+        if route == "mode4":
+            workspace = self._workspace(self._workspaces, b * h * w * P_CHANNELS, x.device)
+            return self._decode_chunks(x, size, self.MODE4_CHUNK_ROWS, 0, lambda packed, out, rows, pix, taps: decode_features(
+                x, packed, out.shape[2:], out=out, workspace=workspace, rows=rows, sin_mode=self.sin_mode, mode=4,
+                head=self._packed_head, taps=taps, compute="bf16x3" if x3 else "f32", modes_x3=x3))
+        if route == "mode4_fp32_only":
+            raise ValueError("mode 4 runs in fp32 only")
+        chunk = initq_chunk_rows(b, int(size[1]), self.INITQ_CHUNK_BYTES)
+        if route == "initq":
+            return self._decode_chunks(x, size, chunk, 0, lambda packed, out, rows, pix, taps: decode_features(
+                x, packed, out.shape[2:], out=out, rows=rows, sin_mode=self.sin_mode, initq=self._packed_initq, pix=pix,
+                compute="bf16x3" if x3 else "f32", initq_x3=self._packed_initq_x3 if x3 else None))
+        # route == "initq_modes".  Mode 4 computes the planes and the taps of one more row each way (clipped to the image): THOSE
+        # rows follow the chunk rule -- within the cap and a whole number of the kernels' 8-row blocks, as MODE4_CHUNK_ROWS = 254
+        # does without init_q -- so a chunk is two output rows shorter (16 + 2 tap rows would start a third block row of both
+        # kernels: B = 16 of 48 x 48 x4 measured 22.8 ms that way against the eager sequence's 21.4)
+        halo = 2 if self.mode == 4 else 0
+        return self._decode_chunks(x, size, chunk - halo, halo, lambda packed, out, rows, pix, taps: decode_features_initq(
+            x, packed, self._packed_initq, out.shape[2:], self.mode, head=self._packed_head, taps=taps, pix=pix, rows=rows, out=out,
+            sin_mode=self.sin_mode))
+
+    def _workspace(self, cache, numel: int, device) -> torch.Tensor:
+        """An fp32 buffer of at least ``numel`` from ``cache``, one per (device, stream) that called forward."""
+        # hipGraph capture (modules._GraphReplay): the captured kernels keep the workspace pointer for the
+        # graph's lifetime, so it must come from the graph's private pool -- the cached workspace is
+        # replaced (and its block recycled) as soon as a larger input arrives
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty(numel, dtype=torch.float32, device=device)
+        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        ws = cache.get(key)
+        if ws is None or ws.numel() < numel:
+            cache.pop(key, None)
+            while len(cache) >= self._MAX_WORKSPACES:
+                cache.pop(next(iter(cache)))
+            ws = cache[key] = torch.empty(numel, dtype=torch.float32, device=device)
+        return ws
+
+    def _decode_chunks(self, x: torch.Tensor, size, chunk: int, halo: int, decode) -> torch.Tensor:
+        """The image in bands of ``chunk`` HR rows: ``decode(packed, out, rows, pix, taps)`` per band into one ``out``.  ``pix``
+        (``init_q``) holds the planes of a band plus ``halo`` rows, ``taps`` (mode 4) those of the largest band: rows
+        [0, chunk + 1) reach one tap row each way unless the image ends first."""
+        b = x.shape[0]
+        hu, wu = size
+        hu, wu = int(hu), int(wu)
+        pix = taps = None
+        if self.mode == 4:
+            require_2x2(hu, wu)
+            taps = self._workspace(self._tap_workspaces, _native.load().diinn_mode4_taps_bytes(b, hu, wu, 1, min(hu, chunk + 1)) // 4,
+                                   x.device)
         if self.init_q:
-            hu, wu = size
-            hu, wu = int(hu), int(wu)
-            chunk = initq_chunk_rows(b, wu, self.INITQ_CHUNK_BYTES)
-            pix = cached(self._pix_workspaces, b * min(chunk, hu) * wu * (P_CHANNELS + HIDDEN))
-            with torch.no_grad():
-                packed = self.packed_weights(x.device)
-                out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
-                for y0 in range(0, hu, chunk):
-                    decode_features(x, packed, (hu, wu), out=out, rows=(y0, min(hu, y0 + chunk)), sin_mode=self.sin_mode,
-                                    initq=self._packed_initq, pix=pix, compute="bf16x3" if initq_x3 else "f32",
-                                    initq_x3=self._packed_initq_x3 if initq_x3 else None)
-                return out
-        workspace = cached(self._workspaces, need)
-        modes_x3 = bool(self.hip_modes_split_bf16 and self.mode in (1, 2, 4) and self.compute == "bf16x3")      # the opt-in
+            pix = self._workspace(self._pix_workspaces, b * min(chunk + halo, hu) * wu * (P_CHANNELS + HIDDEN), x.device)
         with torch.no_grad():
             packed = self.packed_weights(x.device)
-            if self.mode != 4:
-                return decode_features(x, packed, size, workspace=workspace, sin_mode=self.sin_mode,
-                                       compute=self.compute, mode=self.mode, modes_x3=modes_x3)
-            if self.compute != "f32" and not modes_x3:
-                raise ValueError("mode 4 runs in fp32 only")
-            hu, wu = size
-            hu, wu = int(hu), int(wu)
-            if hu < 2 or wu < 2:
-                raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
-            chunk = self.MODE4_CHUNK_ROWS
-            # (rows [0, chunk + 1) reach one tap row each way unless the image ends first: the largest band of the loop below)
-            taps = cached(self._tap_workspaces, _native.load().diinn_mode4_taps_bytes(b, hu, wu, 1, min(hu, chunk + 1)) // 4)
             out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=x.device)
             for y0 in range(0, hu, chunk):
-                decode_features(x, packed, (hu, wu), out=out, workspace=workspace, rows=(y0, min(hu, y0 + chunk)),
-                                sin_mode=self.sin_mode, mode=4, head=self._packed_head, taps=taps,
-                                compute="bf16x3" if modes_x3 else "f32", modes_x3=modes_x3)
-            return out
+                decode(packed, out, (y0, min(hu, y0 + chunk)), pix, taps)
+        return out

@@ -34,8 +34,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _native
+from .decoder import require_2x2
 from .initq_training import (INITQ_PARAM_NAMES, INITQ_PARAM_SHAPES, PAD_ROWS, backward_fused_initq, embedding_planes,
                              pack_body_on_device, pack_train_image_on_device)
+from .sheets import head3x3_gather
 from .mode4_training import TAP_STRIDE, TAPS, head_adjoint_taps, pack_head3x3_on_device
 from .training import (HIDDEN, PARAM_NAMES, PLANE_TILE, UNFOLD, _cell_sum, _fill_wpu, checked_features, coordinate_tensors)
 
@@ -101,12 +103,6 @@ def images_on_device(params: Sequence[torch.Tensor], mode: int):
 # ---------------------------------------------------------------------------
 # the formula sheet (device-agnostic tensor algebra)
 # ---------------------------------------------------------------------------
-def _reflect_index(n: int, dev) -> torch.Tensor:
-    """[n + 2]: the source position of padded position -1 .. n under 'reflect' (-1 -> 1, n -> n - 2)."""
-    r = torch.arange(-1, n + 1, device=dev).abs()
-    return torch.where(r >= n, 2 * (n - 1) - r, r)
-
-
 def forward_planes_initq_modes(feat: torch.Tensor, params: Sequence[torch.Tensor], size: Sequence[int], mode: int):
     """The forward of ``init_q=True`` with mode 1, 2 or 4 in tensor algebra (any device, ``feat``'s dtype), in the restructured form of
     ``decoder.initq_modes_forward_reference``.  ``params`` in INITQ_PARAM_NAMES order with ``param_shapes(mode)``.
@@ -138,14 +134,9 @@ def forward_planes_initq_modes(feat: torch.Tensor, params: Sequence[torch.Tensor
     if mode != 4:
         out = p["last_layer.weight"].reshape(3, HIDDEN) @ q + p["last_layer.bias"].reshape(3, 1)
         return out.reshape(3, b, hu, wu).permute(1, 0, 2, 3).contiguous(), torch.stack(acts)
-    if hu < 2 or wu < 2:
-        raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+    require_2x2(hu, wu)
     taps = torch.einsum("chyx,hn->yxcn", p["last_layer.weight"], q).reshape(3, 3, 3, b, hu, wu)       # T[ky][kx][c] per pixel
-    ry, rx = _reflect_index(hu, dev), _reflect_index(wu, dev)
-    out = p["last_layer.bias"].reshape(3, 1, 1, 1).expand(3, b, hu, wu).clone()
-    for ky in range(3):
-        for kx in range(3):
-            out = out + taps[ky, kx][:, :, ry[ky:ky + hu]][:, :, :, rx[kx:kx + wu]]
+    out = head3x3_gather(taps, p["last_layer.bias"].reshape(3, 1, 1, 1))
     return out.permute(1, 0, 2, 3).contiguous(), torch.stack(acts)
 
 
@@ -289,8 +280,8 @@ class DecodeInitqModesFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, mode: int, *params: torch.Tensor) -> torch.Tensor:
-        if mode == 4 and (hu < 2 or wu < 2):
-            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+        if mode == 4:
+            require_2x2(hu, wu)
         feat_c = checked_features(feat, params, INITQ_PARAM_NAMES, param_shapes(mode), hu, wu, PAD_ROWS,
                                   f" for decoder mode {mode} with init_q")
         out, acts, packed, image, head = train_forward_initq_modes(feat_c, params, hu, wu, sin_mode, mode)

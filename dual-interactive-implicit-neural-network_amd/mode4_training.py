@@ -35,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native
+from .decoder import require_2x2
 from .training import (HIDDEN, PARAM_NAMES, PLANE_TILE, backward_from_saved, backward_fused, checked_features,
                        coordinate_tensors, pack_on_device, param_shapes)
 
@@ -135,8 +136,7 @@ def head_adjoint_taps(gout: torch.Tensor) -> torch.Tensor:
     dT[b, r, y', x'] = sum of g[b, c, y, x] over the (y, x) with refl(y + ky - 1, Hu) = y' and refl(x + kx - 1, Wu) = x', the up to
     four terms added in bwd_head3x3_kernel's order: (direct y, direct x), (direct y, border x), (border y, direct x), (border, border)."""
     b, _, hu, wu = gout.shape
-    if hu < 2 or wu < 2:
-        raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+    require_2x2(hu, wu)
     iy, oy = _axis_sources(hu, gout.device)
     ix, ox = _axis_sources(wu, gout.device)
     taps = []
@@ -205,8 +205,7 @@ class DecodeMode4Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, *params: torch.Tensor) -> torch.Tensor:
-        if hu < 2 or wu < 2:
-            raise ValueError(f"mode 4: the reflect-padded 3x3 head needs an output of at least 2 x 2, got {hu} x {wu}")
+        require_2x2(hu, wu)
         feat_c = checked_features(feat, params, PARAM_NAMES, MODE4_PARAM_SHAPES, hu, wu, 2 * HIDDEN, " for decoder mode 4")
         out, acts, packed, head = train_forward_mode4(feat_c, params, hu, wu, sin_mode)
         ctx.save_for_backward(feat_c, acts, packed, head, *[p_.detach() for p_ in params])

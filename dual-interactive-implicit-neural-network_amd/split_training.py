@@ -30,6 +30,7 @@ import torch
 
 from . import _native
 from . import training as T
+from .sheets import split_hi_lo, split_matmul  # noqa: F401  (the sheet's two primitives; cited here by tests and DESIGN.md 3.7f)
 from .training import HIDDEN, PARAM_NAMES, PARAM_SHAPES, PLANE_TILE
 
 
@@ -128,20 +129,6 @@ def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.
 # ---------------------------------------------------------------------------
 # the emulation sheet (any device; the CPU tests and DESIGN.md 3.7f cite it)
 # ---------------------------------------------------------------------------
-def split_hi_lo(v: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """hi = bf16(v), lo = bf16(v - hi), round to nearest even, both returned in v's dtype (fp32)."""
-    hi = v.to(torch.bfloat16).to(v.dtype)
-    lo = (v - hi).to(torch.bfloat16).to(v.dtype)
-    return hi, lo
-
-
-def split_matmul(w: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
-    """w . q as the kernels form it: the two small products first, the leading one last; fp32 accumulation."""
-    wh, wl = split_hi_lo(w)
-    qh, ql = split_hi_lo(q)
-    return (wl @ qh + wh @ ql) + wh @ qh
-
-
 def split_forward_reference(sd: Dict[str, np.ndarray], feat: np.ndarray, size: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
     """The split training forward in torch fp32 on the CPU: (out [B,3,Hu,Wu], planes [4,2,256,N] = k_i, s_i in radians).
     P = conv3x3(feat; Wx) + bK per LR cell, replicated to the cell's pixels (the hoisted form the kernels run); layer 0, the seeds,
