@@ -6,6 +6,7 @@ product; nothing here ever routes to a CPU implementation.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -276,6 +277,31 @@ def check(status: int, what: str) -> None:
         msg = lib.diinn_status_string(status).decode()
         extra = f" (hipError_t {lib.diinn_last_hip_error()})" if status == 3 else ""
         raise DiinnNativeError(f"{what} failed: {msg}{extra}")
+
+
+def _arg(a):
+    if a is None or isinstance(a, int):
+        return a
+    if isinstance(a, tuple):                                     # (tensor, n): the tensor's address plus n floats
+        return C.c_void_p(a[0].data_ptr() + 4 * a[1])
+    return C.c_void_p(a.data_ptr())
+
+
+@contextlib.contextmanager
+def launcher(device):
+    """The one place a kernel launch is made: enters ``device`` and reads its current stream once, then yields
+    ``run(name, *args)``, which enqueues the library's ``name`` there and raises unless it answers DIINN_OK.  A tensor goes as its
+    address, a ``(tensor, n)`` pair as the address plus n floats, None as NULL, integers as they are.  A backward pass makes its
+    14 to 23 launches inside one ``with``: the device is entered per block, not per launch."""
+    import torch
+    lib = load()
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def run(name: str, *args) -> None:
+            check(getattr(lib, name)(stream, *[_arg(a) for a in args]), name)
+        run.stream = stream                                      # (for a launch helper that takes the stream: convs.launch_conv3x3)
+        yield run
 
 
 def debug_set(name: str, value: int) -> None:

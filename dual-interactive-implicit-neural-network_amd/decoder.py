@@ -223,11 +223,8 @@ def _not_a_band(y0: int, y1: int, hu: int) -> ValueError:
 
 def _launch(name: str, device, *args) -> None:
     """Enqueue the library's ``name`` on the current stream of ``device``: tensors go as their addresses, integers as they are."""
-    lib = _native.load()
-    with torch.cuda.device(device):
-        st = getattr(lib, name)(C.c_void_p(torch.cuda.current_stream().cuda_stream),
-                                *[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args])
-    _native.check(st, name)
+    with _native.launcher(device) as run:
+        run(name, *args)
 
 
 def decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],

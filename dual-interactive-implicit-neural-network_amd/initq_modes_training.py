@@ -28,7 +28,6 @@ slots of the pixel record hold bK_i exactly, dx' gets nothing from layers 1..3 a
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -39,7 +38,8 @@ from .initq_training import (INITQ_PARAM_NAMES, INITQ_PARAM_SHAPES, PAD_ROWS, ba
                              pack_body_on_device, pack_train_image_on_device)
 from .sheets import head3x3_gather
 from .mode4_training import TAP_STRIDE, TAPS, head_adjoint_taps, pack_head3x3_on_device
-from .training import (HIDDEN, PARAM_NAMES, PLANE_TILE, UNFOLD, _cell_sum, _fill_wpu, checked_features, coordinate_tensors)
+from .training import (HIDDEN, PARAM_NAMES, UNFOLD, _cell_sum, _fill_wpu, checked_features, coordinate_tensors, function_grads, kept,
+                       named_params, train_buffers, weights_key)
 
 MODES = (1, 2, 4)
 _K123 = tuple(f"K.{i}.0.weight" for i in (1, 2, 3))
@@ -78,17 +78,12 @@ def image_tensors(params: Sequence[torch.Tensor], mode: int) -> Dict[str, torch.
     return p
 
 
-_image_cache: tuple = (None, None, None, None, None)    # (key, body image, training image, head image, the tensors the key describes)
-
-
 def images_on_device(params: Sequence[torch.Tensor], mode: int):
     """(body image, init_q training image, head image or None) of the INITQ_PARAM_NAMES tensors of a mode-``mode`` decoder on their GPU,
     each one gather (``initq_training.pack_body_on_device`` / ``pack_train_image_on_device``, ``mode4_training.pack_head3x3_on_device``).
     Mode 4's body image also carries section WPU and its validity word (``training._fill_wpu``): diinn_head3x3_from_planes answers NaN
     on a body image without one.  The last triple is kept while no parameter has been modified; the entry pins its tensors."""
-    global _image_cache
-    key = (mode, *((t.data_ptr(), t._version) for t in params))
-    if _image_cache[0] != key:
+    def build():
         p = image_tensors(params, mode)
         body = pack_body_on_device(p)
         head = None
@@ -96,8 +91,8 @@ def images_on_device(params: Sequence[torch.Tensor], mode: int):
             _fill_wpu(body, [p[name] for name in PARAM_NAMES], 3)
             named = dict(zip(INITQ_PARAM_NAMES, params))
             head = pack_head3x3_on_device(named["last_layer.weight"], named["last_layer.bias"])
-        _image_cache = (key, body, pack_train_image_on_device(p), head, tuple(t.detach() for t in params))
-    return _image_cache[1], _image_cache[2], _image_cache[3]
+        return body, pack_train_image_on_device(p), head
+    return kept("initq_modes", (mode, *weights_key(params)), params, build)
 
 
 # ---------------------------------------------------------------------------
@@ -248,29 +243,17 @@ def backward_fused_initq_modes(gout: torch.Tensor, feat: torch.Tensor, acts: tor
 def train_forward_initq_modes(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int, mode: int):
     """The training forward on a contiguous fp32 CUDA ``feat_c``.  Returns (out, acts [4,T,512,32], body image, training image, head
     image or None).  The pixel planes (5,120 bytes per HR pixel) and mode 4's tap buffer are dropped on return."""
-    lib = _native.load()
-    b, c, h, w = feat_c.shape
-    n = b * hu * wu
-    dev = feat_c.device
+    b, _, h, w = feat_c.shape
     packed, image, head = images_on_device(params, mode)
-    f32 = dict(dtype=torch.float32, device=dev)
-    pix = torch.empty(lib.diinn_initq_pix_bytes(b, wu, hu) // 4, **f32)
-    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), **f32)
-    out = torch.empty((b, 3, hu, wu), **f32)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    acts, out, pix = train_buffers(feat_c, hu, wu, _native.load().diinn_initq_pix_bytes(b, wu, hu) // 4)
+    with _native.launcher(feat_c.device) as run:
         if mode != 4:
-            _native.check(lib.diinn_decode_initq_train_fwd_qonly(stream, ptr(feat_c), ptr(packed), ptr(image), ptr(pix), ptr(out), ptr(acts),
-                                                                 b, h, w, hu, wu, int(sin_mode), int(mode == 1)),
-                          "diinn_decode_initq_train_fwd_qonly")
+            run("diinn_decode_initq_train_fwd_qonly", feat_c, packed, image, pix, out, acts, b, h, w, hu, wu, int(sin_mode), int(mode == 1))
         else:
-            out3 = torch.empty((b, 3, hu, wu), **f32)             # the body image's 1x1 head is zero: discarded
-            taps = torch.empty(n * TAP_STRIDE, **f32)
-            _native.check(lib.diinn_decode_initq_train_fwd(stream, ptr(feat_c), ptr(packed), ptr(image), ptr(pix), ptr(out3), ptr(acts),
-                                                           b, h, w, hu, wu, int(sin_mode)), "diinn_decode_initq_train_fwd")
-            _native.check(lib.diinn_head3x3_from_planes(stream, ptr(acts), ptr(packed), ptr(head), ptr(taps), ptr(out), b, hu, wu),
-                          "diinn_head3x3_from_planes")
+            out3 = torch.empty_like(out)                          # the body image's 1x1 head is zero: discarded
+            taps = torch.empty(b * hu * wu * TAP_STRIDE, dtype=torch.float32, device=feat_c.device)
+            run("diinn_decode_initq_train_fwd", feat_c, packed, image, pix, out3, acts, b, h, w, hu, wu, int(sin_mode))
+            run("diinn_head3x3_from_planes", acts, packed, head, taps, out, b, hu, wu)
     return out, acts, packed, image, head
 
 
@@ -295,14 +278,12 @@ class DecodeInitqModesFunction(torch.autograd.Function):
         feat, acts, packed, image, *head = ctx.saved_tensors
         d_feat, d_params = backward_fused_initq_modes(gout.contiguous(), feat, acts, packed, image, ctx.size, ctx.mode,
                                                       head=head[0] if head else None, need_feat_grad=ctx.needs_input_grad[0])
-        need = ctx.needs_input_grad[5:]
-        return (d_feat, None, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return function_grads(ctx, d_feat, d_params, 5)
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``ImplicitDecoder(mode in (1, 2, 4), init_q=True, hip_initq_modes=True, hip_autograd_initq_modes=True).forward(x, size, None)``
     under autograd."""
-    named = dict(decoder.named_parameters())
     hu, wu = size
     return DecodeInitqModesFunction.apply(feat, int(hu), int(wu), int(decoder.sin_mode), int(decoder.mode),
-                                          *[named[name] for name in INITQ_PARAM_NAMES])
+                                          *named_params(decoder, INITQ_PARAM_NAMES))

@@ -27,16 +27,16 @@ inference image never has to be redone on the device -- followed by Wx^T and Q0^
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
-from .training import (HIDDEN, IN_CHANNELS, PARAM_NAMES, PARAM_SHAPES, PLANE_TILE, ROWDOT_SPLITS, UNFOLD, WGRAD_KSPLIT,
-                       _cell_sum, _geometry, _sum_parts, checked_features, coordinate_tensors, pack_gather_index,
-                       position_state_dict, tile_planes)
+from .training import (HIDDEN, IN_CHANNELS, PARAM_NAMES, PARAM_SHAPES, PLANE_TILE, UNFOLD, ChainStage, _cell_sum, _sum_parts,
+                       checked_features, coordinate_tensors, function_grads, gather_index, index_on, kept, named_params,
+                       pack_gather_index, position_state_dict, train_buffers, weights_key)
 
 PAD_ROWS = 640             # the 576 unfolded rows padded to 5 x 128: diinn_plane_gemm_nt wants M % 128 == 0
 WGRAD_X_KSPLIT = 51        # pixel-axis splits of the x' / E weight-gradient GEMMs: 5 output blocks x 51 = 255 workgroups, one per CU
@@ -71,28 +71,16 @@ def image_word() -> int:
     return UNFOLD * 4 + 8 * (UNFOLD // 8) * 256 + HIDDEN
 
 
-_image_index_cpu: Optional[torch.Tensor] = None
-_index_dev: Dict[tuple, torch.Tensor] = {}
-
-
+@functools.lru_cache(maxsize=None)
 def train_image_gather_index() -> torch.Tensor:
     """int64 [image floats]: image[i] = flat[index[i]] with ``flat`` the IMAGE_NAMES tensors flattened in order followed by one 0.0
     (the padding rows and the validity word point at it; the word is written after the gather).  Derived by packing a state dict
     whose values are their own flat position (exact in fp32), as ``training.pack_gather_index``."""
-    global _image_index_cpu
-    if _image_index_cpu is not None:
-        return _image_index_cpu
     sd, total = position_state_dict(IMAGE_NAMES, INITQ_PARAM_SHAPES)
     packed = pack_initq_train(sd).numpy()
     word = image_word()
     if packed[word:word + 1].view(np.uint32)[0] != _native.INITQ_TRAIN_MAGIC:
         raise RuntimeError("the init_q training image carries no validity word where the layout says")
-    idx = np.rint(packed).astype(np.int64) - 1
-    idx[word] = -1
-    if idx.max() >= total or idx.min() < -1:
-        raise RuntimeError("the init_q training image is not a permutation of the reference tensors")
-    used = np.zeros(total, bool)
-    used[idx[idx >= 0]] = True
     # (the q-columns of K.1..3 -- Wq_i -- live in the body image, not here)
     need = np.ones(total, bool)
     off = 0
@@ -101,22 +89,14 @@ def train_image_gather_index() -> torch.Tensor:
         if name in ("K.1.0.weight", "K.2.0.weight", "K.3.0.weight"):
             need[off:off + n].reshape(HIDDEN, HIDDEN + UNFOLD)[:, :HIDDEN] = False
         off += n
-    if not used[need].all():
-        raise RuntimeError("the init_q training image does not reference every element it is built from")
-    idx[idx < 0] = total
-    _image_index_cpu = torch.from_numpy(idx)
-    return _image_index_cpu
+    return gather_index(packed, total, [(word, 1)], "the init_q training image", need=need)
 
 
 def pack_train_image_on_device(p: Dict[str, torch.Tensor]) -> torch.Tensor:
     """``pack_initq_train`` of the named tensors ``p`` on their GPU: one gather and the validity word."""
     dev = p["Q.0.0.weight"].device
-    key = ("image", str(dev))
-    idx = _index_dev.get(key)
-    if idx is None:
-        idx = _index_dev[key] = train_image_gather_index().to(dev)
     flat = torch.cat([p[name].detach().reshape(-1).to(torch.float32) for name in IMAGE_NAMES] + [torch.zeros(1, device=dev)])
-    image = flat.index_select(0, idx)
+    image = flat.index_select(0, index_on(dev, "initq", train_image_gather_index))
     word = image_word()
     image[word:word + 1].view(torch.int32).fill_(_native.INITQ_TRAIN_MAGIC)
     return image
@@ -127,27 +107,18 @@ def pack_body_on_device(p: Dict[str, torch.Tensor]) -> torch.Tensor:
     NaN on it) of the K / Q.1..3 / head tensors with a zero [256,3] in place of the 576-wide ``Q.0.0.weight``, whose rows the init_q
     kernels never read.  No Winograd section: this configuration has no hoisted conv."""
     dev = p["Q.0.0.weight"].device
-    key = ("body", str(dev))
-    idx = _index_dev.get(key)
-    if idx is None:
-        idx = _index_dev[key] = pack_gather_index(3).to(dev)
     parts = [torch.zeros(HIDDEN * 3, device=dev) if name == "Q.0.0.weight" else p[name].detach().reshape(-1).to(torch.float32)
              for name in PARAM_NAMES]
-    return torch.cat(parts + [torch.zeros(1, device=dev)]).index_select(0, idx)
-
-
-_image_cache: tuple = (None, None, None, None)     # (key, body image, training image, the parameter tensors the key describes)
+    return torch.cat(parts + [torch.zeros(1, device=dev)]).index_select(0, index_on(dev, 3, pack_gather_index))
 
 
 def images_on_device(params: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """(body image, init_q training image) of the INITQ_PARAM_NAMES tensors on their GPU.  The last pair is kept while no parameter has
     been modified (a training step decodes once per scale with the same weights); the entry pins the tensors its key describes."""
-    global _image_cache
-    key = tuple((t.data_ptr(), t._version) for t in params)
-    if _image_cache[0] != key:
+    def build():
         p = dict(zip(INITQ_PARAM_NAMES, params))
-        _image_cache = (key, pack_body_on_device(p), pack_train_image_on_device(p), tuple(t.detach() for t in params))
-    return _image_cache[1], _image_cache[2]
+        return pack_body_on_device(p), pack_train_image_on_device(p)
+    return kept("initq", weights_key(params), params, build)
 
 
 # ---------------------------------------------------------------------------
@@ -255,94 +226,37 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
                 are two 256-row plane GEMMs per layer in place of the stacked 512-row one;
       ``head``  (mode 4: the 3x3 head image; ``packed`` is the body image with a zero 1x1 head)  diinn_backward_data_head3x3, and
                 d last_layer.weight [3,256,3,3] from q_3 against the seven 4-row groups of dT, as in ``training.backward_fused``."""
-    lib = _native.load()
-    b, _, h, w = feat.shape
-    hu, wu = int(size[0]), int(size[1])
-    n = b * hu * wu
-    t = (n + PLANE_TILE - 1) // PLANE_TILE
-    dev = gout.device
-    if tuple(acts.shape) != (4, t, 2 * HIDDEN, PLANE_TILE) or not acts.is_contiguous():
-        raise ValueError("acts must be the contiguous tiled [4, T, 512, 32] buffer of the training forward")
-    geo = _geometry(b, h, w, hu, wu, dev)
-    seg_h, seg_w, syn_t = geo["seg_h"], geo["seg_w"], geo["syn_t"]
-    f32 = dict(dtype=torch.float32, device=dev)
-    gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
-    g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), **f32)
-    q = torch.empty((4, t, HIDDEN, PLANE_TILE), **f32)
-    if qonly and head is not None:
-        raise ValueError("qonly (modes 1/2) and head (mode 4) exclude each other")
-    if head is None:
-        heads = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))[None]     # 4-row right-hand side of the head product
-    else:
-        # dT as seven 4-row groups (row 27 zero), written by bwd_head3x3_kernel; the rowdot reads whole tiles: a ragged last tile's padding is zeroed here
-        heads = (torch.empty if n % PLANE_TILE == 0 else torch.zeros)((7, t, 4, PLANE_TILE), **f32)
+    c = ChainStage(gout, feat, acts, packed, size, head=head, qonly=qonly)
+    b, h, w, hu, wu, n, t, g = c.b, c.h, c.w, c.hu, c.wu, c.n, c.t, c.g
+    syn_t = c.geo["syn_t"]
+    f32 = dict(dtype=torch.float32, device=c.dev)
     u_t = torch.empty((t, UNFOLD, PLANE_TILE), **f32)
     da_t = torch.empty((t, UNFOLD, PLANE_TILE), **f32)
     xp_t = torch.empty((t, PAD_ROWS, PLANE_TILE), **f32)
     e_t = torch.empty((t, PAD_ROWS, PLANE_TILE), **f32)
-    # (qonly: the weight-gradient GEMMs have 256 rows = 2 output blocks; twice the splits make one workgroup per CU, as in backward_fused_modes12)
-    ksplit = max(1, min(2 * WGRAD_KSPLIT if qonly else WGRAD_KSPLIT, t))
     xsplit = max(1, min(WGRAD_X_KSPLIT, t))
-    rsplit = max(1, min(ROWDOT_SPLITS, t))
-    part = torch.empty((6, ksplit, HIDDEN, HIDDEN + 1) if qonly else (3, ksplit, 2 * HIDDEN, HIDDEN + 1), **f32)
+    rsplit = c.rsplit
     partx = torch.empty((5, xsplit, PAD_ROWS, HIDDEN), **f32)
-    part0 = torch.empty((rsplit, 2 * HIDDEN, 4), **f32)
-    partl = torch.empty((len(heads), rsplit, HIDDEN, 4), **f32)
     partf = torch.empty((rsplit, 2 * HIDDEN, 4), **f32)           # (dFw | dbF): the rowdot takes at most 512 rows per launch --
     partg = torch.empty((rsplit, UNFOLD - 2 * HIDDEN, 4), **f32)   # rows 0..511, then rows 512..575
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     d_feat = None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if qonly:
-            _native.check(lib.diinn_backward_data_qonly(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n), "diinn_backward_data_qonly")
-            _native.check(lib.diinn_pixel_chain_bwd(stream, ptr(g), ptr(acts), ptr(packed), n), "diinn_pixel_chain_bwd")
-            for i in (3, 2, 1):                                  # [dKk_i | dbK_i] = g_a,i . k_{i-1}^T, then [dQw_i | dbQ_i] = g_s,i . q_{i-1}^T
-                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(acts[i - 1]), 2 * HIDDEN, 0,
-                                                      ptr(part[2 * (i - 1)]), HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
-                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, HIDDEN, ptr(q[i - 1]), HIDDEN, 0,
-                                                      ptr(part[2 * (i - 1) + 1]), HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
-        else:
-            if head is None:
-                _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n), "diinn_backward_data")
-            else:
-                _native.check(lib.diinn_backward_data_head3x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(head), ptr(g), ptr(q), ptr(heads),
-                                                              b, hu, wu), "diinn_backward_data_head3x3")
-            for i in (3, 2, 1):
-                _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(q[i - 1]), HIDDEN, 0,
-                                                      ptr(part[i - 1]), 2 * HIDDEN, HIDDEN, n, ksplit, 1), "diinn_plane_gemm_nt")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(g[0]), 2 * HIDDEN, ptr(syn_t), ptr(part0), 2 * HIDDEN, n, rsplit),
-                      "diinn_plane_rowdot")
-        for i in range(len(heads)):
-            _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(heads[i]), ptr(partl[i]), HIDDEN, n, rsplit),
-                          "diinn_plane_rowdot")
-        _native.check(lib.diinn_initq_backward(stream, ptr(feat), ptr(g), ptr(image), ptr(u_t), ptr(da_t), ptr(xp_t), ptr(e_t),
-                                               b, h, w, hu, wu), "diinn_initq_backward")
+    with _native.launcher(c.dev) as run:
+        c.launch(run)
+        run("diinn_initq_backward", feat, g, image, u_t, da_t, xp_t, e_t, b, h, w, hu, wu)
         for i in range(4):                                       # dWx_i^T [640 x 256] = x' . g_a,i^T
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(xp_t), PAD_ROWS, 0, ptr(g[i]), 2 * HIDDEN, 0, ptr(partx[i]),
-                                                  PAD_ROWS, HIDDEN, n, xsplit, 0), "diinn_plane_gemm_nt")
-        _native.check(lib.diinn_plane_gemm_nt(stream, ptr(e_t), PAD_ROWS, 0, ptr(g[0]), 2 * HIDDEN, HIDDEN, ptr(partx[4]),
-                                              PAD_ROWS, HIDDEN, n, xsplit, 0), "diinn_plane_gemm_nt")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(da_t), UNFOLD, ptr(syn_t), ptr(partf), 2 * HIDDEN, n, rsplit), "diinn_plane_rowdot")
-        _native.check(lib.diinn_plane_rowdot(stream, C.c_void_p(da_t.data_ptr() + 2 * HIDDEN * PLANE_TILE * 4), UNFOLD, ptr(syn_t), ptr(partg),
-                                             UNFOLD - 2 * HIDDEN, n, rsplit), "diinn_plane_rowdot")
+            run("diinn_plane_gemm_nt", xp_t, PAD_ROWS, 0, g[i], 2 * HIDDEN, 0, partx[i], PAD_ROWS, HIDDEN, n, xsplit, 0)
+        run("diinn_plane_gemm_nt", e_t, PAD_ROWS, 0, g[0], 2 * HIDDEN, HIDDEN, partx[4], PAD_ROWS, HIDDEN, n, xsplit, 0)
+        run("diinn_plane_rowdot", da_t, UNFOLD, syn_t, partf, 2 * HIDDEN, n, rsplit)
+        run("diinn_plane_rowdot", (da_t, 2 * HIDDEN * PLANE_TILE), UNFOLD, syn_t, partg, UNFOLD - 2 * HIDDEN, n, rsplit)
         if need_feat_grad:
             d_unf = torch.empty((b, UNFOLD, h, w), **f32)
             d_feat = torch.empty((b, IN_CHANNELS, h, w), **f32)
-            _native.check(lib.diinn_cell_sum_rows(stream, ptr(u_t), UNFOLD, UNFOLD, ptr(seg_h), ptr(seg_w), ptr(d_unf), b, h, w, hu, wu),
-                          "diinn_cell_sum_rows")
-            _native.check(lib.diinn_fold3x3(stream, ptr(d_unf), ptr(d_feat), b, IN_CHANNELS, h, w), "diinn_fold3x3")
+            run("diinn_cell_sum_rows", u_t, UNFOLD, UNFOLD, c.geo["seg_h"], c.geo["seg_w"], d_unf, b, h, w, hu, wu)
+            run("diinn_fold3x3", d_unf, d_feat, b, IN_CHANNELS, h, w)
     grads: Dict[str, torch.Tensor] = {}
-    dl = _sum_parts(partl.view(len(heads), rsplit, -1)).view(len(heads), HIDDEN, 4)   # group i: q_3 . (rows 4 i .. 4 i + 3 of the right-hand side)^T
-    if head is None:                                             # [256, 4]: q_3 . (g_out ; 0)^T
-        grads["last_layer.weight"] = dl[0, :, :3].t().reshape(3, HIDDEN, 1, 1)
-    else:                                                        # [256, r = 3 (3 ky + kx) + c] -> [c, ch, ky, kx]
-        grads["last_layer.weight"] = dl.permute(1, 0, 2).reshape(HIDDEN, 28)[:, :27].t().reshape(3, 3, 3, HIDDEN).permute(2, 3, 0, 1).contiguous()
-    grads["last_layer.bias"] = gp.sum(1)
-    # [3, 512, 257]: [dWq_i ; dQw_i | bias sums] (qonly: the two 256-row products of a layer are neighbours in ``part``: the same view)
-    dws = _sum_parts(part.view(part.shape[0], ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)
+    d_wq, d_bk = c.grads(grads)
     dxs = _sum_parts(partx.view(5, xsplit, -1)).view(5, PAD_ROWS, HIDDEN)[:, :UNFOLD].transpose(1, 2)   # [5, 256, 576]: dWx_0..3, dQ0
-    d0 = _sum_parts(part0.view(1, rsplit, -1)).view(2 * HIDDEN, 4)   # column 3: (dbK_0 ; dbQ0)
+    d0 = c.layer0()
     df = torch.cat([_sum_parts(partf.view(1, rsplit, -1)).view(2 * HIDDEN, 4),
                     _sum_parts(partg.view(1, rsplit, -1)).view(UNFOLD - 2 * HIDDEN, 4)], 0)               # [576, 4]: (dFw | dbF)
     grads["first_layer.0.weight"] = df[:, :3].reshape(UNFOLD, 3, 1, 1)
@@ -352,29 +266,18 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
     grads["Q.0.0.weight"] = dxs[4].reshape(HIDDEN, UNFOLD, 1, 1)
     grads["Q.0.0.bias"] = d0[HIDDEN:, 3]
     for i in (3, 2, 1):
-        dw = dws[i - 1]
-        grads[f"K.{i}.0.weight"] = torch.cat([dw[:HIDDEN, :HIDDEN], dxs[i]], dim=1).reshape(HIDDEN, HIDDEN + UNFOLD, 1, 1)
-        grads[f"K.{i}.0.bias"] = dw[:HIDDEN, HIDDEN]
-        grads[f"Q.{i}.0.weight"] = dw[HIDDEN:, :HIDDEN].reshape(HIDDEN, HIDDEN, 1, 1)
-        grads[f"Q.{i}.0.bias"] = dw[HIDDEN:, HIDDEN]
+        grads[f"K.{i}.0.weight"] = torch.cat([d_wq[i], dxs[i]], dim=1).reshape(HIDDEN, HIDDEN + UNFOLD, 1, 1)
+        grads[f"K.{i}.0.bias"] = d_bk[i]
     return d_feat, [grads[name] for name in INITQ_PARAM_NAMES]
 
 
 def train_forward_initq(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int):
     """The training forward on a contiguous fp32 CUDA ``feat_c``.  Returns (out, acts [4,T,512,32], body image, training image)."""
-    lib = _native.load()
-    b, c, h, w = feat_c.shape
-    n = b * hu * wu
-    dev = feat_c.device
+    b, _, h, w = feat_c.shape
     packed, image = images_on_device(params)
-    pix = torch.empty(lib.diinn_initq_pix_bytes(b, wu, hu) // 4, dtype=torch.float32, device=dev)
-    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_decode_initq_train_fwd(stream, ptr(feat_c), ptr(packed), ptr(image), ptr(pix), ptr(out), ptr(acts),
-                                                       b, h, w, hu, wu, int(sin_mode)), "diinn_decode_initq_train_fwd")
+    acts, out, pix = train_buffers(feat_c, hu, wu, _native.load().diinn_initq_pix_bytes(b, wu, hu) // 4)
+    with _native.launcher(feat_c.device) as run:
+        run("diinn_decode_initq_train_fwd", feat_c, packed, image, pix, out, acts, b, h, w, hu, wu, int(sin_mode))
     return out, acts, packed, image
 
 
@@ -396,12 +299,10 @@ class DecodeInitqFunction(torch.autograd.Function):
         feat, acts, packed, image = ctx.saved_tensors
         d_feat, d_params = backward_fused_initq(gout.contiguous(), feat, acts, packed, image, ctx.size,
                                                 need_feat_grad=ctx.needs_input_grad[0])
-        need = ctx.needs_input_grad[4:]
-        return (d_feat, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return function_grads(ctx, d_feat, d_params, 4)
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``ImplicitDecoder(mode=3, init_q=True, hip_autograd=True).forward(x, size, None)`` under autograd."""
-    named = dict(decoder.named_parameters())
     hu, wu = size
-    return DecodeInitqFunction.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *[named[name] for name in INITQ_PARAM_NAMES])
+    return DecodeInitqFunction.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *named_params(decoder, INITQ_PARAM_NAMES))

@@ -36,7 +36,7 @@ other training paths is not used: P must be the inference forward's, bit for bit
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -171,58 +171,28 @@ def liif_backward_reference(gout: torch.Tensor, feat: torch.Tensor, params: Sequ
 # ---------------------------------------------------------------------------
 # the image gathered on the device (the weights change every optimiser step: no host packing inside the step)
 # ---------------------------------------------------------------------------
-_pack_index_cpu: Optional[torch.Tensor] = None
-_index_dev: Dict[str, torch.Tensor] = {}
-DERIVED_SECTIONS = (7, 9, 10, 11, 12, 13, 14, 15, 16)           # inference-only sections of the DIINN image: derived values, no gather
+DERIVED_SECTIONS = T.DERIVED_SECTIONS                          # inference-only sections of the DIINN image: derived values, no gather
 
 
+@functools.lru_cache(maxsize=None)
 def pack_gather_index() -> torch.Tensor:
     """int64 [packed floats]: packed[i] = flat[index[i]] with ``flat`` the ten imnet tensors flattened in PARAM_NAMES order followed
     by one 0.0.  Derived by packing a state dict whose values are their own flat position (exact in fp32) through
     ``pack_liif_state_dict``.  The places LIIF leaves empty (the modulation slots), the derived sections -- no LIIF kernel
     reads them -- and the validity word point at the appended zero; every parameter element is referenced."""
-    global _pack_index_cpu
-    if _pack_index_cpu is None:
-        from .decoder import pack_liif_state_dict
-        lib = _native.load()
-        sd, total = T.position_state_dict(PARAM_NAMES, PARAM_SHAPES)
-        idx = np.rint(pack_liif_state_dict(sd, prefix="").numpy()).astype(np.int64) - 1
-        off, size = C.c_size_t(), C.c_size_t()
-        for section in DERIVED_SECTIONS:
-            _native.check(lib.diinn_packed_section(section, C.byref(off), C.byref(size)), "diinn_packed_section")
-            idx[off.value:off.value + size.value] = -1
-        _native.check(lib.diinn_packed_section(6, C.byref(off), C.byref(size)), "diinn_packed_section")
-        idx[off.value + 3] = -1
-        if idx.max() >= total or idx.min() < -1:
-            raise RuntimeError("the LIIF packed image is not a permutation of the imnet tensors")
-        used = np.zeros(total, bool)
-        used[idx[idx >= 0]] = True
-        if not used.all():
-            raise RuntimeError("the LIIF packed image does not reference every parameter element")
-        idx[idx < 0] = total
-        _pack_index_cpu = torch.from_numpy(idx)
-    return _pack_index_cpu
-
-
-_image_cache: tuple = (None, None, None)           # (key, image, the parameter tensors the key describes)
+    from .decoder import pack_liif_state_dict
+    sd, total = T.position_state_dict(PARAM_NAMES, PARAM_SHAPES)
+    return T.gather_index(pack_liif_state_dict(sd, prefix="").numpy(), total, T.derived_ranges(), "the LIIF packed image", of="imnet")
 
 
 def image_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
     """imnet tensors (PARAM_NAMES order) on a GPU -> the packed image on that GPU: one ``index_select``.  Kept while no parameter
     has been modified (a training step decodes once per scale with the same weights)."""
-    global _image_cache
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    if _image_cache[0] == key:
-        return _image_cache[1]
-    dev = params[0].device
-    idx = _index_dev.get(str(dev))
-    if idx is None:
-        idx = _index_dev[str(dev)] = pack_gather_index().to(dev)
-    flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params] + [torch.zeros(1, device=dev)])
-    image = flat.index_select(0, idx)
-    # the entry keeps the tensors alive: their addresses cannot be handed to other weights while the key is cached
-    _image_cache = (key, image, tuple(p.detach() for p in params))
-    return image
+    def build():
+        dev = params[0].device
+        flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params] + [torch.zeros(1, device=dev)])
+        return flat.index_select(0, T.index_on(dev, "liif", pack_gather_index))
+    return T.kept("liif", T.weights_key(params), params, build)
 
 
 # ---------------------------------------------------------------------------
@@ -235,17 +205,13 @@ def virtual_tiles(n: int) -> int:
 def train_forward(feat_c: torch.Tensor, image: torch.Tensor, hu: int, wu: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """``diinn_liif_train_fwd`` on a contiguous fp32 CUDA ``feat_c``: (out [B,3,Hu,Wu], acts [4, ceil(4 N / 32), 256, 32] = h_1..h_4 over
     the virtual pixels)."""
-    lib = _native.load()
     b, _, h, w = feat_c.shape
     dev = feat_c.device
     out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
     acts = torch.empty((4, virtual_tiles(b * hu * wu), HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    workspace = torch.empty(lib.diinn_workspace_bytes(b, h, w) // 4, dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_liif_train_fwd(stream, ptr(feat_c), ptr(image), ptr(workspace), ptr(out), ptr(acts), b, h, w, hu, wu),
-                      "diinn_liif_train_fwd")
+    workspace = torch.empty(_native.load().diinn_workspace_bytes(b, h, w) // 4, dtype=torch.float32, device=dev)
+    with _native.launcher(dev) as run:
+        run("diinn_liif_train_fwd", feat_c, image, workspace, out, acts, b, h, w, hu, wu)
     return out, acts
 
 
@@ -262,9 +228,7 @@ def _geometry(b: int, h: int, w: int, hu: int, wu: int, dev) -> dict:
     """Per-shape constants of the backward pass, built once per (B, LR size, HR size, device) like ``training._geometry``: the
     members' cell rectangles (seg_h [2, H+1], seg_w [2, W+1]; each index table must be monotone), the ensemble weights over the
     virtual pixels and the tiled right-hand side (rel_h, rel_w, 1, 0) of the layer-1 product."""
-    key = (b, h, w, hu, wu, str(dev))
-    geo = _geo_cache.pop(key, None)
-    if geo is None:
+    def build():
         th, tw, (cell_h, cell_w) = _axis_tables(h, w, hu, wu)
         for idx, _, _ in th + tw:
             if (np.diff(idx) < 0).any():
@@ -277,19 +241,15 @@ def _geometry(b: int, h: int, w: int, hu: int, wu: int, dev) -> dict:
         rhs[0] = r[..., 0].reshape(-1)
         rhs[1] = r[..., 1].reshape(-1)
         rhs[2] = 1.0
-        geo = {"seg_h": torch.from_numpy(seg_h).to(dev), "seg_w": torch.from_numpy(seg_w).to(dev),
-               "wgt": wgt.contiguous(), "rhs_t": T.tile_planes(rhs), "cell": (cell_h, cell_w)}
-        while len(_geo_cache) >= T.GEOMETRY_CACHE_ENTRIES:
-            _geo_cache.pop(next(iter(_geo_cache)))
-    _geo_cache[key] = geo
-    return geo
+        return {"seg_h": torch.from_numpy(seg_h).to(dev), "seg_w": torch.from_numpy(seg_w).to(dev),
+                "wgt": wgt.contiguous(), "rhs_t": T.tile_planes(rhs), "cell": (cell_h, cell_w)}
+    return T.lru(_geo_cache, (b, h, w, hu, wu, str(dev)), build)
 
 
 def cell_sum(g1: torch.Tensor, b: int, h: int, w: int, hu: int, wu: int,
              dp: Optional[torch.Tensor] = None, dp_t: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``diinn_liif_cell_sum`` on g_a,1 (tiled over the virtual pixels, [ceil(4 N / 32), 256, 32]): (dP1 in planes 0..255 of an NCHW
     [B,1024,H,W] buffer, the same in rows 0..255 of a tiled [ceil(B H W / 32), 1024, 32] group).  Given buffers are written in place."""
-    lib = _native.load()
     dev = g1.device
     cells = b * h * w
     tc = (cells + PLANE_TILE - 1) // PLANE_TILE
@@ -298,11 +258,8 @@ def cell_sum(g1: torch.Tensor, b: int, h: int, w: int, hu: int, wu: int,
         dp = torch.empty((b, 4 * HIDDEN, h, w), dtype=torch.float32, device=dev)
     if dp_t is None:                                             # (a ragged last tile's padding stays zero)
         dp_t = (torch.empty if cells % PLANE_TILE == 0 else torch.zeros)((tc, 4 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_liif_cell_sum(stream, ptr(g1), ptr(geo["seg_h"]), ptr(geo["seg_w"]), ptr(dp), ptr(dp_t), b, h, w, hu, wu),
-                      "diinn_liif_cell_sum")
+    with _native.launcher(dev) as run:
+        run("diinn_liif_cell_sum", g1, geo["seg_h"], geo["seg_w"], dp, dp_t, b, h, w, hu, wu)
     return dp, dp_t
 
 
@@ -312,7 +269,6 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, i
     """The same gradients as ``liif_backward_reference``, on the HIP kernels throughout (module docstring).  ``acts``: the tiled
     buffer of ``train_forward``; ``w0``: imnet.layers.0.weight; ``wkey`` / ``wpins`` identify its values for the cache of the
     transposed conv weight.  ``need_w0_grad`` false skips the conv's weight GEMM (d layers.0.weight is then None)."""
-    lib = _native.load()
     b, _, h, w = feat.shape
     hu, wu = int(size[0]), int(size[1])
     n = b * hu * wu
@@ -333,15 +289,12 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, i
     part = torch.empty((3, ksplit, HIDDEN, HIDDEN + 1), dtype=torch.float32, device=dev)
     part1 = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
     partl = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_liif_backward_data(stream, ptr(gp), ptr(acts), ptr(image), ptr(g), b, h, w, hu, wu), "diinn_liif_backward_data")
+    with _native.launcher(dev) as run:
+        run("diinn_liif_backward_data", gp, acts, image, g, b, h, w, hu, wu)
         for li in (3, 2, 1):                                      # [dW_l | db_l] = g_a,l . h_{l-1}^T, l = li + 1
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[li]), HIDDEN, 0, ptr(acts[li - 1]), HIDDEN, 0, ptr(part[li - 1]),
-                                                  HIDDEN, HIDDEN, vn, ksplit, 1), "diinn_plane_gemm_nt")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(acts[3]), HIDDEN, ptr(wg_t), ptr(partl), HIDDEN, vn, rsplit), "diinn_plane_rowdot")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(g[0]), HIDDEN, ptr(geo["rhs_t"]), ptr(part1), HIDDEN, vn, rsplit), "diinn_plane_rowdot")
+            run("diinn_plane_gemm_nt", g[li], HIDDEN, 0, acts[li - 1], HIDDEN, 0, part[li - 1], HIDDEN, HIDDEN, vn, ksplit, 1)
+        run("diinn_plane_rowdot", acts[3], HIDDEN, wg_t, partl, HIDDEN, vn, rsplit)
+        run("diinn_plane_rowdot", g[0], HIDDEN, geo["rhs_t"], part1, HIDDEN, vn, rsplit)
     dp, dp_t = cell_sum(g[0], b, h, w, hu, wu)
     dl = T._sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)      # [256, 4]: h_4 . (w_v g ; 0)^T
     dws = T._sum_parts(part.view(3, ksplit, -1)).view(3, HIDDEN, HIDDEN + 1)
@@ -378,11 +331,10 @@ class LIIFFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         d_feat, d_params = backward_fused(gout, feat, acts, image, w0, ctx.wkey, ctx.wpins, ctx.size,
                                           need_feat_grad=need[0], need_w0_grad=need[3])
-        return (d_feat, None, None, *[g if nd else None for g, nd in zip(d_params, need[3:])])
+        return T.function_grads(ctx, d_feat, d_params, 3)
 
 
 def decode_with_grad(imnet, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``LIIF.query_rgb`` + ``reshape_pred`` of every HR pixel under autograd; ``imnet`` is the model's MLP (modules.MLP)."""
-    named = dict(imnet.named_parameters())
     hu, wu = size
-    return LIIFFunction.apply(feat, int(hu), int(wu), *[named[name] for name in PARAM_NAMES])
+    return LIIFFunction.apply(feat, int(hu), int(wu), *T.named_params(imnet, PARAM_NAMES))

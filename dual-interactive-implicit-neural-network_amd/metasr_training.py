@@ -33,7 +33,7 @@ row 768 + comp holds b2[:, comp], every other row and every bias is zero.
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -126,78 +126,55 @@ def metasr_backward_reference(gout: torch.Tensor, feat: torch.Tensor, params: Se
 # ---------------------------------------------------------------------------
 # images gathered on the device (the weights change every optimiser step: no host packing inside the step)
 # ---------------------------------------------------------------------------
-_conv_index_cpu: Optional[torch.Tensor] = None
-_pack_index_cpu: Optional[torch.Tensor] = None
-_index_dev: Dict[tuple, torch.Tensor] = {}
-
-
+@functools.lru_cache(maxsize=None)
 def conv_gather_index() -> torch.Tensor:
     """int64 [1024*576]: Wx.flatten()[i] = flat[index[i]] for the embedded conv weight Wx [1024,64,3,3], where ``flat`` is
     (layers.2.weight [1728,256], layers.2.bias [1728]) flattened, followed by one 0.0:
         Wx[256 comp + j, n] = W2[3 n + comp, j],    Wx[768 + comp, n] = b2[3 n + comp],    zero elsewhere."""
-    global _conv_index_cpu
-    if _conv_index_cpu is None:
-        nw = 3 * UNFOLD * HIDDEN
-        idx = np.full((ROWS, UNFOLD), nw + 3 * UNFOLD, dtype=np.int64)                # the appended zero
-        n = np.arange(UNFOLD, dtype=np.int64)
-        j = np.arange(HIDDEN, dtype=np.int64)
-        for comp in range(3):
-            idx[HIDDEN * comp:HIDDEN * (comp + 1)] = (3 * n[None, :] + comp) * HIDDEN + j[:, None]
-            idx[3 * HIDDEN + comp] = nw + 3 * n + comp
-        _conv_index_cpu = torch.from_numpy(idx.reshape(-1))
-    return _conv_index_cpu
+    nw = 3 * UNFOLD * HIDDEN
+    idx = np.full((ROWS, UNFOLD), nw + 3 * UNFOLD, dtype=np.int64)                # the appended zero
+    n = np.arange(UNFOLD, dtype=np.int64)
+    j = np.arange(HIDDEN, dtype=np.int64)
+    for comp in range(3):
+        idx[HIDDEN * comp:HIDDEN * (comp + 1)] = (3 * n[None, :] + comp) * HIDDEN + j[:, None]
+        idx[3 * HIDDEN + comp] = nw + 3 * n + comp
+    return torch.from_numpy(idx.reshape(-1))
 
 
+@functools.lru_cache(maxsize=None)
 def pack_gather_index() -> torch.Tensor:
     """int64 [MetaSR packed floats]: packed[i] = flat[index[i]] with ``flat`` the four imnet tensors flattened in PARAM_NAMES
     order.  Derived by packing a state dict whose values are their own flat position (exact in fp32); the MetaSR image is a
-    pure permutation of its parameters."""
-    global _pack_index_cpu
-    if _pack_index_cpu is None:
-        from .decoder import pack_metasr_state_dict
-        sd, total = T.position_state_dict(PARAM_NAMES, PARAM_SHAPES)
-        idx = np.rint(pack_metasr_state_dict(sd, prefix="").numpy()).astype(np.int64) - 1
-        if idx.min() < 0 or idx.max() >= total or np.unique(idx).size != total or idx.size != total:
-            raise RuntimeError("the MetaSR packed image is not a permutation of the imnet tensors")
-        _pack_index_cpu = torch.from_numpy(idx)
-    return _pack_index_cpu
-
-
-def _dev_index(which: str, dev) -> torch.Tensor:
-    key = (which, str(dev))
-    if key not in _index_dev:
-        _index_dev[key] = (conv_gather_index() if which == "conv" else pack_gather_index()).to(dev)
-    return _index_dev[key]
+    pure permutation of its parameters (no padding, no appended zero: a stricter rule than ``training.gather_index``'s)."""
+    from .decoder import pack_metasr_state_dict
+    sd, total = T.position_state_dict(PARAM_NAMES, PARAM_SHAPES)
+    idx = np.rint(pack_metasr_state_dict(sd, prefix="").numpy()).astype(np.int64) - 1
+    if idx.min() < 0 or idx.max() >= total or np.unique(idx).size != total or idx.size != total:
+        raise RuntimeError("the MetaSR packed image is not a permutation of the imnet tensors")
+    return torch.from_numpy(idx)
 
 
 def conv_weight_on_device(w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
     """The embedded conv weight Wx [1024,64,3,3] (``conv_gather_index``) on the tensors' device: one gather."""
     dev = w2.device
     flat = torch.cat([w2.detach().reshape(-1).to(torch.float32), b2.detach().reshape(-1).to(torch.float32), torch.zeros(1, device=dev)])
-    return flat.index_select(0, _dev_index("conv", dev)).view(ROWS, T.IN_CHANNELS, 3, 3)
-
-
-_images_cache: tuple = (None, None, None)          # (key, (inference image, training image, Wx), the parameter tensors the key describes)
+    return flat.index_select(0, T.index_on(dev, "metasr conv", conv_gather_index)).view(ROWS, T.IN_CHANNELS, 3, 3)
 
 
 def images_on_device(params: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """imnet tensors (PARAM_NAMES order) on a GPU -> (the MetaSR packed image metasr_kernel reads, the DIINN-shaped training
     image whose section 13 holds the embedded conv in Winograd form -- what diinn_precompute_P_wpu reads; every bias zero --,
     the embedded conv weight Wx).  Kept while no parameter has been modified (a training step decodes once per scale)."""
-    global _images_cache
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    if _images_cache[0] == key:
-        return _images_cache[1]
-    w1, b1, w2, b2 = params
-    dev = w2.device
-    flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params])
-    packed = flat.index_select(0, _dev_index("pack", dev))
-    wx = conv_weight_on_device(w2, b2)
-    image = torch.zeros(_native.load().diinn_packed_weight_floats(), dtype=torch.float32, device=dev)
-    T._fill_wpu_weight(image, wx)
-    # the entry keeps the tensors alive: their addresses cannot be handed to other weights while the key is cached
-    _images_cache = (key, (packed, image, wx), tuple(p.detach() for p in params))
-    return _images_cache[1]
+    def build():
+        w1, b1, w2, b2 = params
+        dev = w2.device
+        flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params])
+        packed = flat.index_select(0, T.index_on(dev, "metasr pack", pack_gather_index))
+        wx = conv_weight_on_device(w2, b2)
+        image = torch.zeros(_native.load().diinn_packed_weight_floats(), dtype=torch.float32, device=dev)
+        T._fill_wpu_weight(image, wx)
+        return packed, image, wx
+    return T.kept("metasr", T.weights_key(params), params, build)
 
 
 # ---------------------------------------------------------------------------
@@ -210,24 +187,19 @@ def cell_segments(h: int, w: int, hu: int, wu: int, dev) -> Tuple[torch.Tensor, 
     """seg_h [H+1] / seg_w [W+1] (int32, on ``dev``): the first HR row / column of every LR row / column of MetaSR's index table
     (monotone), last entry Hu / Wu.  One entry per (LR size, HR size, device) of a training run."""
     from .decoder import metasr_axis_tables
-    key = (h, w, hu, wu, str(dev))
-    seg = _seg_cache.pop(key, None)
-    if seg is None:
+
+    def build():
         idx_h, idx_w = metasr_axis_tables(h, hu)[0], metasr_axis_tables(w, wu)[0]
         if (np.diff(idx_h) < 0).any() or (np.diff(idx_w) < 0).any():
             raise RuntimeError("MetaSR's index table is not monotone")
-        seg = (torch.from_numpy(np.searchsorted(idx_h, np.arange(h + 1)).astype(np.int32)).to(dev),
-               torch.from_numpy(np.searchsorted(idx_w, np.arange(w + 1)).astype(np.int32)).to(dev))
-        while len(_seg_cache) >= T.GEOMETRY_CACHE_ENTRIES:
-            _seg_cache.pop(next(iter(_seg_cache)))
-    _seg_cache[key] = seg
-    return seg
+        return (torch.from_numpy(np.searchsorted(idx_h, np.arange(h + 1)).astype(np.int32)).to(dev),
+                torch.from_numpy(np.searchsorted(idx_w, np.arange(w + 1)).astype(np.int32)).to(dev))
+    return T.lru(_seg_cache, (h, w, hu, wu, str(dev)), build)
 
 
 def backward_cells(gout: torch.Tensor, m: torch.Tensor, packed: torch.Tensor, size: Sequence[int]):
     """``diinn_metasr_backward_cells`` on contiguous fp32 CUDA tensors: gout [B,3,Hu,Wu], m [B,H,W,1024], packed the MetaSR image.
     Returns (dM NCHW [B,1024,H,W], dM tiled over cells [T,1024,32], [dW1 | db1] [256,4])."""
-    lib = _native.load()
     b, h, w, _ = m.shape
     hu, wu = int(size[0]), int(size[1])
     dev = gout.device
@@ -236,11 +208,8 @@ def backward_cells(gout: torch.Tensor, m: torch.Tensor, packed: torch.Tensor, si
     dm = torch.empty((b, ROWS, h, w), dtype=torch.float32, device=dev)
     dm_t = torch.empty((tc, ROWS, T.PLANE_TILE), dtype=torch.float32, device=dev)
     part0 = torch.empty((2 * tc, HIDDEN, 4), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_metasr_backward_cells(stream, ptr(gout), ptr(m), ptr(packed), ptr(seg_h), ptr(seg_w), ptr(dm), ptr(dm_t),
-                                                      ptr(part0), b, h, w, hu, wu), "diinn_metasr_backward_cells")
+    with _native.launcher(dev) as run:
+        run("diinn_metasr_backward_cells", gout, m, packed, seg_h, seg_w, dm, dm_t, part0, b, h, w, hu, wu)
     d0 = T._sum_parts(part0.view(1, 2 * tc, HIDDEN * 4)).view(HIDDEN, 4)
     return dm, dm_t, d0
 
@@ -265,16 +234,13 @@ class MetaSRFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, *params: torch.Tensor) -> torch.Tensor:
         from .decoder import metasr_decode_features
-        lib = _native.load()
         feat_c = T.checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, ROWS)
         b, _, h, w = feat_c.shape
         packed, image, wx = images_on_device(params)
         out = metasr_decode_features(feat_c, packed, (hu, wu))
         m = torch.empty((b, h, w, ROWS), dtype=torch.float32, device=feat_c.device)
-        with torch.cuda.device(feat_c.device):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _native.check(lib.diinn_precompute_P_wpu(stream, C.c_void_p(feat_c.data_ptr()), C.c_void_p(image.data_ptr()),
-                                                     C.c_void_p(m.data_ptr()), b, h, w, 0, h), "diinn_precompute_P_wpu")
+        with _native.launcher(feat_c.device) as run:
+            run("diinn_precompute_P_wpu", feat_c, image, m, b, h, w, 0, h)
         ctx.save_for_backward(feat_c, m, packed, wx)
         ctx.size = (hu, wu)
         ctx.wkey = ("metasr", *((p_.data_ptr(), p_._version) for p_ in params[2:]))
@@ -287,11 +253,10 @@ class MetaSRFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         d_feat, d_params = backward_fused(gout, feat, m, packed, wx, ctx.wkey, ctx.wpins, ctx.size,
                                           need_feat_grad=need[0], need_w2_grad=need[5] or need[6])
-        return (d_feat, None, None, *[g if nd else None for g, nd in zip(d_params, need[3:])])
+        return T.function_grads(ctx, d_feat, d_params, 3)
 
 
 def decode_with_grad(imnet, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``MetaSR.query_rgb`` + ``reshape_pred`` of every HR pixel under autograd; ``imnet`` is the model's meta-network (modules.MLP)."""
-    named = dict(imnet.named_parameters())
     hu, wu = size
-    return MetaSRFunction.apply(feat, int(hu), int(wu), *[named[name] for name in PARAM_NAMES])
+    return MetaSRFunction.apply(feat, int(hu), int(wu), *T.named_params(imnet, PARAM_NAMES))

@@ -28,7 +28,6 @@ the 16 K / Q tensors with a zero 1x1 head) and the head image (``pack_head3x3_on
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -36,8 +35,8 @@ import torch.nn.functional as F
 
 from . import _native
 from .decoder import require_2x2
-from .training import (HIDDEN, PARAM_NAMES, PLANE_TILE, backward_from_saved, backward_fused, checked_features,
-                       coordinate_tensors, pack_on_device, param_shapes)
+from .training import (HIDDEN, PARAM_NAMES, backward_from_saved, backward_fused, checked_features, coordinate_tensors,
+                       function_grads, kept, named_params, pack_on_device, param_shapes, train_forward_mode3, weights_key)
 
 TAPS = 27                  # 9 taps x 3 colours per HR pixel
 TAP_STRIDE = 28            # floats per pixel of the tap buffer (one pad float)
@@ -57,24 +56,19 @@ def pack_head3x3_on_device(lw: torch.Tensor, lb: torch.Tensor) -> torch.Tensor:
 
 
 _zero_heads: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-_head_cache: tuple = (None, None, None)            # (key, head image, the tensors the key describes)
 
 
 def images_on_device(params: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """(body image, head image) of the PARAM_NAMES tensors of a mode-4 decoder on their GPU.  The body image is
     ``training.pack_on_device`` over the 16 K / Q tensors with a zero 1x1 head (layout 3; the zeros are kept per device, so the
     image's cache key is stable); both are kept while no parameter has been modified."""
-    global _head_cache
     dev = params[0].device
     zeros = _zero_heads.get(str(dev))
     if zeros is None:
         zeros = _zero_heads[str(dev)] = (torch.zeros((3, HIDDEN, 1, 1), device=dev), torch.zeros(3, device=dev))
     body = pack_on_device([*params[:16], *zeros], 4)
     lw, lb = params[16], params[17]
-    key = (str(dev), lw.data_ptr(), lw._version, lb.data_ptr(), lb._version)
-    if _head_cache[0] != key:
-        _head_cache = (key, pack_head3x3_on_device(lw, lb), (lw.detach(), lb.detach()))
-    return body, _head_cache[1]
+    return body, kept("head4", (str(dev), *weights_key((lw, lb))), (lw, lb), lambda: pack_head3x3_on_device(lw, lb))
 
 
 # ---------------------------------------------------------------------------
@@ -176,25 +170,15 @@ def backward_from_saved_mode4(gout: torch.Tensor, feat: torch.Tensor, acts: torc
 # the HIP path
 # ---------------------------------------------------------------------------
 def train_forward_mode4(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int):
-    """The mode-4 training forward on a contiguous fp32 CUDA ``feat_c``.  Returns (out, acts [4,T,512,32], body image, head image)."""
-    lib = _native.load()
-    b, c, h, w = feat_c.shape
-    n = b * hu * wu
-    dev = feat_c.device
+    """The mode-4 training forward on a contiguous fp32 CUDA ``feat_c``: mode 3's on the body image (whose 1x1 head is zero: its
+    ``out`` is discarded), then diinn_head3x3_from_planes.  Returns (out, acts [4,T,512,32], body image, head image)."""
+    b = feat_c.shape[0]
     packed, head = images_on_device(params)
-    workspace = torch.empty(b * h * w * 4 * HIDDEN, dtype=torch.float32, device=dev)
-    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    out3 = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)      # the body image's 1x1 head is zero: discarded
-    taps = torch.empty(n * TAP_STRIDE, dtype=torch.float32, device=dev)
-    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_precompute_P_wpu(stream, ptr(feat_c), ptr(packed), ptr(workspace), b, h, w, 0, h), "diinn_precompute_P_wpu")
-        _native.check(lib.diinn_decode_train_fwd(stream, ptr(workspace), ptr(packed), ptr(out3), ptr(acts), b, h, w, hu, wu, int(sin_mode)),
-                      "diinn_decode_train_fwd")
-        _native.check(lib.diinn_head3x3_from_planes(stream, ptr(acts), ptr(packed), ptr(head), ptr(taps), ptr(out), b, hu, wu),
-                      "diinn_head3x3_from_planes")
+    _, acts = train_forward_mode3(feat_c, packed, hu, wu, sin_mode)
+    taps = torch.empty(b * hu * wu * TAP_STRIDE, dtype=torch.float32, device=feat_c.device)
+    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=feat_c.device)
+    with _native.launcher(feat_c.device) as run:
+        run("diinn_head3x3_from_planes", acts, packed, head, taps, out, b, hu, wu)
     return out, acts, packed, head
 
 
@@ -217,12 +201,10 @@ class DecodeMode4Function(torch.autograd.Function):
         feat, acts, packed, head, *params = ctx.saved_tensors
         d_feat, d_params = backward_fused(gout.contiguous(), feat, acts, params, packed, ctx.size,
                                           need_feat_grad=ctx.needs_input_grad[0], head=head)
-        need = ctx.needs_input_grad[4:]
-        return (d_feat, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return function_grads(ctx, d_feat, d_params, 4)
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``ImplicitDecoder(mode=4, hip_autograd_mode4=True).forward(x, size, None)`` under autograd."""
-    named = dict(decoder.named_parameters())
     hu, wu = size
-    return DecodeMode4Function.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *[named[name] for name in PARAM_NAMES])
+    return DecodeMode4Function.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *named_params(decoder, PARAM_NAMES))

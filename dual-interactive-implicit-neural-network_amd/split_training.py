@@ -22,7 +22,6 @@ the float64 oracle.  What an end-to-end gradient comparison cannot hold is the R
 split rounding of zero lands on the other side, and the gate is discontinuous there (DESIGN.md 3.7f has the measured case)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -31,7 +30,7 @@ import torch
 from . import _native
 from . import training as T
 from .sheets import split_hi_lo, split_matmul  # noqa: F401  (the sheet's two primitives; cited here by tests and DESIGN.md 3.7f)
-from .training import HIDDEN, PARAM_NAMES, PARAM_SHAPES, PLANE_TILE
+from .training import HIDDEN, PARAM_NAMES, PARAM_SHAPES
 
 
 # ---------------------------------------------------------------------------
@@ -50,49 +49,29 @@ def pack_split_host(image: np.ndarray) -> np.ndarray:
     return out
 
 
-_split_cache: tuple = (None, None, None)           # (key, split image, the parameter tensors the key describes)
-
-
 def pack_split_on_device(params: Sequence[torch.Tensor]) -> torch.Tensor:
     """Reference-ordered parameter tensors (PARAM_NAMES, mode 3's shapes) on a GPU -> the split training image on that GPU, from
     ``training.pack_on_device``'s gathered image.  Kept, like that image, while no parameter has been modified: the key is the
     parameters' (address, version) pairs, and the entry pins the tensors it describes."""
-    global _split_cache
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    if _split_cache[0] == key:
-        return _split_cache[1]
-    packed = T.pack_on_device(params)
-    dev = packed.device
-    split = torch.empty(split_train_floats(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _native.check(_native.load().diinn_pack_split_train(C.c_void_p(torch.cuda.current_stream().cuda_stream),
-                                                            C.c_void_p(packed.data_ptr()), C.c_void_p(split.data_ptr())),
-                      "diinn_pack_split_train")
-    _split_cache = (key, split, tuple(p.detach() for p in params))
-    return split
+    def build():
+        packed = T.pack_on_device(params)
+        split = torch.empty(split_train_floats(), dtype=torch.float32, device=packed.device)
+        with _native.launcher(packed.device) as run:
+            run("diinn_pack_split_train", packed, split)
+        return split
+    return T.kept("split", T.weights_key(params), params, build)
 
 
 # ---------------------------------------------------------------------------
 # forward and the autograd function
 # ---------------------------------------------------------------------------
 def train_forward_split(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int):
-    """The split training forward on a contiguous fp32 CUDA ``feat_c``: the hoisted conv (diinn_precompute_P_wpu), then
-    decode_bf16x3_kernel<SIN | X3_SAVE> (diinn_decode_train_fwd_x3).  Returns (out, acts [4,T,512,32], packed image, split image)."""
-    lib = _native.load()
-    b, c, h, w = feat_c.shape
-    n = b * hu * wu
-    dev = feat_c.device
+    """The split training forward on a contiguous fp32 CUDA ``feat_c``: ``training.train_forward_mode3`` with the split image, i.e.
+    the hoisted conv (diinn_precompute_P_wpu), then decode_bf16x3_kernel<SIN | X3_SAVE> (diinn_decode_train_fwd_x3).
+    Returns (out, acts [4,T,512,32], packed image, split image)."""
     packed = T.pack_on_device(params)
     split = pack_split_on_device(params)
-    workspace = torch.empty(b * h * w * 4 * HIDDEN, dtype=torch.float32, device=dev)
-    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_precompute_P_wpu(stream, ptr(feat_c), ptr(packed), ptr(workspace), b, h, w, 0, h), "diinn_precompute_P_wpu")
-        _native.check(lib.diinn_decode_train_fwd_x3(stream, ptr(workspace), ptr(packed), ptr(split), ptr(out), ptr(acts),
-                                                    b, h, w, hu, wu, int(sin_mode)), "diinn_decode_train_fwd_x3")
+    out, acts = T.train_forward_mode3(feat_c, packed, hu, wu, sin_mode, split=split)
     return out, acts, packed, split
 
 
@@ -113,17 +92,14 @@ class DecodeMode3SplitFunction(torch.autograd.Function):
         feat, acts, packed, split, *params = ctx.saved_tensors
         d_feat, d_params = T.backward_fused(gout.contiguous(), feat, acts, params, packed, ctx.size,
                                             need_feat_grad=ctx.needs_input_grad[0], split=split)
-        need = ctx.needs_input_grad[4:]
-        return (d_feat, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return T.function_grads(ctx, d_feat, d_params, 4)
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``ImplicitDecoder.forward(x, size, None)`` under autograd for mode 3, ``init_q=False``, ``compute="bf16x3"`` with
     ``hip_autograd_split_bf16`` set."""
-    named = dict(decoder.named_parameters())
-    params = [named[name] for name in PARAM_NAMES]
     hu, wu = size
-    return DecodeMode3SplitFunction.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *params)
+    return DecodeMode3SplitFunction.apply(feat, int(hu), int(wu), int(decoder.sin_mode), *T.named_params(decoder, PARAM_NAMES))
 
 
 # ---------------------------------------------------------------------------

@@ -73,8 +73,53 @@ def param_shapes(mode: int = 3) -> Dict[str, Tuple[int, ...]]:
 WGRAD_KSPLIT = 64          # pixel-axis splits of the weight-gradient GEMM: 4 output blocks x 64 = one workgroup per CU
 ROWDOT_SPLITS = 1024       # workgroups of the skinny products (HBM-bound)
 
-_gather_index_cpu: Dict[int, torch.Tensor] = {}          # keyed by weight layout: 1 (mode 1) or 3 (modes 2 and 3)
-_gather_index_dev: Dict[tuple, torch.Tensor] = {}
+GEOMETRY_CACHE_ENTRIES = 8
+
+
+# ---------------------------------------------------------------------------
+# the caches of the training paths (this module's and those of the modules that build on it)
+# ---------------------------------------------------------------------------
+_kept: Dict[str, tuple] = {}                       # slot -> (key, value, the tensors the key describes)
+
+
+def weights_key(tensors: Sequence[torch.Tensor]) -> tuple:
+    """What identifies the values of ``tensors`` while they are alive: their (address, version) pairs."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+def kept(slot: str, key, pins: Sequence[torch.Tensor], build):
+    """The rule "keep the last image while no parameter has changed", stated once: the value ``build()`` returned for ``key`` the
+    last time ``slot`` was asked, or a new one when the key differs.  The entry PINS ``pins``, the tensors the key describes: while
+    it is cached their addresses cannot be handed to other weights with equal version counts.
+    (What a key contains is its caller's: a write through ``.data`` bumps no ``_version`` and none of them sees it -- to change
+    that, change the callers' keys through ``weights_key``.)"""
+    ent = _kept.get(slot)
+    if ent is None or ent[0] != key:
+        ent = _kept[slot] = (key, build(), tuple(t.detach() for t in pins))
+    return ent[1]
+
+
+def lru(cache: dict, key, build):
+    """``cache[key]``, built on a miss, in a small LRU (GEOMETRY_CACHE_ENTRIES; a hit becomes the newest entry): the per-shape
+    constants of the backward passes -- training revisits a handful of shapes, one per scale."""
+    value = cache.pop(key, None)
+    if value is None:
+        value = build()
+        while len(cache) >= GEOMETRY_CACHE_ENTRIES:
+            cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+_index_dev: Dict[tuple, torch.Tensor] = {}
+
+
+def index_on(dev, name, index) -> torch.Tensor:
+    """The gather index ``index()`` (a CPU tensor its maker keeps) on ``dev``: copied once per (name, device)."""
+    key = (name, str(dev))
+    if key not in _index_dev:
+        _index_dev[key] = index().to(dev)
+    return _index_dev[key]
 
 
 def _layout(mode: int) -> int:
@@ -97,6 +142,39 @@ def position_state_dict(names: Sequence[str], shapes: Dict[str, Tuple[int, ...]]
     return sd, pos - 1
 
 
+def gather_index(packed: np.ndarray, total: int, blank: Sequence[Tuple[int, int]], what: str, of: str = "reference",
+                 need: Optional[np.ndarray] = None) -> torch.Tensor:
+    """int64 [image floats]: image[i] = flat[index[i]], from ``packed``, the image a host packer made of ``position_state_dict``'s
+    ``total`` elements; ``flat`` is those tensors flattened in order followed by one 0.0.  The (offset, size) float ranges
+    ``blank`` (derived values, a validity word) and the padding point at the appended zero.  Raises unless the rest is a
+    permutation that references every element (``need``: a mask of the elements that must be; default all): ``what`` / ``of``
+    name the image and its tensors in the two messages."""
+    idx = np.rint(packed).astype(np.int64) - 1
+    for off, size in blank:
+        idx[off:off + size] = -1
+    if idx.max() >= total or idx.min() < -1:
+        raise RuntimeError(f"{what} is not a permutation of the {of} tensors")
+    used = np.zeros(total, bool)
+    used[idx[idx >= 0]] = True
+    if not (used.all() if need is None else used[need].all()):
+        raise RuntimeError(f"{what} does not reference every " + ("parameter element" if need is None else "element it is built from"))
+    idx[idx < 0] = total                                # the appended zero
+    return torch.from_numpy(idx)
+
+
+DERIVED_SECTIONS = (7, 9, 10, 11, 12, 13, 14, 15, 16)           # inference-only sections of the DIINN image: derived values, no gather
+
+
+def derived_ranges() -> List[Tuple[int, int]]:
+    """The float ranges of a DIINN-layout image that a gather leaves empty: the derived sections and the validity word behind bL
+    (DIINN_PACKED_MAGIC), which reads as zero in a gathered image: the inference entry points, which read the derived sections,
+    then answer NaN instead of decoding with empty weights."""
+    return [_section(i) for i in DERIVED_SECTIONS] + [(_section(6)[0] + 3, 1)]
+
+
+_gather_index_cpu: Dict[int, torch.Tensor] = {}          # keyed by weight layout: 1 (mode 1) or 3 (modes 2 and 3)
+
+
 def pack_gather_index(mode: int = 3) -> torch.Tensor:
     """int64 [packed floats]: packed[i] = flat[index[i]] where ``flat`` is the 18 reference tensors
     flattened in PARAM_NAMES order followed by one 0.0 (padding and the bf16 section point at it).
@@ -104,47 +182,18 @@ def pack_gather_index(mode: int = 3) -> torch.Tensor:
     Mode 1 (K.1..3 are [256,256]): the feature columns the host packer widens them with are zeros, so
     those places -- layers 1..3 of the hoisted conv -- point at the appended zero as well."""
     layout = _layout(mode)
-    if layout in _gather_index_cpu:
-        return _gather_index_cpu[layout]
-    from .decoder import pack_state_dict
-    lib = _native.load()
-    sd, total = position_state_dict(PARAM_NAMES, param_shapes(layout))
-    packed = pack_state_dict(sd, mode=layout).numpy()
-    idx = np.rint(packed).astype(np.int64) - 1
-    off, size = C.c_size_t(), C.c_size_t()
-    for section in (7, 9, 10, 11, 12, 13, 14, 15, 16):          # inference-only sections: derived values, not a permutation
-        _native.check(lib.diinn_packed_section(section, C.byref(off), C.byref(size)), "diinn_packed_section")
-        idx[off.value:off.value + size.value] = -1
-    # the validity word behind bL (DIINN_PACKED_MAGIC) reads as zero in a gathered image: the inference entry points,
-    # which read the derived sections, then answer NaN instead of decoding with empty weights
-    _native.check(lib.diinn_packed_section(6, C.byref(off), C.byref(size)), "diinn_packed_section")
-    idx[off.value + 3] = -1
-    if idx.max() >= total or idx.min() < -1:
-        raise RuntimeError("packed image is not a permutation of the reference tensors")
-    used = np.zeros(total, bool)
-    used[idx[idx >= 0]] = True
-    if not used.all():
-        raise RuntimeError("packed image does not reference every parameter element")
-    idx[idx < 0] = total                                # the appended zero
-    _gather_index_cpu[layout] = torch.from_numpy(idx)
+    if layout not in _gather_index_cpu:
+        from .decoder import pack_state_dict
+        sd, total = position_state_dict(PARAM_NAMES, param_shapes(layout))
+        _gather_index_cpu[layout] = gather_index(pack_state_dict(sd, mode=layout).numpy(), total, derived_ranges(), "packed image")
     return _gather_index_cpu[layout]
-
-
-_packed_cache: tuple = (None, None, None)          # (key, packed image, the parameter tensors the key describes)
 
 
 def pack_on_device(params: Sequence[torch.Tensor], mode: int = 3) -> torch.Tensor:
     """Reference-ordered parameter tensors (PARAM_NAMES) on a GPU -> packed image on that GPU.
     The last image is kept while no parameter has been modified (a training step decodes once per
     scale with the same weights, sr_module.py:116-121).  ``mode`` 1: the tensors have mode 1's shapes."""
-    global _packed_cache
-    key = (_layout(mode), *((p.data_ptr(), p._version) for p in params))
-    if _packed_cache[0] == key:
-        return _packed_cache[1]
-    packed = _pack_on_device(params, mode)
-    # the entry keeps the tensors alive: their addresses cannot be handed to other weights while the key is cached
-    _packed_cache = (key, packed, tuple(p.detach() for p in params))
-    return packed
+    return kept("packed", (_layout(mode), *weights_key(params)), params, lambda: _pack_on_device(params, mode))
 
 
 _section_cache: Dict[int, Tuple[int, int]] = {}
@@ -193,13 +242,8 @@ def _fill_wpu_weight(packed: torch.Tensor, w: torch.Tensor) -> None:
 
 def _pack_on_device(params: Sequence[torch.Tensor], mode: int = 3) -> torch.Tensor:
     dev = params[0].device
-    key = (str(dev), _layout(mode))
-    idx = _gather_index_dev.get(key)
-    if idx is None:
-        idx = pack_gather_index(mode).to(dev)
-        _gather_index_dev[key] = idx
     flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params] + [torch.zeros(1, device=dev)])
-    packed = flat.index_select(0, idx)
+    packed = flat.index_select(0, index_on(dev, _layout(mode), lambda: pack_gather_index(mode)))
     _fill_wpu(packed, params, mode)
     return packed
 
@@ -327,11 +371,9 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
     The weight and its cache key are the caller's: ``wx`` (a tensor, or a callable returning it, evaluated only when the
     transposed weight has to be repacked), ``wkey`` (what identifies its values: the DIINN callers pass their K weights'
     (address, version) pairs, MetaSR its own tagged tuple) and ``wpins`` (the tensors the key describes)."""
-    lib = _native.load()
     b, c, h, w = feat.shape
     n = b * h * w
     dev = feat.device
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
     dp = dp.contiguous()
     d_wx = None
     if want_weight:
@@ -339,9 +381,6 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
         # the reference's unfold (rows (c, ky, kx), diinn.py:168) from unfold_tiled_kernel (rows 576..639 zero)
         tiles = (n + PLANE_TILE - 1) // PLANE_TILE
         b_t = torch.empty((tiles, 640, PLANE_TILE), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _native.check(lib.diinn_unfold_tiled(C.c_void_p(torch.cuda.current_stream().cuda_stream), ptr(feat.contiguous()), ptr(b_t),
-                                                 640, b, h, w), "diinn_unfold_tiled")
         if a_t is None:
             a_t = tile_planes(dp.permute(1, 0, 2, 3).reshape(4 * HIDDEN, n))
         # the product is taken transposed, dWx^T [640 x 1024] = unfold . dP^T: with 1024 = 4 x 256 columns it runs on the kernel's
@@ -349,11 +388,10 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
         ks = max(1, min(WGRAD_CONV_KSPLIT, a_t.shape[0]))
         part = torch.empty((ks, 640, rows), dtype=torch.float32, device=dev)
     d_feat = None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _native.launcher(dev) as run:
         if want_weight:
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(b_t), 640, 0, ptr(a_t), 4 * HIDDEN, 0, ptr(part), 640, rows, n, ks, 0),
-                          "diinn_plane_gemm_nt")
+            run("diinn_unfold_tiled", feat.contiguous(), b_t, 640, b, h, w)
+            run("diinn_plane_gemm_nt", b_t, 640, 0, a_t, 4 * HIDDEN, 0, part, 640, rows, n, ks, 0)
             d_wx = _sum_parts(part.view(1, ks, -1)).view(640, rows)[:UNFOLD].t()
         if need_feat_grad:
             d_feat = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
@@ -364,7 +402,7 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
             # load_state_dict), not on every backward call.  The Winograd transforms are taken in float64 and rounded once,
             # like the encoder's: F(4x4)'s gradient error 2.5e-5 -> ~1e-5 of max|d_feat| (the fixtures' bound is 1e-4).
             # One entry per (kernel form, device): a multi-scale step alternates forms without evicting each other.  An entry
-            # PINS the weight tensors its key describes (as _packed_cache does): while it is cached their addresses cannot be
+            # PINS the weight tensors its key describes (as ``kept`` does): while it is cached their addresses cannot be
             # handed to another decoder's weights with equal version counts.
             key = (str(dev), wkey, rows)
             ent = _dgrad_pack.get((form, str(dev)))
@@ -377,7 +415,7 @@ def _conv_grads_native(feat: torch.Tensor, wx: torch.Tensor, dp: torch.Tensor, n
                     _dgrad_pack[(form, str(dev))] = ent
             # (F(4x4) takes the encoder's split area of this (device, stream): a partly filled last round is split over the input channels)
             ws = convs.w4_area(dev) if form == "wino4" else None
-            convs.launch_conv3x3(form, stream, ws, b, h, w, dp, 0, in_bs, cin, ent[1], zero, None, 0, 0, d_feat, 0, c * h * w, 0)
+            convs.launch_conv3x3(form, run.stream, ws, b, h, w, dp, 0, in_bs, cin, ent[1], zero, None, 0, 0, d_feat, 0, c * h * w, 0)
     return d_wx, d_feat
 
 
@@ -414,31 +452,25 @@ def untile_planes(x: torch.Tensor, n: int) -> torch.Tensor:
 
 
 _geometry_cache: "Dict[tuple, dict]" = {}
-GEOMETRY_CACHE_ENTRIES = 8
 
 
 def _geometry(b: int, h: int, w: int, hu: int, wu: int, dev) -> dict:
     """Per-shape constants of the backward pass, built once per (B, LR size, HR size, device): the cell
     rectangles of cell_sum_kernel and the tiled right-hand side (rel_h, rel_w, ratio, 1) of the layer-0
     product.  Training revisits a handful of shapes (one per scale), so a small LRU suffices."""
-    key = (b, h, w, hu, wu, str(dev))
-    geo = _geometry_cache.pop(key, None)
-    if geo is None:
+    def build():
         idx_h, rel_h, idx_w, rel_w, ratio = coordinate_tensors(h, w, hu, wu, dev)
         syn = torch.empty((4, b, hu, wu), dtype=torch.float32, device=dev)
         syn[0] = rel_h[None, :, None]
         syn[1] = rel_w[None, None, :]
         syn[2] = ratio
         syn[3] = 1.0
-        geo = {
+        return {
             "seg_h": torch.searchsorted(idx_h, torch.arange(h + 1, device=dev)).to(torch.int32),
             "seg_w": torch.searchsorted(idx_w, torch.arange(w + 1, device=dev)).to(torch.int32),
             "syn_t": tile_planes(syn.view(4, b * hu * wu)),
         }
-        while len(_geometry_cache) >= GEOMETRY_CACHE_ENTRIES:
-            _geometry_cache.pop(next(iter(_geometry_cache)))
-    _geometry_cache[key] = geo
-    return geo
+    return lru(_geometry_cache, (b, h, w, hu, wu, str(dev)), build)
 
 
 def _sum_parts(part: torch.Tensor) -> torch.Tensor:
@@ -447,10 +479,120 @@ def _sum_parts(part: torch.Tensor) -> torch.Tensor:
     if n % 4 or not part.is_contiguous():
         return part.sum(1)
     out = torch.empty((groups, n), dtype=torch.float32, device=part.device)
-    with torch.cuda.device(part.device):
-        _native.check(_native.load().diinn_sum_parts(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(part.data_ptr()),
-                                                     C.c_void_p(out.data_ptr()), groups, nparts, n), "diinn_sum_parts")
+    with _native.launcher(part.device) as run:
+        run("diinn_sum_parts", part, out, groups, nparts, n)
     return out
+
+
+class ChainPlanes:
+    """The prologue of every per-pixel backward: the shape numbers (b, h, w, hu, wu, n = B*Hu*Wu, t tiles, dev), the check of
+    ``acts``, g_out as planes ``gp`` [3, N] and the empty tiled groups the data kernel fills, ``g`` [4,T,512,32] and ``q`` [4,T,256,32]."""
+
+    def __init__(self, gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, size: Sequence[int]):
+        self.b, _, self.h, self.w = feat.shape
+        self.hu, self.wu = int(size[0]), int(size[1])
+        self.n = n = self.b * self.hu * self.wu
+        self.t = t = (n + PLANE_TILE - 1) // PLANE_TILE
+        self.dev = dev = gout.device
+        if tuple(acts.shape) != (4, t, 2 * HIDDEN, PLANE_TILE) or not acts.is_contiguous():
+            raise ValueError("acts must be the contiguous tiled [4, T, 512, 32] buffer of the training forward")
+        self.gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
+        self.g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+        self.q = torch.empty((4, t, HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
+
+
+def head_rhs(gp: torch.Tensor) -> torch.Tensor:
+    """(g_out ; 0) tiled: the 4-row right-hand side of the 1x1 head's product."""
+    return tile_planes(torch.cat([gp, gp.new_zeros((1, gp.shape[1]))], 0))
+
+
+class ChainStage(ChainPlanes):
+    """The per-pixel chain of a backward pass, stated once for ``backward_fused`` and ``initq_training.backward_fused_initq``.
+
+    ``ChainStage(...)``  the checks and the buffers (``ChainPlanes``; ``geo``: ``_geometry``; the splits; the partials ``part``,
+                         ``part0``, ``partl``), before any launch
+    ``launch(run)``      on the caller's ``run`` (_native.launcher), whose own launches follow in the same block:
+      the data kernel       diinn_backward_data, or _x3 (``split``: the split training image), _head3x3 (``head``: the 3x3 head image;
+                            it also writes dT as seven 4-row groups, row 27 zero) or _qonly followed by diinn_pixel_chain_bwd
+                            (``qonly``): leaves G_i = (g_a,i ; g_s,i) in ``g`` and q_i in ``q`` as tiled planes
+      diinn_plane_gemm_nt   [dWq_i ; dQw_i | bias sums] = G_i [512 x N] . q_{i-1}^T, i = 3, 2, 1 (``qonly``: two 256-row products per
+                            layer, [dKk_i | dbK_i] = g_a,i . k_{i-1}^T on the saved k planes, then [dQw_i | dbQ_i] = g_s,i . q_{i-1}^T)
+      diinn_plane_rowdot    G_0 against (rel_h, rel_w, ratio, 1); q_3 against each 4-row group of the head's right-hand side
+    ``grads(grads)``     the sums of the head's and the layers' partials as gradients; ``layer0()`` those of the layer-0 product."""
+
+    def __init__(self, gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
+                 head: Optional[torch.Tensor] = None, split: Optional[torch.Tensor] = None, qonly: bool = False):
+        super().__init__(gout, feat, acts, size)
+        if qonly and head is not None:
+            raise ValueError("qonly (modes 1/2) and head (mode 4) exclude each other")
+        self.acts, self.packed, self.head, self.split, self.qonly = acts, packed, head, split, qonly
+        n, t = self.n, self.t
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.geo = _geometry(self.b, self.h, self.w, self.hu, self.wu, self.dev)
+        if head is None:
+            self.heads = head_rhs(self.gp)[None]
+        else:
+            # the rowdot reads whole tiles: a ragged last tile's padding is zeroed here
+            self.heads = (torch.empty if n % PLANE_TILE == 0 else torch.zeros)((7, t, 4, PLANE_TILE), **f32)
+        # (qonly: the weight-gradient GEMMs have 256 rows = 2 output blocks; twice the splits make one workgroup per CU, as in backward_fused_modes12)
+        self.ksplit = max(1, min(2 * WGRAD_KSPLIT if qonly else WGRAD_KSPLIT, t))
+        self.rsplit = max(1, min(ROWDOT_SPLITS, t))
+        self.part = torch.empty((6, self.ksplit, HIDDEN, HIDDEN + 1) if qonly else (3, self.ksplit, 2 * HIDDEN, HIDDEN + 1), **f32)
+        self.part0 = torch.empty((self.rsplit, 2 * HIDDEN, 4), **f32)
+        self.partl = torch.empty((len(self.heads), self.rsplit, HIDDEN, 4), **f32)
+
+    def launch(self, run) -> None:
+        gp, acts, packed, g, q, part, n, ksplit = self.gp, self.acts, self.packed, self.g, self.q, self.part, self.n, self.ksplit
+        if self.qonly:
+            run("diinn_backward_data_qonly", gp, acts, packed, g, q, n)
+            run("diinn_pixel_chain_bwd", g, acts, packed, n)
+            for i in (3, 2, 1):
+                run("diinn_plane_gemm_nt", g[i], 2 * HIDDEN, 0, acts[i - 1], 2 * HIDDEN, 0, part[2 * (i - 1)], HIDDEN, HIDDEN, n, ksplit, 1)
+                run("diinn_plane_gemm_nt", g[i], 2 * HIDDEN, HIDDEN, q[i - 1], HIDDEN, 0, part[2 * (i - 1) + 1], HIDDEN, HIDDEN, n, ksplit, 1)
+        else:
+            if self.split is not None:
+                run("diinn_backward_data_x3", gp, acts, packed, self.split, g, q, n)
+            elif self.head is None:
+                run("diinn_backward_data", gp, acts, packed, g, q, n)
+            else:
+                run("diinn_backward_data_head3x3", gp, acts, packed, self.head, g, q, self.heads, self.b, self.hu, self.wu)
+            for i in (3, 2, 1):
+                run("diinn_plane_gemm_nt", g[i], 2 * HIDDEN, 0, q[i - 1], HIDDEN, 0, part[i - 1], 2 * HIDDEN, HIDDEN, n, ksplit, 1)
+        run("diinn_plane_rowdot", g[0], 2 * HIDDEN, self.geo["syn_t"], self.part0, 2 * HIDDEN, n, self.rsplit)
+        for i in range(len(self.heads)):
+            run("diinn_plane_rowdot", q[3], HIDDEN, self.heads[i], self.partl[i], HIDDEN, n, self.rsplit)
+
+    def grads(self, grads: Dict[str, torch.Tensor]):
+        """``last_layer.*`` and ``Q.i.*`` (i = 3, 2, 1) into ``grads``; returns (dWq, dbK), lists whose entries 1..3 are dWq_i [256,256]
+        and dbK_i [256] (entry 0 None: layer 0 is the caller's)."""
+        groups = len(self.heads)
+        dl = _sum_parts(self.partl.view(groups, self.rsplit, -1)).view(groups, HIDDEN, 4)    # group i: q_3 . (rows 4 i .. 4 i + 3 of the right-hand side)^T
+        if self.head is None:
+            head1x1_grads(grads, dl[0], self.gp)
+        else:                                                    # [256, r = 3 (3 ky + kx) + c] -> [c, ch, ky, kx]
+            grads["last_layer.weight"] = dl.permute(1, 0, 2).reshape(HIDDEN, 28)[:, :27].t().reshape(3, 3, 3, HIDDEN).permute(2, 3, 0, 1).contiguous()
+            grads["last_layer.bias"] = self.gp.sum(1)
+        # [3, 512, 257]: [dWq_i ; dQw_i | bias sums] (qonly: the two 256-row products of a layer are neighbours in ``part``: the same view)
+        dws = _sum_parts(self.part.view(self.part.shape[0], self.ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)
+        d_wq: List[Optional[torch.Tensor]] = [None] * 4
+        d_bk: List[Optional[torch.Tensor]] = [None] * 4
+        for i in (3, 2, 1):
+            dw = dws[i - 1]
+            d_wq[i] = dw[:HIDDEN, :HIDDEN]
+            d_bk[i] = dw[:HIDDEN, HIDDEN]
+            grads[f"Q.{i}.0.weight"] = dw[HIDDEN:, :HIDDEN].reshape(HIDDEN, HIDDEN, 1, 1)
+            grads[f"Q.{i}.0.bias"] = dw[HIDDEN:, HIDDEN]
+        return d_wq, d_bk
+
+    def layer0(self) -> torch.Tensor:
+        """[512, 4]: (g_a,0 ; g_s,0) . (rel_h, rel_w, ratio, 1)^T -- column 3 is (dbK_0 ; dbQ_0)."""
+        return _sum_parts(self.part0.view(1, self.rsplit, -1)).view(2 * HIDDEN, 4)
+
+
+def head1x1_grads(grads: Dict[str, torch.Tensor], dl: torch.Tensor, gp: torch.Tensor) -> None:
+    """d last_layer.* of the 1x1 head from ``dl`` [256, 4] = q_3 . (g_out ; 0)^T and the planes of g_out."""
+    grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
+    grads["last_layer.bias"] = gp.sum(1)
 
 
 def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, params: Sequence[torch.Tensor],
@@ -474,82 +616,26 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, p
     have the same layout and everything behind them is the same code.  None: today's fp32 chain."""
     if split is not None and head is not None:
         raise ValueError("the split-bf16 chain covers mode 3 only (no 3x3 head)")
-    lib = _native.load()
     p = dict(zip(PARAM_NAMES, params))
-    b, _, h, w = feat.shape
-    hu, wu = int(size[0]), int(size[1])
-    n = b * hu * wu
-    t = (n + PLANE_TILE - 1) // PLANE_TILE
-    dev = gout.device
-    if tuple(acts.shape) != (4, t, 2 * HIDDEN, PLANE_TILE) or not acts.is_contiguous():
-        raise ValueError("acts must be the contiguous tiled [4, T, 512, 32] buffer of the training forward")
-    geo = _geometry(b, h, w, hu, wu, dev)
-    seg_h, seg_w, syn_t = geo["seg_h"], geo["seg_w"], geo["syn_t"]
-    gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
-    g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    q = torch.empty((4, t, HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    ksplit = max(1, min(WGRAD_KSPLIT, t))
-    rsplit = max(1, min(ROWDOT_SPLITS, t))
-    if head is None:
-        heads = [tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))]     # 4-row right-hand side of the head product
-    else:
-        # dT as seven 4-row groups (row 27 zero), written by bwd_head3x3_kernel; the rowdot reads whole tiles: a ragged last tile's padding is zeroed here
-        heads = (torch.empty if n % PLANE_TILE == 0 else torch.zeros)((7, t, 4, PLANE_TILE), dtype=torch.float32, device=dev)
-    part = torch.empty((3, ksplit, 2 * HIDDEN, HIDDEN + 1), dtype=torch.float32, device=dev)
-    part0 = torch.empty((rsplit, 2 * HIDDEN, 4), dtype=torch.float32, device=dev)
-    partl = torch.empty((len(heads), rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
+    c = ChainStage(gout, feat, acts, packed, size, head=head, split=split)
+    b, h, w, dev = c.b, c.h, c.w, c.dev
     dp = torch.empty((b, 4 * HIDDEN, h, w), dtype=torch.float32, device=dev)
     # the hoisted conv's weight gradient on the library's own GEMM wants dP tiled over the cell axis as well: cell_sum_kernel
     # writes it (a ragged last tile's padding must be zero: the GEMM reads whole tiles)
     cells = b * h * w
     a_t = (torch.empty if cells % PLANE_TILE == 0 else torch.zeros)(((cells + PLANE_TILE - 1) // PLANE_TILE, 4 * HIDDEN, PLANE_TILE),
                                                                     dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if split is not None:
-            _native.check(lib.diinn_backward_data_x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(split), ptr(g), ptr(q), n),
-                          "diinn_backward_data_x3")
-        elif head is None:
-            _native.check(lib.diinn_backward_data(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
-                          "diinn_backward_data")
-        else:
-            _native.check(lib.diinn_backward_data_head3x3(stream, ptr(gp), ptr(acts), ptr(packed), ptr(head), ptr(g), ptr(q), ptr(heads),
-                                                          b, hu, wu), "diinn_backward_data_head3x3")
-        for i in (3, 2, 1):
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, 0, ptr(q[i - 1]), HIDDEN, 0,
-                                                  ptr(part[i - 1]), 2 * HIDDEN, HIDDEN, n, ksplit, 1),
-                          "diinn_plane_gemm_nt")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(g[0]), 2 * HIDDEN, ptr(syn_t), ptr(part0), 2 * HIDDEN, n, rsplit),
-                      "diinn_plane_rowdot")
-        for i, rhs in enumerate(heads):
-            _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(rhs), ptr(partl[i]), HIDDEN, n, rsplit),
-                          "diinn_plane_rowdot")
-        _native.check(lib.diinn_backward_cell_sum(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t), b, h, w, hu, wu),
-                      "diinn_backward_cell_sum")
+    with _native.launcher(dev) as run:
+        c.launch(run)
+        run("diinn_backward_cell_sum", c.g, c.geo["seg_h"], c.geo["seg_w"], dp, a_t, b, h, w, c.hu, c.wu)
     grads: Dict[str, torch.Tensor] = {}
-    dl = _sum_parts(partl.view(len(heads), rsplit, -1)).view(len(heads), HIDDEN, 4)    # group i: q_3 . (rows 4 i .. 4 i + 3 of the right-hand side)^T
-    if head is None:                                             # [256, 4]: q_3 . (g_out ; 0)^T
-        grads["last_layer.weight"] = dl[0, :, :3].t().reshape(3, HIDDEN, 1, 1)
-    else:                                                        # [256, r = 3 (3 ky + kx) + c] -> [c, ch, ky, kx]
-        grads["last_layer.weight"] = dl.permute(1, 0, 2).reshape(HIDDEN, 28)[:, :27].t().reshape(3, 3, 3, HIDDEN).permute(2, 3, 0, 1).contiguous()
-    grads["last_layer.bias"] = gp.sum(1)
-    dws = _sum_parts(part.view(3, ksplit, -1)).view(3, 2 * HIDDEN, HIDDEN + 1)   # [3, 512, 257]: [dWq_i ; dQw_i | bias sums]
-    d_wq: List[Optional[torch.Tensor]] = [None] * 4
-    d_bk: List[Optional[torch.Tensor]] = [None] * 4
-    for i in (3, 2, 1):
-        dw = dws[i - 1]
-        d_wq[i] = dw[:HIDDEN, :HIDDEN]
-        d_bk[i] = dw[:HIDDEN, HIDDEN]
-        grads[f"Q.{i}.0.weight"] = dw[HIDDEN:, :HIDDEN].reshape(HIDDEN, HIDDEN, 1, 1)
-        grads[f"Q.{i}.0.bias"] = dw[HIDDEN:, HIDDEN]
-    d0 = _sum_parts(part0.view(1, rsplit, -1)).view(2 * HIDDEN, 4)   # [512, 4]: (g_a,0 ; g_s,0) . (rel_h, rel_w, ratio, 1)^T
+    d_wq, d_bk = c.grads(grads)
+    d0 = c.layer0()
     d_bk[0] = d0[:HIDDEN, 3]
     grads["Q.0.0.weight"] = d0[HIDDEN:, :3].reshape(HIDDEN, 3, 1, 1)
     grads["Q.0.0.bias"] = d0[HIDDEN:, 3]
     kw = tuple(p[f"K.{i}.0.weight"] for i in range(4))
-    d_wx, d_feat = _conv_grads_native(feat, _hoisted_conv_weight(p), dp, need_feat_grad, wkey=tuple((t.data_ptr(), t._version) for t in kw),
-                                      wpins=kw, a_t=a_t)
+    d_wx, d_feat = _conv_grads_native(feat, _hoisted_conv_weight(p), dp, need_feat_grad, wkey=weights_key(kw), wpins=kw, a_t=a_t)
     _assemble_k_grads(grads, d_wx, d_wq, d_bk)
     return d_feat, [grads[name] for name in PARAM_NAMES]
 
@@ -675,14 +761,7 @@ _cell_ones_cache: Dict[tuple, torch.Tensor] = {}
 def _cell_ones(cells: int, dev) -> torch.Tensor:
     """The tiled 4-row group of ones over ``cells`` cells (zero padding): diinn_plane_rowdot against it sums dP over the cells.
     Kept per (cell count, device) like the geometry constants (one entry per batch geometry of a training run)."""
-    key = (cells, str(dev))
-    ones = _cell_ones_cache.pop(key, None)
-    if ones is None:
-        ones = tile_planes(torch.ones((4, cells), dtype=torch.float32, device=dev))
-        while len(_cell_ones_cache) >= GEOMETRY_CACHE_ENTRIES:
-            _cell_ones_cache.pop(next(iter(_cell_ones_cache)))
-    _cell_ones_cache[key] = ones
-    return ones
+    return lru(_cell_ones_cache, (cells, str(dev)), lambda: tile_planes(torch.ones((4, cells), dtype=torch.float32, device=dev)))
 
 
 def backward_fused_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, chain: torch.Tensor,
@@ -696,73 +775,51 @@ def backward_fused_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.T
       diinn_cell_chain_bwd       the chain backwards: dP (in place of S, and NCHW) and k_0..k_2 tiled over cells
       diinn_plane_gemm_nt        dKk_i = dP_i [256 x cells] . k_{i-1}^T;  diinn_plane_rowdot against ones: dbK = sum of dP over cells
       _conv_grads_native         the 3x3 convolution's gradients from dP (mode 1: layer 0's 256 rows)
-    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward, ``chain`` its [B,H,W,1024] workspace."""
+    ``acts`` is the tiled buffer [4, T, 512, 32] of the training forward, ``chain`` its [B,H,W,1024] workspace.
+    Of ``ChainStage`` this shares the prologue (``ChainPlanes``) and the 1x1 head; its GEMMs take the lower 256 rows of G_i alone and
+    its layer-0 product the lower half-plane."""
     if mode not in (1, 2):
         raise ValueError("backward_fused_modes12 covers decoder modes 1 and 2")
-    lib = _native.load()
     p = dict(zip(PARAM_NAMES, params))
-    b, _, h, w = feat.shape
-    hu, wu = int(size[0]), int(size[1])
-    n = b * hu * wu
-    t = (n + PLANE_TILE - 1) // PLANE_TILE
+    c = ChainPlanes(gout, feat, acts, size)
+    b, h, w, hu, wu, n, t, dev, gp, g, q = c.b, c.h, c.w, c.hu, c.wu, c.n, c.t, c.dev, c.gp, c.g, c.q
     cells = b * h * w
     tc = (cells + PLANE_TILE - 1) // PLANE_TILE
-    dev = gout.device
-    if tuple(acts.shape) != (4, t, 2 * HIDDEN, PLANE_TILE) or not acts.is_contiguous():
-        raise ValueError("acts must be the contiguous tiled [4, T, 512, 32] buffer of the training forward")
     if chain.numel() != cells * 4 * HIDDEN or not chain.is_contiguous():
         raise ValueError("chain must be the contiguous [B,H,W,1024] workspace of the training forward")
     geo = _geometry(b, h, w, hu, wu, dev)
-    seg_h, seg_w, syn_t = geo["seg_h"], geo["seg_w"], geo["syn_t"]
     ones_t = _cell_ones(cells, dev)
-    gp = gout.to(torch.float32).permute(1, 0, 2, 3).reshape(3, n).contiguous()
-    g = torch.empty((4, t, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    q = torch.empty((4, t, HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    gout_t = tile_planes(torch.cat([gp, gp.new_zeros((1, n))], 0))     # 4-row right-hand side of the head product
+    gout_t = head_rhs(gp)
+    f32 = dict(dtype=torch.float32, device=dev)
     # the weight-gradient GEMMs here have 256 rows = 2 output blocks (mode 3's: 512 rows = 4): twice the splits make one workgroup per CU
     ksplit = max(1, min(2 * WGRAD_KSPLIT, t))
     kcsplit = max(1, min(2 * WGRAD_KSPLIT, tc))
     rsplit = max(1, min(ROWDOT_SPLITS, t))
     rcsplit = max(1, min(ROWDOT_SPLITS, tc))
-    part = torch.empty((3, ksplit, HIDDEN, HIDDEN + 1), dtype=torch.float32, device=dev)
-    partk = torch.empty((3, kcsplit, HIDDEN, HIDDEN), dtype=torch.float32, device=dev)
-    part0 = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
-    partl = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
-    partb = torch.empty((2, rcsplit, 2 * HIDDEN, 4), dtype=torch.float32, device=dev)
-    dp = torch.empty((b, 4 * HIDDEN, h, w), dtype=torch.float32, device=dev)
+    part = torch.empty((3, ksplit, HIDDEN, HIDDEN + 1), **f32)
+    partk = torch.empty((3, kcsplit, HIDDEN, HIDDEN), **f32)
+    part0 = torch.empty((rsplit, HIDDEN, 4), **f32)
+    partl = torch.empty((rsplit, HIDDEN, 4), **f32)
+    partb = torch.empty((2, rcsplit, 2 * HIDDEN, 4), **f32)
+    dp = torch.empty((b, 4 * HIDDEN, h, w), **f32)
     alloc = torch.empty if cells % PLANE_TILE == 0 else torch.zeros      # (a ragged last tile's padding stays zero)
-    a_t = alloc((tc, 4 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    k_t = alloc((tc, 3 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    half = 2 * HIDDEN * PLANE_TILE * 4                            # bytes from row 0 to row 512 of a tile of a_t
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_backward_data_qonly(stream, ptr(gp), ptr(acts), ptr(packed), ptr(g), ptr(q), n),
-                      "diinn_backward_data_qonly")
+    a_t = alloc((tc, 4 * HIDDEN, PLANE_TILE), **f32)
+    k_t = alloc((tc, 3 * HIDDEN, PLANE_TILE), **f32)
+    with _native.launcher(dev) as run:
+        run("diinn_backward_data_qonly", gp, acts, packed, g, q, n)
         for i in (3, 2, 1):
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(g[i]), 2 * HIDDEN, HIDDEN, ptr(q[i - 1]), HIDDEN, 0,
-                                                  ptr(part[i - 1]), HIDDEN, HIDDEN, n, ksplit, 1),
-                          "diinn_plane_gemm_nt")
+            run("diinn_plane_gemm_nt", g[i], 2 * HIDDEN, HIDDEN, q[i - 1], HIDDEN, 0, part[i - 1], HIDDEN, HIDDEN, n, ksplit, 1)
         # layer 0: only g_s,0 (rows 256..511 of G_0) meets (rel_h, rel_w, ratio, 1); dbK_0 comes from the chain below
-        _native.check(lib.diinn_plane_rowdot(stream, C.c_void_p(g[0].data_ptr() + HIDDEN * PLANE_TILE * 4), 2 * HIDDEN, ptr(syn_t), ptr(part0),
-                                             HIDDEN, n, rsplit), "diinn_plane_rowdot")
-        _native.check(lib.diinn_plane_rowdot(stream, ptr(q[3]), HIDDEN, ptr(gout_t), ptr(partl), HIDDEN, n, rsplit),
-                      "diinn_plane_rowdot")
-        _native.check(lib.diinn_backward_cell_sum(stream, ptr(g), ptr(seg_h), ptr(seg_w), ptr(dp), ptr(a_t), b, h, w, hu, wu),
-                      "diinn_backward_cell_sum")
-        _native.check(lib.diinn_cell_chain_bwd(stream, ptr(a_t), ptr(chain), ptr(packed), ptr(dp), ptr(a_t), ptr(k_t), b, h, w),
-                      "diinn_cell_chain_bwd")
+        run("diinn_plane_rowdot", (g[0], HIDDEN * PLANE_TILE), 2 * HIDDEN, geo["syn_t"], part0, HIDDEN, n, rsplit)
+        run("diinn_plane_rowdot", q[3], HIDDEN, gout_t, partl, HIDDEN, n, rsplit)
+        run("diinn_backward_cell_sum", g, geo["seg_h"], geo["seg_w"], dp, a_t, b, h, w, hu, wu)
+        run("diinn_cell_chain_bwd", a_t, chain, packed, dp, a_t, k_t, b, h, w)
         for i in (3, 2, 1):
-            _native.check(lib.diinn_plane_gemm_nt(stream, ptr(a_t), 4 * HIDDEN, i * HIDDEN, ptr(k_t), 3 * HIDDEN, (i - 1) * HIDDEN,
-                                                  ptr(partk[i - 1]), HIDDEN, HIDDEN, cells, kcsplit, 0),
-                          "diinn_plane_gemm_nt")
-        for hf in (0, 1):                                        # rows 0..511 and 512..1023 of dP against ones
-            _native.check(lib.diinn_plane_rowdot(stream, C.c_void_p(a_t.data_ptr() + hf * half), 4 * HIDDEN, ptr(ones_t), ptr(partb[hf]),
-                                                 2 * HIDDEN, cells, rcsplit), "diinn_plane_rowdot")
+            run("diinn_plane_gemm_nt", a_t, 4 * HIDDEN, i * HIDDEN, k_t, 3 * HIDDEN, (i - 1) * HIDDEN, partk[i - 1], HIDDEN, HIDDEN, cells, kcsplit, 0)
+        for hf in (0, 1):                                        # rows 0..511 and 512..1023 of dP (of a tile of a_t) against ones
+            run("diinn_plane_rowdot", (a_t, hf * 2 * HIDDEN * PLANE_TILE), 4 * HIDDEN, ones_t, partb[hf], 2 * HIDDEN, cells, rcsplit)
     grads: Dict[str, torch.Tensor] = {}
-    dl = _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4)    # [256, 4]: q_3 . (g_out ; 0)^T
-    grads["last_layer.weight"] = dl[:, :3].t().reshape(3, HIDDEN, 1, 1)
-    grads["last_layer.bias"] = gp.sum(1)
+    head1x1_grads(grads, _sum_parts(partl.view(1, rsplit, -1)).view(HIDDEN, 4), gp)     # [256, 4]: q_3 . (g_out ; 0)^T
     dws = _sum_parts(part.view(3, ksplit, -1)).view(3, HIDDEN, HIDDEN + 1)        # [3, 256, 257]: [dQw_i | dbQ_i]
     dks = _sum_parts(partk.view(3, kcsplit, -1)).view(3, HIDDEN, HIDDEN)          # [3, 256, 256]: dKk_i
     d_bk = _sum_parts(partb.view(2, rcsplit, -1)).view(4, HIDDEN, 4)[:, :, 0]     # [4, 256]: sum of dP_i over the cells
@@ -776,14 +833,13 @@ def backward_fused_modes12(gout: torch.Tensor, feat: torch.Tensor, acts: torch.T
     grads["Q.0.0.bias"] = d0[:, 3]
     kw = tuple(p[f"K.{i}.0.weight"] for i in range(4))
     wx = _hoisted_conv_weight(p, mode)
-    d_wx, d_feat = _conv_grads_native(feat, wx, dp, need_feat_grad, wkey=(mode, *((x.data_ptr(), x._version) for x in kw)),
-                                      wpins=kw, a_t=a_t, rows=wx.shape[0])
+    d_wx, d_feat = _conv_grads_native(feat, wx, dp, need_feat_grad, wkey=(mode, *weights_key(kw)), wpins=kw, a_t=a_t, rows=wx.shape[0])
     _assemble_k_grads_modes12(grads, d_wx, d_kk, d_bk, mode)
     return d_feat, [grads[name] for name in PARAM_NAMES]
 
 
 # ---------------------------------------------------------------------------
-# autograd function
+# autograd functions
 # ---------------------------------------------------------------------------
 def checked_features(feat: torch.Tensor, params: Sequence[torch.Tensor], names: Sequence[str], shapes: Dict[str, Tuple[int, ...]],
                      hu: int, wu: int, plane_rows: int, what: str = "") -> torch.Tensor:
@@ -806,29 +862,53 @@ def checked_features(feat: torch.Tensor, params: Sequence[torch.Tensor], names: 
     return feat_c
 
 
+def named_params(module, names: Sequence[str]) -> List[torch.Tensor]:
+    """``module``'s parameters ``names``, in that order: what a ``decode_with_grad`` hands its Function."""
+    named = dict(module.named_parameters())
+    return [named[name] for name in names]
+
+
+def function_grads(ctx, d_feat: Optional[torch.Tensor], d_params: Sequence[Optional[torch.Tensor]], first: int) -> tuple:
+    """What a training Function's ``backward`` returns: d feat, None for the integers behind it, and from input ``first`` on each
+    parameter's gradient where one was asked for."""
+    need = ctx.needs_input_grad[first:]
+    return (d_feat, *[None] * (first - 1), *[g if nd else None for g, nd in zip(d_params, need)])
+
+
+def train_buffers(feat_c: torch.Tensor, hu: int, wu: int, workspace=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(acts [4,T,512,32], out [B,3,Hu,Wu], workspace) of a training forward on ``feat_c``: empty fp32 buffers on its device.
+    ``workspace``: its float count; None: the hoisted conv's [B,H,W,1024]."""
+    b, _, h, w = feat_c.shape
+    f32 = dict(dtype=torch.float32, device=feat_c.device)
+    acts = torch.empty((4, (b * hu * wu + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), **f32)
+    return acts, torch.empty((b, 3, hu, wu), **f32), torch.empty((b, h, w, 4 * HIDDEN) if workspace is None else workspace, **f32)
+
+
+def train_forward_mode3(feat_c: torch.Tensor, packed: torch.Tensor, hu: int, wu: int, sin_mode: int,
+                        split: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The mode-3 training forward on a contiguous fp32 CUDA ``feat_c`` and its packed image: the hoisted conv on the Winograd
+    kernel (diinn_precompute_P_wpu; the image carries its section, DIINN_PACKED_MAGIC_WPU: ``_fill_wpu``), then decode_kernel<SAVE>
+    (diinn_decode_train_fwd) or, with the split training image ``split``, decode_bf16x3_kernel<SIN | X3_SAVE>
+    (diinn_decode_train_fwd_x3).  Returns (out, acts [4,T,512,32])."""
+    b, _, h, w = feat_c.shape
+    acts, out, workspace = train_buffers(feat_c, hu, wu)
+    with _native.launcher(feat_c.device) as run:
+        run("diinn_precompute_P_wpu", feat_c, packed, workspace, b, h, w, 0, h)
+        if split is None:
+            run("diinn_decode_train_fwd", workspace, packed, out, acts, b, h, w, hu, wu, int(sin_mode))
+        else:
+            run("diinn_decode_train_fwd_x3", workspace, packed, split, out, acts, b, h, w, hu, wu, int(sin_mode))
+    return out, acts
+
+
 class DecodeMode3Function(torch.autograd.Function):
     """out = decoder(feat) on the HIP kernels, differentiable in feat and the 18 parameter tensors."""
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, sin_mode: int, *params: torch.Tensor) -> torch.Tensor:
-        lib = _native.load()
         feat_c = checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, 2 * HIDDEN, " for decoder mode 3")
-        b, c, h, w = feat_c.shape
-        n = b * hu * wu
-        dev = feat_c.device
         packed = pack_on_device(params)
-        workspace = torch.empty(b * h * w * 4 * HIDDEN, dtype=torch.float32, device=dev)
-        acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-        out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            # the hoisted conv on the Winograd kernel: the image carries its section (DIINN_PACKED_MAGIC_WPU: _fill_wpu)
-            _native.check(lib.diinn_precompute_P_wpu(stream, C.c_void_p(feat_c.data_ptr()), C.c_void_p(packed.data_ptr()),
-                                                     C.c_void_p(workspace.data_ptr()), b, h, w, 0, h), "diinn_precompute_P_wpu")
-            _native.check(lib.diinn_decode_train_fwd(stream, C.c_void_p(workspace.data_ptr()),
-                                                     C.c_void_p(packed.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                     C.c_void_p(acts.data_ptr()), b, h, w, hu, wu, int(sin_mode)),
-                          "diinn_decode_train_fwd")
+        out, acts = train_forward_mode3(feat_c, packed, hu, wu, sin_mode)
         ctx.save_for_backward(feat_c, acts, packed, *[p_.detach() for p_ in params])
         ctx.size = (hu, wu)
         return out
@@ -838,29 +918,20 @@ class DecodeMode3Function(torch.autograd.Function):
         feat, acts, packed, *params = ctx.saved_tensors
         d_feat, d_params = backward_fused(gout.contiguous(), feat, acts, params, packed, ctx.size,
                                           need_feat_grad=ctx.needs_input_grad[0])
-        need = ctx.needs_input_grad[4:]
-        return (d_feat, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return function_grads(ctx, d_feat, d_params, 4)
 
 
 def train_forward_modes12(feat_c: torch.Tensor, params: Sequence[torch.Tensor], hu: int, wu: int, sin_mode: int, mode: int):
     """The modes-1/2 training forward on a contiguous fp32 CUDA ``feat_c``: the hoisted conv (diinn_precompute_P_wpu), the per-cell
     chain (diinn_cell_chain), decode_kernel<SIN, KPART=false, SAVE> (diinn_decode_train_fwd_qonly).
     Returns (out, acts [4,T,512,32], chain workspace [B,H,W,1024], packed image)."""
-    lib = _native.load()
-    b, c, h, w = feat_c.shape
-    n = b * hu * wu
-    dev = feat_c.device
+    b, _, h, w = feat_c.shape
     packed = pack_on_device(params, mode)
-    chain = torch.empty((b, h, w, 4 * HIDDEN), dtype=torch.float32, device=dev)
-    acts = torch.empty((4, (n + PLANE_TILE - 1) // PLANE_TILE, 2 * HIDDEN, PLANE_TILE), dtype=torch.float32, device=dev)
-    out = torch.empty((b, 3, hu, wu), dtype=torch.float32, device=dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr())                      # noqa: E731
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.diinn_precompute_P_wpu(stream, ptr(feat_c), ptr(packed), ptr(chain), b, h, w, 0, h), "diinn_precompute_P_wpu")
-        _native.check(lib.diinn_cell_chain(stream, ptr(chain), ptr(packed), b, h, w, 0, h), "diinn_cell_chain")
-        _native.check(lib.diinn_decode_train_fwd_qonly(stream, ptr(chain), ptr(packed), ptr(out), ptr(acts), b, h, w, hu, wu,
-                                                       int(sin_mode)), "diinn_decode_train_fwd_qonly")
+    acts, out, chain = train_buffers(feat_c, hu, wu)
+    with _native.launcher(feat_c.device) as run:
+        run("diinn_precompute_P_wpu", feat_c, packed, chain, b, h, w, 0, h)
+        run("diinn_cell_chain", chain, packed, b, h, w, 0, h)
+        run("diinn_decode_train_fwd_qonly", chain, packed, out, acts, b, h, w, hu, wu, int(sin_mode))
     return out, acts, chain, packed
 
 
@@ -882,14 +953,12 @@ class DecodeModes12Function(torch.autograd.Function):
         feat, acts, chain, packed, *params = ctx.saved_tensors
         d_feat, d_params = backward_fused_modes12(gout.contiguous(), feat, acts, chain, params, packed, ctx.size, ctx.mode,
                                                   need_feat_grad=ctx.needs_input_grad[0])
-        need = ctx.needs_input_grad[5:]
-        return (d_feat, None, None, None, None, *[g if nd else None for g, nd in zip(d_params, need)])
+        return function_grads(ctx, d_feat, d_params, 5)
 
 
 def decode_with_grad(decoder, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """``ImplicitDecoder.forward(x, size, None)`` under autograd (modes 1, 2 and 3; mode 4: mode4_training.decode_with_grad)."""
-    named = dict(decoder.named_parameters())
-    params = [named[name] for name in PARAM_NAMES]
+    params = named_params(decoder, PARAM_NAMES)
     hu, wu = size
     if decoder.mode in (1, 2):
         return DecodeModes12Function.apply(feat, int(hu), int(wu), int(decoder.sin_mode), int(decoder.mode), *params)
