@@ -522,6 +522,33 @@ def metasr_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Seque
     return _comparison_decode("diinn_metasr_decode", _native.load().diinn_metasr_workspace_bytes, feat, packed, size, out, workspace)
 
 
+def metasr_decode_hoisted(feat: torch.Tensor, packed: torch.Tensor, image: torch.Tensor, size: Sequence[int],
+                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                          rows: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The same MetaSR query in the hoisted form (``metasr_training``'s docstring; opt-in, not the reference's bits): the 3x3 conv
+    [M; B0] of the whole map per LR cell (``diinn_precompute_P_wpu`` on ``image``, the DIINN-shaped training image of
+    ``metasr_training.images_on_device``, into ``workspace``: ``diinn_workspace_bytes(B,H,W)`` bytes, replaced if too small),
+    then ``diinn_metasr_decode_hoisted`` on ``packed`` (the MetaSR image of the same call; its W1 / b1 rows).  ``rows=(y0,y1)``
+    writes only that HR row window of a full-size ``out``.  Measured faster than the direct decode at every scale tried, x0.33 to x4
+    (17x at 256 x 256 x4, 1.1x below x1: DESIGN.md §3.8, profiles/metasr_hoisted_times.txt)."""
+    _require_cuda(feat, "feat")
+    _require_cuda(packed, "packed weights")
+    _require_cuda(image, "training image")
+    feat, (b, h, w) = _checked_feat(feat)
+    hu, wu = int(size[0]), int(size[1])
+    y0, y1 = (0, hu) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= y0 <= y1 <= hu:
+        raise ValueError(f"rows must satisfy 0 <= y0 <= y1 <= {hu}, got ({y0}, {y1})")
+    out = _checked_out(out, (b, 3, hu, wu), feat.device)
+    need = _native.load().diinn_workspace_bytes(b, h, w)
+    if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
+    with _native.launcher(feat.device) as run:
+        run("diinn_precompute_P_wpu", feat, image, workspace, b, h, w, 0, h)
+        run("diinn_metasr_decode_hoisted", workspace, packed, out, b, h, w, hu, wu, y0, y1)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # nn.Module mirror of the reference class
 # ---------------------------------------------------------------------------

@@ -21,7 +21,8 @@ g = d loss / d out:
     d_feat = conv3x3([S; G]; the conv's weight transposed and flipped).
 
   forward   the inference kernels (``metasr_decode_features``: the output under grad is the no_grad output bit for bit),
-            plus M on ``diinn_precompute_P_wpu`` from a training image gathered on the device.
+            plus M on ``diinn_precompute_P_wpu`` from a training image gathered on the device.  With ``MetaSR.hip_hoisted`` the
+            output comes from that M instead (``metasr_decode_hoisted``, again the no_grad call itself): metasr_kernel is not run.
   backward  ``metasr_bwd_cells_kernel`` (C ABI ``diinn_metasr_backward_cells``): everything per pixel, leaving [S; G] in both of
             cell_sum_kernel's layouts and the layer-0 partials; then ``training._conv_grads_native`` -- unfold + plane GEMM for
             dW2 / db2, the encoder's convolution kernels for d_feat -- and ``diinn_sum_parts``.  No framework convolution or GEMM.
@@ -228,24 +229,32 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, m: torch.Tensor, pack
     return d_feat, [d0[:, :3].contiguous(), d0[:, 3].contiguous(), d_w2, d_b2]
 
 
+def _function_forward(ctx, hoisted: bool, feat: torch.Tensor, hu: int, wu: int, params: Sequence[torch.Tensor]) -> torch.Tensor:
+    from .decoder import metasr_decode_features, metasr_decode_hoisted
+    feat_c = T.checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, ROWS)
+    b, _, h, w = feat_c.shape
+    packed, image, wx = images_on_device(params)
+    if hoisted:                                                  # the inference call itself: M into m, the pixels from m
+        m = torch.empty((b, h, w, ROWS), dtype=torch.float32, device=feat_c.device)
+        out = metasr_decode_hoisted(feat_c, packed, image, (hu, wu), workspace=m.view(-1))
+    else:
+        out = metasr_decode_features(feat_c, packed, (hu, wu))
+        m = torch.empty((b, h, w, ROWS), dtype=torch.float32, device=feat_c.device)
+        with _native.launcher(feat_c.device) as run:
+            run("diinn_precompute_P_wpu", feat_c, image, m, b, h, w, 0, h)
+    ctx.save_for_backward(feat_c, m, packed, wx)
+    ctx.size = (hu, wu)
+    ctx.wkey = ("metasr", *((p_.data_ptr(), p_._version) for p_ in params[2:]))
+    ctx.wpins = tuple(params[2:])
+    return out
+
+
 class MetaSRFunction(torch.autograd.Function):
     """out = MetaSR decoder(feat) on the HIP kernels, differentiable in feat and the four imnet tensors (PARAM_NAMES order)."""
 
     @staticmethod
     def forward(ctx, feat: torch.Tensor, hu: int, wu: int, *params: torch.Tensor) -> torch.Tensor:
-        from .decoder import metasr_decode_features
-        feat_c = T.checked_features(feat, params, PARAM_NAMES, PARAM_SHAPES, hu, wu, ROWS)
-        b, _, h, w = feat_c.shape
-        packed, image, wx = images_on_device(params)
-        out = metasr_decode_features(feat_c, packed, (hu, wu))
-        m = torch.empty((b, h, w, ROWS), dtype=torch.float32, device=feat_c.device)
-        with _native.launcher(feat_c.device) as run:
-            run("diinn_precompute_P_wpu", feat_c, image, m, b, h, w, 0, h)
-        ctx.save_for_backward(feat_c, m, packed, wx)
-        ctx.size = (hu, wu)
-        ctx.wkey = ("metasr", *((p_.data_ptr(), p_._version) for p_ in params[2:]))
-        ctx.wpins = tuple(params[2:])
-        return out
+        return _function_forward(ctx, False, feat, hu, wu, params)
 
     @staticmethod
     def backward(ctx, gout: torch.Tensor):
@@ -256,7 +265,17 @@ class MetaSRFunction(torch.autograd.Function):
         return T.function_grads(ctx, d_feat, d_params, 3)
 
 
-def decode_with_grad(imnet, feat: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
+class MetaSRHoistedFunction(MetaSRFunction):
+    """The same function with the forward in the hoisted form (``decoder.metasr_decode_hoisted``: M by diinn_precompute_P_wpu as
+    above, the output from M by diinn_metasr_decode_hoisted; diinn_metasr_decode is not launched).  The backward is the same."""
+
+    @staticmethod
+    def forward(ctx, feat: torch.Tensor, hu: int, wu: int, *params: torch.Tensor) -> torch.Tensor:
+        return _function_forward(ctx, True, feat, hu, wu, params)
+
+
+def decode_with_grad(imnet, feat: torch.Tensor, size: Sequence[int], hoisted: bool = False) -> torch.Tensor:
     """``MetaSR.query_rgb`` + ``reshape_pred`` of every HR pixel under autograd; ``imnet`` is the model's meta-network (modules.MLP)."""
     hu, wu = size
-    return MetaSRFunction.apply(feat, int(hu), int(wu), *T.named_params(imnet, PARAM_NAMES))
+    fn = MetaSRHoistedFunction if hoisted else MetaSRFunction
+    return fn.apply(feat, int(hu), int(wu), *T.named_params(imnet, PARAM_NAMES))

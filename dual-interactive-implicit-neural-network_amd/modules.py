@@ -280,7 +280,7 @@ class _GraphReplay:
                 getattr(dec, "sin_mode", None), getattr(dec, "compute", None), getattr(dec, "mode", None),
                 getattr(enc, "hip_trunk_max_pixels", None), getattr(enc, "hip_winograd", None),
                 getattr(enc, "hip_split_bf16", None), getattr(enc, "hip_winograd4", None),
-                getattr(dec, "hip_modes_split_bf16", None))
+                getattr(dec, "hip_modes_split_bf16", None), getattr(self, "hip_hoisted", None))
 
     def _forward_graphed(self, x, size, bsize):
         key = self._graph_key(x, size)
@@ -301,7 +301,7 @@ class _GraphReplay:
                 # private pool: workspaces, activations, the result) or kept alive by the entry below (packed
                 # weight images, which live in module caches that a later call may replace)
                 static_y = self._forward_eager(static_x, size, bsize)
-            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_packed_head", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2")]
+            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_packed_head", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2", "_hoisted_images")]
             entry = (graph, static_x, static_y, keep)
             self._graph_cache[key] = entry
         graph, static_x, static_y = entry[:3]
@@ -469,15 +469,27 @@ class MetaSR(nn.Module, _GraphReplay):
     HIP path (``metasr_kernel``).  Under autograd with ``bsize=None`` -- the reference's training call, sr_module.py:127-129 --
     the decoder runs through ``metasr_training.MetaSRFunction`` (the same forward kernels, the per-cell backward on the HIP
     kernels; ROCm GPU only).  With ``bsize`` given the reference decodes under no_grad (``batched_predict``, metasr.py:106-117):
-    the output carries no graph, and ``bsize`` itself, a memory knob, is ignored.  Graph replay is inference-only."""
+    the output carries no graph, and ``bsize`` itself, a memory knob, is ignored.  Graph replay is inference-only.
 
-    def __init__(self, graphs: bool = False):
+    ``hip_hoisted`` (a plain attribute, also a constructor keyword; default False; not in the reference): the decoder in its hoisted
+    form -- the 3x3 conv [M; B0] per LR cell (``diinn_precompute_P_wpu``), then ``metasr_hoisted_kernel`` turns M into pixels
+    (``decoder.metasr_decode_hoisted``) -- in inference and, under autograd, as the forward of ``MetaSRHoistedFunction`` (the same two
+    launches on the same device-gathered image: the output under grad is the no_grad output bit for bit; the backward is
+    unchanged).  The output is within the reference tolerance but not metasr_kernel's bits, which the fixtures pin: hence a
+    switch.  Measured (profiles/metasr_hoisted_times.txt): decode 17x and training step 4x faster at x4,
+    2x / 1.5x at x1, 1.1x / 1.3x when down-scaling; no scale was found at which the direct kernel wins."""
+
+    hip_hoisted = False
+
+    def __init__(self, graphs: bool = False, hip_hoisted: bool = False):
         super().__init__()
         self._init_graphs(graphs)
+        self.hip_hoisted = bool(hip_hoisted)
         self.encoder = make_rdn()
         self.imnet = MLP(3, self.encoder.out_dim * 9 * 3, [256])
         self._packed = None
         self._packed_key = None
+        self._hoisted_images = None                              # (packed, image, wx) of the last hoisted decode: a graph entry keeps them
 
     def gen_feat(self, inp):
         self.feat = self.encoder(inp)
@@ -492,15 +504,22 @@ class MetaSR(nn.Module, _GraphReplay):
         return self._packed
 
     def _forward_eager(self, inp, size, bsize=None):
-        from .decoder import metasr_decode_features
+        from .decoder import metasr_decode_features, metasr_decode_hoisted
         feat = self.gen_feat(inp)
+        if self.hip_hoisted:
+            from .metasr_training import PARAM_NAMES, images_on_device
+            from .training import named_params
+            # (gathered on the device, cached per weight version in a cache that may evict them: the module holds on to them)
+            self._hoisted_images = images_on_device(named_params(self.imnet, PARAM_NAMES))
+            packed, image, _ = self._hoisted_images
+            return metasr_decode_hoisted(feat, packed, image, size)
         return metasr_decode_features(feat, self._packed_weights(feat.device), size)
 
     def _forward_train(self, inp, size):
         from .metasr_training import decode_with_grad
         if not inp.is_cuda:
             raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
-        return decode_with_grad(self.imnet, self.gen_feat(inp), size)
+        return decode_with_grad(self.imnet, self.gen_feat(inp), size, hoisted=self.hip_hoisted)
 
     def forward(self, inp, size, bsize=None):
         if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in self.parameters())):

@@ -728,6 +728,21 @@ int    diinn_metasr_make_axis_tables(int n_in, int n_out, int32_t* idx, float* r
 int    diinn_metasr_backward_cells(void* stream, const float* gout_dev, const float* M_dev, const float* packed_dev,
                                    const int32_t* seg_h_dev, const int32_t* seg_w_dev, float* dM_dev, float* dM_tiled_dev,
                                    float* part0_dev, int B, int H, int W, int Hu, int Wu);
+/* MetaSR in the hoisted form (added under ABI 11, backward compatible): the pixels from the same convolution output,
+ *     out[comp] = sum_j h_j M[c][comp][j] + B0[c][comp],   h = relu(W1 (rel_h, rel_w, r_rev) + b1),
+ * in place of diinn_metasr_decode's per-pixel meta-network (~3.6 kFLOP per pixel instead of 885 kFLOP).  Given
+ *   M_dev [B,H,W,1024] fp32, 16-byte aligned, the layout diinn_precompute_P_wpu writes and diinn_metasr_backward_cells reads:
+ *   rows 256 comp + j hold M, rows 768 + comp hold B0, rows 771..1023 are not read;  packed_dev the MetaSR packed image (only
+ *   its W1 / b1 rows are read),
+ * it writes HR rows [y0, y1) of out_dev, a contiguous [B,3,Hu,Wu] fp32 tensor: every element of the window once, nothing outside
+ * it.  The pixel's cell and (rel_h, rel_w, r_rev) are diinn_metasr_make_axis_tables', and a_j is computed as metasr_kernel does
+ * (fma(w_r, r_rev, b), fma(w_w, rel_w, .), fma(w_h, rel_h, .)), so the ReLU mask is the one the backward recomputes, bit for
+ * bit.  The sum runs over j in order, then + B0; no atomics: deterministic.  One kernel; every argument is validated first
+ * (DIINN_ERR_INVALID_ARG: a null pointer, a non-positive size, not 0 <= y0 <= y1 <= Hu, a misaligned M_dev; DIINN_ERR_TOO_LARGE:
+ * the limits of diinn_metasr_decode and more than 65,535 blocks of 16 rows in the window); y0 == y1 is a no-op that returns
+ * DIINN_OK.  Allocates nothing, does not synchronise, capture-safe. */
+int    diinn_metasr_decode_hoisted(void* stream, const float* M_dev, const float* packed_dev, float* out_dev,
+                                   int B, int H, int W, int Hu, int Wu, int y0, int y1);
 
 /* ---- RDN encoder trunk ------------------------------------
  * Replaces: RDN.forward after SFENet1 (rdn.py:95-105), config 'B' (16 RDBs x 8 dense 3x3 convs, growth 64,
