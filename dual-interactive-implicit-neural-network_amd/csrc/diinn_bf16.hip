@@ -1232,31 +1232,19 @@ int launch_decode_bf16(void* stream, const DecodeParams& p, int gx, int gy, int 
             if (nst > 0x7fffffffLL) return DIINN_ERR_TOO_LARGE;
             pc.pg[5] = (int)((nst + 7) / 8);
             const dim3 gridp(CO_PGRID);
-            if (sin_mode == DIINN_SIN_HW)
-                hipLaunchKernelGGL(decode_bf16_coop8p_kernel<DIINN_SIN_HW>, gridp, dim3(512), 0, (hipStream_t)stream, pc);
-            else
-                hipLaunchKernelGGL(decode_bf16_coop8p_kernel<DIINN_SIN_HW_REDUCED>, gridp, dim3(512), 0, (hipStream_t)stream, pc);
-        } else if (coop) {                                        // one block per workgroup (DIINN_BF16_KERNEL=8)
-            if (sin_mode == DIINN_SIN_HW)
-                hipLaunchKernelGGL(decode_bf16_coop8_kernel<DIINN_SIN_HW>, grid, dim3(512), 0, (hipStream_t)stream, pc);
-            else if (sin_mode == DIINN_SIN_HW_REDUCED)
-                hipLaunchKernelGGL(decode_bf16_coop8_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(512), 0, (hipStream_t)stream, pc);
-            else
-                hipLaunchKernelGGL(decode_bf16_coop8_kernel<DIINN_SIN_ACCURATE>, grid, dim3(512), 0, (hipStream_t)stream, pc);
-        } else if (!((force == 1 || force == 2) ? force == 2 : two_tiles)) {
-            if (sin_mode == DIINN_SIN_HW)
-                hipLaunchKernelGGL(decode_bf16_kernel<DIINN_SIN_HW>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-            else if (sin_mode == DIINN_SIN_HW_REDUCED)
-                hipLaunchKernelGGL(decode_bf16_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-            else
-                hipLaunchKernelGGL(decode_bf16_kernel<DIINN_SIN_ACCURATE>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-        } else {
-            if (sin_mode == DIINN_SIN_HW)
-                hipLaunchKernelGGL(decode_bf16x2_kernel<DIINN_SIN_HW>, grid2, dim3(blk), 0, (hipStream_t)stream, p);
-            else if (sin_mode == DIINN_SIN_HW_REDUCED)
-                hipLaunchKernelGGL(decode_bf16x2_kernel<DIINN_SIN_HW_REDUCED>, grid2, dim3(blk), 0, (hipStream_t)stream, p);
-            else
-                hipLaunchKernelGGL(decode_bf16x2_kernel<DIINN_SIN_ACCURATE>, grid2, dim3(blk), 0, (hipStream_t)stream, p);
+            return launch_sin_of<DIINN_SIN_HW, DIINN_SIN_HW_REDUCED>(sin_mode, [&](auto S) {   // (never ACCURATE: not instantiated)
+                hipLaunchKernelGGL(decode_bf16_coop8p_kernel<decltype(S)::value>, gridp, dim3(512), 0, (hipStream_t)stream, pc);
+            });
         }
-            return hip_status(hipGetLastError());
+        if (coop)                                                 // one block per workgroup (DIINN_BF16_KERNEL=8)
+            return launch_sin(sin_mode, [&](auto S) {
+                hipLaunchKernelGGL(decode_bf16_coop8_kernel<decltype(S)::value>, grid, dim3(512), 0, (hipStream_t)stream, pc);
+            });
+        if (!((force == 1 || force == 2) ? force == 2 : two_tiles))
+            return launch_sin(sin_mode, [&](auto S) {
+                hipLaunchKernelGGL(decode_bf16_kernel<decltype(S)::value>, grid, dim3(blk), 0, (hipStream_t)stream, p);
+            });
+        return launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL(decode_bf16x2_kernel<decltype(S)::value>, grid2, dim3(blk), 0, (hipStream_t)stream, p);
+        });
 }

@@ -91,10 +91,7 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 // [B][p.Orows rows from p.Orow0][Wu][TAP_STRIDE].  The head table (27 x 256 floats from p.head3) sits behind the Q0 rows of
 // `tab`; mode 4's bias and both validity words belong to head3x3_reflect_kernel, which follows unchanged.
 // Both flags ride in SIN_X like X3_INITQ and X3_SAVE; both are one-block forms only.
-constexpr int X3_INITQ = 4;
-constexpr int X3_SAVE = 8;
-constexpr int X3_QONLY = 16;
-constexpr int X3_TAPS = 32;
+// (X3_INITQ = 4, X3_SAVE = 8, X3_QONLY = 16, X3_TAPS = 32: diinn_device.h, beside launch_decode_bf16x3_form)
 typedef f32x4 __attribute__((may_alias)) f32x4_lds;
 template <int SIN_X>
 __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParams p) {
@@ -818,67 +815,18 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
         DecodeParams pc = p;
         pc.pg[0] = gx; pc.pg[1] = gy; pc.pg[2] = gz;
         const dim3 gridp((unsigned)(nblk < pgrid ? nblk : pgrid));
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL(decode_bf16x3h_kernel<DIINN_SIN_HW>, gridp, dim3(256), 0, (hipStream_t)stream, pc);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL(decode_bf16x3h_kernel<DIINN_SIN_HW_REDUCED>, gridp, dim3(256), 0, (hipStream_t)stream, pc);
-        else
-            hipLaunchKernelGGL(decode_bf16x3h_kernel<DIINN_SIN_ACCURATE>, gridp, dim3(256), 0, (hipStream_t)stream, pc);
-        return hip_status(hipGetLastError());
+        return launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL(decode_bf16x3h_kernel<decltype(S)::value>, gridp, dim3(256), 0, (hipStream_t)stream, pc);
+        });
     }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
+    return launch_sin(sin_mode, [&](auto S) {
+        hipLaunchKernelGGL(decode_bf16x3_kernel<decltype(S)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
-// init_q (mode 3): `p.P` = the pixel planes of HR rows [p.y0, p.y1) (p.Prow0 = p.y0); the one-block form (see X3_INITQ)
-int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
-    const dim3 grid(gx, gy, gz);
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
-}
-
-// mode 3 under autograd (diinn_decode_train_fwd_x3): one workgroup per four plane tiles; p.split = the split training image
-int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned blocks, int sin_mode) {
-    const dim3 grid(blocks);
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_SAVE>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
-}
-
-// modes 1/2 in split bf16 (diinn_decode_qonly_x3*): P holds the per-cell chain (cell_chain_kernel); the one-block form only
-int launch_decode_bf16x3_qonly(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
-    const dim3 grid(gx, gy, gz);
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_QONLY>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
-}
-
-// mode 4 in split bf16 (diinn_decode_mode4_x3*): the tap form; p.out = the tap buffer, p.head3 = the head image; the one-block form only
-int launch_decode_bf16x3_taps(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode) {
-    const dim3 grid(gx, gy, gz);
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_HW_REDUCED | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_bf16x3_kernel<DIINN_SIN_ACCURATE | X3_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
+// the forms the flags of SIN_X select (diinn_device.h lists what each reads from p); the one-block kernel only
+int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form) {
+    return launch_sin<X3_INITQ, X3_SAVE, X3_QONLY, X3_TAPS>(sin_mode, form, [&](auto S, auto F) {
+        hipLaunchKernelGGL(decode_bf16x3_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }

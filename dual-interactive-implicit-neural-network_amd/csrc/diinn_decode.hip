@@ -708,32 +708,28 @@ __global__ __launch_bounds__(256, 1) void pixel_chain_kernel(const PixChainParam
 }
 
 static int pixel_chain_impl(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, bool bk_seeds) {
-    if (!pix_dev || !packed_dev) return DIINN_ERR_INVALID_ARG;
+    if (!all_set(pix_dev, packed_dev)) return DIINN_ERR_INVALID_ARG;
     if (B <= 0 || Wu <= 0 || rows <= 0) return DIINN_ERR_INVALID_ARG;
     if ((((size_t)pix_dev) | ((size_t)packed_dev)) & 15) return DIINN_ERR_INVALID_ARG;      // 16-byte seeds and pieces
-    if ((double)rows * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    const dim3 grid((Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X),
-                    (rows + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y), B);
-    if (grid.y > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
+    if (int st = check_extent(rows, Wu)) return st;
+    const dim3 grid(grid_blocks(0, Wu, WG_W), grid_blocks(0, rows, WG_H), B);
+    if (int st = check_grid(grid.y, B)) return st;
     const PixChainParams p{pix_dev, packed_dev, B, Wu, rows};
-    if (bk_seeds) hipLaunchKernelGGL(pixel_chain_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(pixel_chain_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    pick<1, 0>(bk_seeds, [&](auto S) {
+        hipLaunchKernelGGL(pixel_chain_kernel<decltype(S)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
     return hip_status(hipGetLastError());
 }
 
-
 static int cell_chain_impl(void* stream, float* P_dev, const float* packed_dev, int B, int H, int W, int r0, int r1,
                            RowWin pw) {
-    if (!P_dev || !packed_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
+    if (!all_set(P_dev, packed_dev)) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_dims(B, H, W)) return st;
     if (r0 < 0 || r1 > H || r0 >= r1) return DIINN_ERR_INVALID_ARG;
-    st = check_window(pw.row0, pw.rows, H, r0, r1);
-    if (st) return st;
+    if (int st = check_window(pw.row0, pw.rows, H, r0, r1)) return st;
     ChainParams p{P_dev, packed_dev, B, H, W, r0, r1, pw.row0, pw.rows};
-    const dim3 grid((W + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X),
-                    (r1 - r0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y), B);
-    if (grid.y > 65535) return DIINN_ERR_TOO_LARGE;
+    const dim3 grid(grid_blocks(0, W, WG_W), grid_blocks(r0, r1, WG_H), B);
+    if (int st = check_grid(grid.y, B)) return st;
     hipLaunchKernelGGL(cell_chain_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }
@@ -743,6 +739,27 @@ static int cell_chain_impl(void* stream, float* P_dev, const float* packed_dev, 
 struct OutView { int row0, rows, col0; long long bs, ps, rs; };
 static inline OutView contig(RowWin ow, int Wu) {
     return OutView{ow.row0, ow.rows, 0, 3LL * ow.rows * Wu, (long long)ow.rows * Wu, (long long)Wu};
+}
+
+// The one place a DecodeParams is filled: HR rows [y0,y1) x columns [x0,x1) of the Hu x Wu image of a B x H x W map, P holding
+// rows `pw` (LR rows of the hoisted conv -- or HR rows, where P is init_q's pixel planes), the pixels going to `ov`.  Every
+// member a launch does not name is zero: the caller adds what is its own (acts / npix, head3, split, the stamp buffer) and
+// the bf16 launchers their seed_cols / xcd_runs / pg.
+static DecodeParams decode_params(const float* P_dev, const float* packed_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                                  int y0, int y1, int x0, int x1, RowWin pw, OutView ov) {
+    DecodeParams p{};
+    p.P = P_dev; p.Wt = packed_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = y0; p.y1 = y1;
+    p.Prow0 = pw.row0; p.Prows = pw.rows; p.Orow0 = ov.row0; p.Orows = ov.rows;
+    p.x0 = x0; p.x1 = x1; p.Ocol0 = ov.col0; p.o_bs = ov.bs; p.o_ps = ov.ps; p.o_rs = ov.rs;
+    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
+    const int small = diinn_uses_small_output_kernel(Hu, Wu);
+    p.ah = make_axis(H, Hu, small);
+    p.aw = make_axis(W, Wu, small);
+    return p;
+}
+static inline dim3 decode_grid(int B, int y0, int y1, int x0, int x1) {   // workgroups of 16 x 8 pixels anchored at (x0, y0)
+    return dim3(grid_blocks(x0, x1, WG_W), grid_blocks(y0, y1, WG_H), B);
 }
 
 // HR rows [y0,y1) x columns [x0,x1) of the image, every arithmetic mode.  Blocks are anchored at (x0, y0); no pixel's
@@ -757,94 +774,60 @@ static inline OutView contig(RowWin ow, int Wu) {
 // A-B timing).
 struct F32Choice { int kernel; dim3 grid; };
 static F32Choice f32_kernel_choice(int B, int y0, int y1, int x0, int x1) {
-    const int gx = (x1 - x0 + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    const int gy = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
+    const dim3 grid = decode_grid(B, y0, y1, x0, x1);
     const int force = (int)knob(diinn_knobs().f32_kernel);
     const int ncu = device_cus();
-    const dim3 grid16((x1 - x0 + T16_W - 1) / T16_W, (y1 - y0 + T16_H - 1) / T16_H, B);
-    const double t16 = (double)grid16.x * grid16.y * grid16.z, rounds = (double)(((long long)gx * gy * B + ncu - 1) / ncu);
+    const dim3 grid16(grid_blocks(x0, x1, T16_W), grid_blocks(y0, y1, T16_H), B);
+    const double t16 = (double)grid16.x * grid16.y * grid16.z, rounds = (double)(((long long)grid.x * grid.y * B + ncu - 1) / ncu);
     const bool cheaper16 = 0.0896 * t16 * (256.0 / ncu) + 25.0 < 181.1 * rounds + 3.0;
     if (grid16.y <= 65535 && (force ? force == 3 : cheaper16)) return F32Choice{DIINN_DECODE_KERNEL_LATENCY16, grid16};
-    return F32Choice{DIINN_DECODE_KERNEL_THROUGHPUT, dim3(gx, gy, B)};
+    return F32Choice{DIINN_DECODE_KERNEL_THROUGHPUT, grid};
 }
 
 static int decode_tile_impl(void* stream, const float* P_dev, const float* packed_dev,
                             float* out_dev, int B, int H, int W, int Hu, int Wu,
                             int y0, int y1, int x0, int x1, int sin_mode, int compute, RowWin pw, OutView ov,
                             bool x3q = false) {
-    if (!compute_ok(compute))
-        return DIINN_ERR_UNSUPPORTED;
-    if (!P_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1 || x0 < 0 || x1 > Wu || x0 >= x1) return DIINN_ERR_INVALID_ARG;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    {
-        int r0, r1;
-        st = diinn_lr_rows_for_band(H, Hu, Wu, y0, y1, &r0, &r1);
-        if (st) return st;
-        st = check_window(pw.row0, pw.rows, H, r0, r1);
-        if (st) return st;
-        st = check_window(ov.row0, ov.rows, Hu, y0, y1);
-        if (st) return st;
-    }
+    if (!compute_ok(compute)) return DIINN_ERR_UNSUPPORTED;      // (this entry point's order: the arithmetic first)
+    if (!all_set(P_dev, packed_dev, out_dev)) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_dims(B, H, W)) return st;
+    if (int st = check_band(Hu, Wu, y0, y1)) return st;
+    if (x0 < 0 || x1 > Wu || x0 >= x1) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_extent(Hu, Wu)) return st;
+    int r0, r1;
+    if (int st = diinn_lr_rows_for_band(H, Hu, Wu, y0, y1, &r0, &r1)) return st;
+    if (int st = check_window(pw.row0, pw.rows, H, r0, r1)) return st;
+    if (int st = check_window(ov.row0, ov.rows, Hu, y0, y1)) return st;
     // strides: a row holds the tile's columns, a plane its rows, a batch item its three planes (no overlap); < 2^40 floats
     if (ov.col0 < 0 || ov.col0 > x0 || ov.rs < (long long)(x1 - ov.col0) || ov.ps < ov.rs * (y1 - ov.row0 - 1) + (x1 - ov.col0) ||
         ov.bs < 2 * ov.ps + ov.rs * (y1 - ov.row0 - 1) + (x1 - ov.col0) || ov.bs > (1LL << 40))
         return DIINN_ERR_INVALID_ARG;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    const int gx = (x1 - x0 + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    const int gy = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    const int gz = B, blk = 256;
-    if (gy > 65535 || gz > 65535) return DIINN_ERR_TOO_LARGE;   // HIP grid.y / grid.z limits
-    DecodeParams p;
-    p.P = P_dev; p.Wt = packed_dev; p.out = out_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = y0; p.y1 = y1;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = pw.row0; p.Prows = pw.rows; p.Orow0 = ov.row0; p.Orows = ov.rows;
-    p.x0 = x0; p.x1 = x1; p.Ocol0 = ov.col0; p.o_bs = ov.bs; p.o_ps = ov.ps; p.o_rs = ov.rs;
-    p.acts = nullptr; p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
+    if (int st = check_sin(sin_mode)) return st;
+    const dim3 grid = decode_grid(B, y0, y1, x0, x1);
+    if (int st = check_grid(grid.y, grid.z)) return st;
+    DecodeParams p = decode_params(P_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, x0, x1, pw, ov);
 #ifdef DIINN_STAMPS
     p.stamps = g_stamps;
 #endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    const dim3 grid(gx, gy, gz);
     if (compute == DIINN_COMPUTE_BF16 || compute == DIINN_COMPUTE_BF16_FULL)
-        return launch_decode_bf16(stream, p, gx, gy, gz, sin_mode);
+        return launch_decode_bf16(stream, p, grid.x, grid.y, grid.z, sin_mode);
     if (compute == DIINN_COMPUTE_BF16X3)
-        return launch_decode_bf16x3(stream, p, gx, gy, gz, sin_mode);
-    if (compute == DIINN_COMPUTE_F32_QONLY && x3q)              // modes 1/2, the synthesis branch in split bf16: decode_bf16x3_kernel<SIN | X3_QONLY>
-        return launch_decode_bf16x3_qonly(stream, p, gx, gy, gz, sin_mode);
-    if (compute == DIINN_COMPUTE_F32_QONLY) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, false>), grid, dim3(blk), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, false>), grid, dim3(blk), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, false>), grid, dim3(blk), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
+        return launch_decode_bf16x3(stream, p, grid.x, grid.y, grid.z, sin_mode);
+    if (compute == DIINN_COMPUTE_F32_QONLY && x3q)              // modes 1/2, the synthesis branch in split bf16
+        return launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_QONLY);
+    if (compute == DIINN_COMPUTE_F32_QONLY)
+        return launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL((decode_kernel<decltype(S)::value, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        });
     // Which of the two fp32 kernels (bit-equal: tests/test_gpu_parity.py::test_latency_kernel_is_bit_identical_...)?
     const F32Choice ch = f32_kernel_choice(B, y0, y1, x0, x1);
-    if (ch.kernel == DIINN_DECODE_KERNEL_LATENCY16) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL(decode_coop16_kernel<DIINN_SIN_HW>, ch.grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL(decode_coop16_kernel<DIINN_SIN_HW_REDUCED>, ch.grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL(decode_coop16_kernel<DIINN_SIN_ACCURATE>, ch.grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_ACCURATE>, grid, dim3(blk), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
+    if (ch.kernel == DIINN_DECODE_KERNEL_LATENCY16)
+        return launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL(decode_coop16_kernel<decltype(S)::value>, ch.grid, dim3(256), 0, (hipStream_t)stream, p);
+        });
+    return launch_sin(sin_mode, [&](auto S) {
+        hipLaunchKernelGGL(decode_kernel<decltype(S)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 static int decode_band_impl(void* stream, const float* P_dev, const float* packed_dev,
@@ -929,53 +912,43 @@ __global__ __launch_bounds__(256) void head3x3_reflect_kernel(const Head3Params 
     o[2 * plane] = a2;
 }
 
-// Mode 4, HR rows [y0,y1) of the image from P: the tap form of decode_kernel over the extended rows [ty0,ty1), then the gather.
-// `ow`: the rows `out_dev` holds.  fp32: the throughput kernel only (no 16-pixel latency twin); x3: the tap form of the split-bf16
-// kernel, decode_bf16x3_kernel<SIN | X3_TAPS>, in its place (the same tap buffer, the same gather).
+// Mode 4, HR rows [y0,y1) of the image: the tap form over the extended rows [ty0,ty1) into the tap buffer, then the gather.
+// `ow`: the rows `out_dev` holds.  `pw`: the LR rows P_dev holds -- or NULL: P_dev is init_q's pixel planes of exactly the tap
+// rows (decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS>).  From P in fp32: the throughput kernel's tap form (no 16-pixel latency
+// twin); x3: the tap form of the split-bf16 kernel, decode_bf16x3_kernel<SIN | X3_TAPS>, in its place (the same tap buffer, the
+// same gather).
 static int decode_mode4_band_impl(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
                                   float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                                  int sin_mode, RowWin pw, RowWin ow, bool x3 = false) {
-    if (!P_dev || !packed_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
+                                  int sin_mode, const RowWin* pw, RowWin ow, bool x3 = false) {
+    if (!all_set(P_dev, packed_dev, head_dev, taps_dev, out_dev)) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_dims(B, H, W)) return st;
     int ty0, ty1, r0, r1;
-    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);      // Hu, Wu >= 2 and 0 <= y0 < y1 <= Hu
-    if (st) return st;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    st = check_window(pw.row0, pw.rows, H, r0, r1);
-    if (st) return st;
-    st = check_window(ow.row0, ow.rows, Hu, y0, y1);
-    if (st) return st;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    const int gy = (ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    const dim3 hgrid((Wu + H3_BLOCK_W - 1) / H3_BLOCK_W, (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H, B);
-    if (gy > 65535 || hgrid.y > 65535) return DIINN_ERR_TOO_LARGE;
-    DecodeParams p;
-    p.P = P_dev; p.Wt = packed_dev; p.out = taps_dev; p.head3 = head_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = ty0; p.y1 = ty1;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = pw.row0; p.Prows = pw.rows; p.Orow0 = ty0; p.Orows = ty1 - ty0;      // rows of the tap buffer
-    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_bs = 0; p.o_ps = 0; p.o_rs = 0;           // (unused by the tap form)
-    p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
-#ifdef DIINN_STAMPS
-    p.stamps = nullptr;
-#endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    const dim3 grid(gx, gy, B);
-    if (x3) {
-        st = launch_decode_bf16x3_taps(stream, p, gx, gy, B, sin_mode);
-        if (st) return st;
-    } else if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    if (int st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1)) return st;      // Hu, Wu >= 2 and 0 <= y0 < y1 <= Hu
+    if (int st = check_extent(Hu, Wu)) return st;
+    const RowWin taprows{ty0, ty1 - ty0};
+    if (pw)
+        if (int st = check_window(pw->row0, pw->rows, H, r0, r1)) return st;
+    if (int st = check_window(ow.row0, ow.rows, Hu, y0, y1)) return st;
+    if (int st = check_sin(sin_mode)) return st;
+    const dim3 grid = decode_grid(B, ty0, ty1, 0, Wu);
+    const dim3 hgrid(grid_blocks(0, Wu, H3_BLOCK_W), grid_blocks(y0, y1, H3_BLOCK_H), B);
+    if (int st = check_grid(grid.y, B)) return st;
+    if (int st = check_grid(hgrid.y, B)) return st;
+    // the tap buffer holds the tap rows; the tap form does not use the output strides
+    DecodeParams p = decode_params(P_dev, packed_dev, taps_dev, B, H, W, Hu, Wu, ty0, ty1, 0, Wu, pw ? *pw : taprows,
+                                   OutView{taprows.row0, taprows.rows, 0, 0, 0, 0});
+    p.head3 = head_dev;
+    int st;
+    if (x3)
+        st = launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_TAPS);
+    else if (pw)
+        st = launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL((decode_kernel<decltype(S)::value, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        });
     else
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    st = hip_status(hipGetLastError());
+        st = launch_sin(sin_mode, [&](auto S) {
+            hipLaunchKernelGGL(decode_kernel<decltype(S)::value | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        });
     if (st) return st;
     const Head3Params hp{taps_dev, packed_dev, head_dev, out_dev, Hu, Wu, y0, y1, ty0, ty1 - ty0, ow.row0, ow.rows};
     hipLaunchKernelGGL(head3x3_reflect_kernel, hgrid, dim3(256), 0, (hipStream_t)stream, hp);
@@ -1002,118 +975,34 @@ int launch_head3x3_whole(void* stream, const float* taps_dev, const float* head_
 }
 
 // init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
-// The throughput kernel only (no 16-pixel latency twin).  kpart = false: modes 1/2, the planes hold the per-pixel chain (diinn_pixel_chain).
+// The throughput kernel only (no 16-pixel latency twin).  kpart = false: modes 1/2, the planes hold the per-pixel chain
+// (diinn_pixel_chain).  x3: split bf16, decode_bf16x3_kernel<SIN | X3_INITQ>.
 static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
                                   int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool kpart = true,
                                   bool x3 = false) {
-    if (!pix_dev || !packed_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    const int gy = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    if (gy > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
-    const OutView ov = contig(RowWin{0, Hu}, Wu);
-    DecodeParams p;
-    p.P = pix_dev; p.Wt = packed_dev; p.out = out_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = y0; p.y1 = y1;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = y0; p.Prows = y1 - y0; p.Orow0 = ov.row0; p.Orows = ov.rows;          // P = the pixel planes: HR rows
-    p.x0 = 0; p.x1 = Wu; p.Ocol0 = ov.col0; p.o_bs = ov.bs; p.o_ps = ov.ps; p.o_rs = ov.rs;
-    p.acts = nullptr; p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
-#ifdef DIINN_STAMPS
-    p.stamps = nullptr;
-#endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    if (x3) return launch_decode_bf16x3_initq(stream, p, gx, gy, B, sin_mode);   // split bf16: decode_bf16x3_kernel<SIN | X3_INITQ>
-    const dim3 grid(gx, gy, B);
-    if (!kpart) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
+    if (int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, pix_dev, packed_dev, out_dev)) return st;
+    const dim3 grid = decode_grid(B, y0, y1, 0, Wu);
+    if (int st = check_grid(grid.y, B)) return st;
+    const DecodeParams p = decode_params(pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, 0, Wu,
+                                         RowWin{y0, y1 - y0}, contig(RowWin{0, Hu}, Wu));      // P = the pixel planes: HR rows
+    if (x3) return launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_INITQ);
+    return launch_sin<0, 1>(sin_mode, kpart, [&](auto S, auto K) {
+        hipLaunchKernelGGL((decode_kernel<decltype(S)::value | DECODE_INITQ, decltype(K)::value>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
-// init_q with mode 4: HR rows [y0,y1) from the pixel planes of the tap rows [ty0,ty1) = [max(0, y0-1), min(Hu, y1+1)): the tap form
-// decode_kernel<SIN | DECODE_INITQ | DECODE_TAPS> over those rows into the tap buffer of decode_mode4_band_impl's layout, then the same
-// gather.  out_dev is a contiguous [B,3,Hu,Wu].
-static int decode_initq_mode4_band_impl(void* stream, const float* pix_dev, const float* packed_dev, const float* head_dev,
-                                        float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                                        int sin_mode) {
-    if (!pix_dev || !packed_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    int ty0, ty1, r0, r1;
-    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);      // Hu, Wu >= 2 and 0 <= y0 < y1 <= Hu
-    if (st) return st;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    const int gx = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    const int gy = (ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    const dim3 hgrid((Wu + H3_BLOCK_W - 1) / H3_BLOCK_W, (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H, B);
-    if (gy > 65535 || hgrid.y > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
-    DecodeParams p;
-    p.P = pix_dev; p.Wt = packed_dev; p.out = taps_dev; p.head3 = head_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = ty0; p.y1 = ty1;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = ty0; p.Prows = ty1 - ty0; p.Orow0 = ty0; p.Orows = ty1 - ty0;         // the pixel planes and the tap buffer: the tap rows
-    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_bs = 0; p.o_ps = 0; p.o_rs = 0;           // (unused by the tap form)
-    p.npix = 0; p.seed_cols = 0; p.xcd_runs = 0;                                    // (p.acts shares p.head3's storage: left alone)
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
-#ifdef DIINN_STAMPS
-    p.stamps = nullptr;
-#endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    const dim3 grid(gx, gy, B);
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ | DECODE_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    st = hip_status(hipGetLastError());
-    if (st) return st;
-    const Head3Params hp{taps_dev, packed_dev, head_dev, out_dev, Hu, Wu, y0, y1, ty0, ty1 - ty0, 0, Hu};
-    hipLaunchKernelGGL(head3x3_reflect_kernel, hgrid, dim3(256), 0, (hipStream_t)stream, hp);
-    return hip_status(hipGetLastError());
-}
-
-// The launches of an init_q entry point all validate alike; the "all in order" entries check everything a later launch would
-// refuse BEFORE the first launch, so that a bad argument launches nothing.
-static int initq_args_ok(const void* a, const void* b, const void* c, const void* d, const void* e,
-                         int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
-    if (!a || !b || !c || !d || !e) return DIINN_ERR_INVALID_ARG;
-    const int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    if (B > 65535 || (y1 - y0 + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
-    return DIINN_OK;
+// The "all in order" init_q entry points check everything a later launch would refuse BEFORE the first launch, so that a bad
+// argument launches nothing: the band checks, then the grid of every launch over HR rows [y0,y1) (row tiles of 8 all).
+template <class... T>
+static int initq_args_ok(int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, const T*... ptrs) {
+    if (int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, ptrs...)) return st;
+    return check_grid(grid_blocks(y0, y1, WG_H), B);
 }
 
 static int decode_initq_mode12(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                                float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode,
                                bool rows512) {
-    int st = initq_args_ok(feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    int st = initq_args_ok(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, pix_dev, out_dev);
     if (st) return st;
     if ((((size_t)pix_dev) | ((size_t)packed_dev)) & 15) return DIINN_ERR_INVALID_ARG;
     st = launch_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, rows512);
@@ -1121,6 +1010,75 @@ static int decode_initq_mode12(void* stream, const float* feat_dev, const float*
     st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, y1 - y0, rows512);
     if (st) return st;
     return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+// The training forward's checks after the pointers (its own order: the sine mode before the extent); npix = B Hu Wu
+static int check_train_args(int B, int H, int W, int Hu, int Wu, int sin_mode, long long* npix) {
+    if (int st = check_dims(B, H, W)) return st;
+    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_sin(sin_mode)) return st;
+    if (int st = check_extent(Hu, Wu)) return st;
+    *npix = (long long)B * Hu * Wu;
+    return check_npix(*npix);
+}
+
+// The training forward's per-pixel layers over the whole image, one workgroup per four plane tiles: P_dev holds rows `pw` -- the
+// hoisted conv (or, kpart = false, the per-cell chain) of all H LR rows, or (initq) the pixel planes of all Hu HR rows, in
+// radians.  split_dev (mode 3 from P only): the split training image -- decode_bf16x3_kernel<SIN | X3_SAVE> runs the layers.
+static int train_fwd_launch(void* stream, const float* P_dev, const float* packed_dev, float* out_dev, float* acts_dev,
+                            int B, int H, int W, int Hu, int Wu, long long npix, int sin_mode, RowWin pw, bool initq, bool kpart,
+                            const float* split_dev = nullptr) {
+    const dim3 grid((unsigned)((npix + 4 * PLANE_TILE - 1) / (4 * PLANE_TILE)));
+    DecodeParams p = decode_params(P_dev, packed_dev, out_dev, B, H, W, Hu, Wu, 0, Hu, 0, Wu, pw, contig(RowWin{0, Hu}, Wu));
+    p.acts = acts_dev; p.npix = npix;
+    if (split_dev) {
+        p.split = split_dev;
+        return launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_SAVE);
+    }
+    int st = DIINN_ERR_UNSUPPORTED;
+    pick<0, DECODE_INITQ>(initq ? DECODE_INITQ : 0, [&](auto Q) {
+        st = launch_sin<0, 1>(sin_mode, kpart, [&](auto S, auto K) {
+            hipLaunchKernelGGL((decode_kernel<decltype(S)::value | decltype(Q)::value, decltype(K)::value, true>), grid, dim3(256), 0,
+                               (hipStream_t)stream, p);
+        });
+    });
+    return st;
+}
+
+// The training forward, KPART = true (mode 3) or false (modes 1/2: P_dev holds the per-cell chain, diinn_cell_chain)
+static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
+                          float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode, bool kpart,
+                          const float* split_dev = nullptr) {
+    if (!all_set(P_dev, packed_dev, out_dev, acts_dev)) return DIINN_ERR_INVALID_ARG;
+    long long npix;
+    if (int st = check_train_args(B, H, W, Hu, Wu, sin_mode, &npix)) return st;
+    return train_fwd_launch(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, npix, sin_mode, RowWin{0, H}, false, kpart,
+                            split_dev);
+}
+
+// init_q (mode 3) under autograd: the pixel planes of the WHOLE image in radians (initq_planes_kernel<SIN | INITQ_RAD> on the init_q
+// training image), then decode_kernel<SIN | DECODE_INITQ, true, SAVE>: acts in diinn_decode_train_fwd's layout, s_0 in radians.
+// chain: 0 = mode 3; 1 / 2 = modes 1/2 (pixel_chain_kernel over all Hu rows between the planes and the layers, KPART = false),
+// 2 with the chain's layers 1..3 seeded from bK_i of the body image (diinn_pixel_chain's bk_seeds)
+static int initq_train_fwd_impl(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode,
+                                int chain) {
+    if (!all_set(feat_dev, packed_dev, train_image_dev, pix_dev, out_dev, acts_dev)) return DIINN_ERR_INVALID_ARG;
+    long long npix;
+    int st = check_train_args(B, H, W, Hu, Wu, sin_mode, &npix);
+    if (st) return st;
+    if ((((size_t)packed_dev) | ((size_t)train_image_dev) | ((size_t)pix_dev)) & 15) return DIINN_ERR_INVALID_ARG;   // 16-byte pieces and seeds
+    // (what the two launches in front of decode_kernel would refuse: checked before the first of them)
+    st = check_grid(grid_blocks(0, Hu, WG_H), B);
+    if (st) return st;
+    st = launch_initq_planes(stream, feat_dev, packed_dev, train_image_dev, pix_dev, B, H, W, Hu, Wu, 0, Hu, sin_mode, true);
+    if (st) return st;
+    if (chain) {
+        st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, Hu, chain == 2);
+        if (st) return st;
+    }
+    return train_fwd_launch(stream, pix_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, npix, sin_mode, RowWin{0, Hu}, true,
+                            chain == 0);
 }
 
 extern "C" {
@@ -1144,25 +1102,28 @@ int diinn_decode_initq_mode2(void* stream, const float* feat_dev, const float* p
     return decode_initq_mode12(stream, feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
 }
 
+// init_q with mode 4: the pixel planes hold the tap rows [ty0,ty1) = [max(0, y0-1), min(Hu, y1+1)); out_dev is a contiguous [B,3,Hu,Wu]
 int diinn_decode_initq_mode4_band(void* stream, const float* pix_dev, const float* packed_dev, const float* head_dev,
                                   float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                                   int sin_mode) {
-    return decode_initq_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    return decode_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
+                                  nullptr, RowWin{0, Hu});
 }
 
 int diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                              const float* head_dev, float* pix_dev, float* taps_dev, float* out_dev,
                              int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
-    if (!head_dev || !taps_dev) return DIINN_ERR_INVALID_ARG;
-    int st = initq_args_ok(feat_dev, packed_dev, initq_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (!all_set(head_dev, taps_dev)) return DIINN_ERR_INVALID_ARG;
+    int st = initq_args_ok(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, pix_dev, out_dev);
     if (st) return st;
     int ty0, ty1, r0, r1;
     st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
     if (st) return st;
-    if ((ty1 - ty0 + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
+    st = check_grid(grid_blocks(ty0, ty1, WG_H), B);
+    if (st) return st;
     st = diinn_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, ty0, ty1, sin_mode);
     if (st) return st;
-    return decode_initq_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    return diinn_decode_initq_mode4_band(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
 }
 
 int diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
@@ -1196,38 +1157,29 @@ int diinn_decode_initq(void* stream, const float* feat_dev, const float* packed_
 int diinn_decode_mode4_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
                             float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                             int sin_mode) {
+    const RowWin full{0, H};
     return decode_mode4_band_impl(stream, P_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
-                                  RowWin{0, H}, RowWin{0, Hu});
+                                  &full, RowWin{0, Hu});
 }
 
 int diinn_decode_mode4(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
                        float* workspace_dev, float* taps_dev, float* out_dev,
                        int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
-    if (!workspace_dev || !head_dev || !taps_dev || !out_dev) return DIINN_ERR_INVALID_ARG;
+    if (!all_set(workspace_dev, head_dev, taps_dev, out_dev)) return DIINN_ERR_INVALID_ARG;
     int ty0, ty1, r0, r1;
     int st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
     if (st) return st;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
+    st = check_sin(sin_mode);
+    if (st) return st;
     const RowWin full{0, H};
     st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, r0, r1, 16, 0, &full, &full, true);
     if (st) return st;
     return decode_mode4_band_impl(stream, workspace_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1,
-                                  sin_mode, full, RowWin{0, Hu});
+                                  sin_mode, &full, RowWin{0, Hu});
 }
 
 // ---- decoder modes 1, 2 and 4 in split-bf16 arithmetic (include/diinn_hip.h; opt-in: ImplicitDecoder.hip_modes_split_bf16) ----
-// what every launch of these entry points would refuse, checked before the first of them
-static int modes_x3_args_ok(const void* a, const void* b, const void* c, const void* d, int B, int H, int W, int Hu, int Wu,
-                            int y0, int y1, int sin_mode) {
-    if (!a || !b || !c || !d) return DIINN_ERR_INVALID_ARG;
-    const int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    return DIINN_OK;
-}
-
+// (what every launch of these entry points would refuse is checked before the first of them: check_band_args, then the grids)
 int diinn_decode_qonly_x3_band(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
                                int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
     return decode_band_impl(stream, P_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, DIINN_COMPUTE_F32_QONLY,
@@ -1236,9 +1188,10 @@ int diinn_decode_qonly_x3_band(void* stream, const float* P_dev, const float* pa
 
 int diinn_decode_qonly_x3(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev, float* out_dev,
                           int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
-    const int st = modes_x3_args_ok(feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, workspace_dev, out_dev);
     if (st) return st;
-    if ((y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y) > 65535) return DIINN_ERR_TOO_LARGE;
+    st = check_grid(grid_blocks(y0, y1, WG_H), B);
+    if (st) return st;
     // P and the per-cell chain in fp32 (DIINN_COMPUTE_F32_QONLY's), the per-pixel layers on decode_bf16x3_kernel<SIN | X3_QONLY>
     return decode_impl(stream, feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
                        DIINN_COMPUTE_F32_QONLY, RowWin{0, H}, RowWin{0, H}, RowWin{0, Hu}, true);
@@ -1247,27 +1200,30 @@ int diinn_decode_qonly_x3(void* stream, const float* feat_dev, const float* pack
 int diinn_decode_mode4_x3_band(void* stream, const float* P_dev, const float* packed_dev, const float* head_dev,
                                float* taps_dev, float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
                                int sin_mode) {
+    const RowWin full{0, H};
     return decode_mode4_band_impl(stream, P_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
-                                  RowWin{0, H}, RowWin{0, Hu}, true);
+                                  &full, RowWin{0, Hu}, true);
 }
 
 int diinn_decode_mode4_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* head_dev,
                           float* workspace_dev, float* taps_dev, float* out_dev,
                           int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
-    if (!head_dev || !taps_dev) return DIINN_ERR_INVALID_ARG;
-    int st = modes_x3_args_ok(feat_dev, packed_dev, workspace_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    if (!all_set(head_dev, taps_dev)) return DIINN_ERR_INVALID_ARG;
+    int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, workspace_dev, out_dev);
     if (st) return st;
     int ty0, ty1, r0, r1;
     st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
     if (st) return st;
-    if ((ty1 - ty0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y) > 65535 || (y1 - y0 + H3_BLOCK_H - 1) / H3_BLOCK_H > 65535)
-        return DIINN_ERR_TOO_LARGE;
+    st = check_grid(grid_blocks(ty0, ty1, WG_H), B);
+    if (st) return st;
+    st = check_grid(grid_blocks(y0, y1, H3_BLOCK_H), B);
+    if (st) return st;
     const RowWin full{0, H};
     // the hoisted conv as DIINN_COMPUTE_BF16X3 runs it for mode 3 (split bf16 on large maps, the fp32 Winograd form below)
     st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, r0, r1, 16, p_arith(DIINN_COMPUTE_BF16X3), &full, &full, true);
     if (st) return st;
     return decode_mode4_band_impl(stream, workspace_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1,
-                                  sin_mode, full, RowWin{0, Hu}, true);
+                                  sin_mode, &full, RowWin{0, Hu}, true);
 }
 
 int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B, int H, int W, int r0, int r1) {
@@ -1276,26 +1232,22 @@ int diinn_cell_chain(void* stream, float* P_dev, const float* packed_dev, int B,
 
 int diinn_decode_launch_info(int B, int Hu, int Wu, int y0, int y1,
                              int* grid_x, int* grid_y, int* grid_z, int* block) {
-    if (B <= 0 || Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
-    if (grid_x) *grid_x = (Wu + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    if (grid_y) *grid_y = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    if (grid_z) *grid_z = B;
+    if (B <= 0 || check_band(Hu, Wu, y0, y1)) return DIINN_ERR_INVALID_ARG;
+    const dim3 grid = decode_grid(B, y0, y1, 0, Wu);
+    if (grid_x) *grid_x = (int)grid.x;
+    if (grid_y) *grid_y = (int)grid.y;
+    if (grid_z) *grid_z = (int)grid.z;
     if (block) *block = 256;
     return DIINN_OK;
 }
 
 int diinn_decode_kernel_info(int B, int Hu, int Wu, int y0, int y1, int x0, int x1, int compute, int info[4]) {
-    if (!info || B <= 0 || Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1 || x0 < 0 || x1 > Wu || x0 >= x1) return DIINN_ERR_INVALID_ARG;
+    if (!info || B <= 0 || check_band(Hu, Wu, y0, y1) || x0 < 0 || x1 > Wu || x0 >= x1) return DIINN_ERR_INVALID_ARG;
     if (!compute_ok(compute)) return DIINN_ERR_UNSUPPORTED;
-    if (compute == DIINN_COMPUTE_F32) {
-        const F32Choice ch = f32_kernel_choice(B, y0, y1, x0, x1);
-        info[0] = ch.kernel; info[1] = (int)ch.grid.x; info[2] = (int)ch.grid.y; info[3] = (int)ch.grid.z;
-        return DIINN_OK;
-    }
-    info[0] = compute == DIINN_COMPUTE_F32_QONLY ? DIINN_DECODE_KERNEL_THROUGHPUT : DIINN_DECODE_KERNEL_OTHER;
-    info[1] = (x1 - x0 + TILE_W * WG_TILES_X - 1) / (TILE_W * WG_TILES_X);
-    info[2] = (y1 - y0 + TILE_H * WG_TILES_Y - 1) / (TILE_H * WG_TILES_Y);
-    info[3] = B;
+    F32Choice ch{compute == DIINN_COMPUTE_F32_QONLY ? DIINN_DECODE_KERNEL_THROUGHPUT : DIINN_DECODE_KERNEL_OTHER,
+                 decode_grid(B, y0, y1, x0, x1)};
+    if (compute == DIINN_COMPUTE_F32) ch = f32_kernel_choice(B, y0, y1, x0, x1);
+    info[0] = ch.kernel; info[1] = (int)ch.grid.x; info[2] = (int)ch.grid.y; info[3] = (int)ch.grid.z;
     return DIINN_OK;
 }
 
@@ -1330,57 +1282,6 @@ int diinn_decode_tile_win(void* stream, const float* P_win_dev, int p_row0, int 
                             OutView{y0, y1 > y0 ? y1 - y0 : 1, x0, out_batch_stride, out_plane_stride, out_row_stride});
 }
 
-// The training forward, KPART = true (mode 3) or false (modes 1/2: P_dev holds the per-cell chain, diinn_cell_chain)
-// split_dev (mode 3 only): the split training image -- the per-pixel layers run on decode_bf16x3_kernel<SIN | X3_SAVE>
-static int train_fwd_impl(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
-                          float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode, bool kpart,
-                          const float* split_dev = nullptr) {
-    if (!P_dev || !packed_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    const long long npix = (long long)B * Hu * Wu;
-    st = check_npix(npix);
-    if (st) return st;
-    const dim3 grid((unsigned)((npix + 4 * PLANE_TILE - 1) / (4 * PLANE_TILE)));
-    DecodeParams p;
-    p.P = P_dev; p.Wt = packed_dev; p.out = out_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = 0; p.y1 = Hu;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = 0; p.Prows = H; p.Orow0 = 0; p.Orows = Hu;
-    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_rs = Wu; p.o_ps = (long long)Hu * Wu; p.o_bs = 3 * p.o_ps;
-    p.acts = acts_dev; p.npix = npix; p.seed_cols = 0; p.xcd_runs = 0;
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
-#ifdef DIINN_STAMPS
-    p.stamps = nullptr;
-#endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    if (split_dev) {
-        p.split = split_dev;
-        return launch_decode_bf16x3_save(stream, p, grid.x, sin_mode);
-    }
-    if (!kpart) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
-}
-
 int diinn_decode_train_fwd(void* stream, const float* P_dev, const float* packed_dev, float* out_dev,
                            float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
     return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true);
@@ -1390,64 +1291,6 @@ int diinn_decode_train_fwd_x3(void* stream, const float* P_dev, const float* pac
                               float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
     if (!split_dev || (((size_t)split_dev) & 15)) return DIINN_ERR_INVALID_ARG;     // 16-byte weight pieces
     return train_fwd_impl(stream, P_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, true, split_dev);
-}
-
-// init_q (mode 3) under autograd: the pixel planes of the WHOLE image in radians (initq_planes_kernel<SIN | INITQ_RAD> on the init_q
-// training image), then decode_kernel<SIN | DECODE_INITQ, true, SAVE>: acts in diinn_decode_train_fwd's layout, s_0 in radians.
-// chain: 0 = mode 3; 1 / 2 = modes 1/2 (pixel_chain_kernel over all Hu rows between the planes and the layers, KPART = false),
-// 2 with the chain's layers 1..3 seeded from bK_i of the body image (diinn_pixel_chain's bk_seeds)
-static int initq_train_fwd_impl(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
-                                float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode,
-                                int chain) {
-    if (!feat_dev || !packed_dev || !train_image_dev || !pix_dev || !out_dev || !acts_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    const long long npix = (long long)B * Hu * Wu;
-    st = check_npix(npix);
-    if (st) return st;
-    if ((((size_t)packed_dev) | ((size_t)train_image_dev) | ((size_t)pix_dev)) & 15) return DIINN_ERR_INVALID_ARG;   // 16-byte pieces and seeds
-    // (what the two launches in front of decode_kernel would refuse: checked before the first of them)
-    if (B > 65535 || (Hu + 7) / 8 > 65535) return DIINN_ERR_TOO_LARGE;
-    st = launch_initq_planes(stream, feat_dev, packed_dev, train_image_dev, pix_dev, B, H, W, Hu, Wu, 0, Hu, sin_mode, true);
-    if (st) return st;
-    if (chain) {
-        st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, Hu, chain == 2);
-        if (st) return st;
-    }
-    const dim3 grid((unsigned)((npix + 4 * PLANE_TILE - 1) / (4 * PLANE_TILE)));
-    DecodeParams p;
-    p.P = pix_dev; p.Wt = packed_dev; p.out = out_dev;
-    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = 0; p.y1 = Hu;
-    p.ratio = (float)(((double)H * (double)W) / ((double)Hu * (double)Wu));
-    p.Prow0 = 0; p.Prows = Hu; p.Orow0 = 0; p.Orows = Hu;          // P = the pixel planes: HR rows
-    p.x0 = 0; p.x1 = Wu; p.Ocol0 = 0; p.o_rs = Wu; p.o_ps = (long long)Hu * Wu; p.o_bs = 3 * p.o_ps;
-    p.acts = acts_dev; p.npix = npix; p.seed_cols = 0; p.xcd_runs = 0;
-    for (int i = 0; i < 6; ++i) p.pg[i] = 0;
-#ifdef DIINN_STAMPS
-    p.stamps = nullptr;
-#endif
-    const int small = diinn_uses_small_output_kernel(Hu, Wu);
-    p.ah = make_axis(H, Hu, small);
-    p.aw = make_axis(W, Wu, small);
-    if (chain) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_HW_REDUCED | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL((decode_kernel<DIINN_SIN_ACCURATE | DECODE_INITQ, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
 }
 
 int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,

@@ -339,6 +339,59 @@ static inline int check_npix(long long npix) {
     return DIINN_OK;
 }
 
+// The argument checks of the decode launch functions, as pieces: an entry point calls them in ITS order (the status of a call
+// with two faults is part of the ABI: tests/golden/entry_refusals.json), check_band_args() is the order most of them share.
+template <class... T>
+static inline bool all_set(const T*... ptrs) { return (... && (ptrs != nullptr)); }
+static inline int check_band(int Hu, int Wu, int y0, int y1) {         // HR rows [y0,y1) of a Hu x Wu image
+    return (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) ? DIINN_ERR_INVALID_ARG : DIINN_OK;
+}
+static inline int check_extent(double rows, double cols) {             // pixel indices stay below 2^31
+    return rows * cols >= 2.0e9 ? DIINN_ERR_TOO_LARGE : DIINN_OK;
+}
+static inline int check_sin(int sin_mode) {
+    return (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) ? DIINN_ERR_UNSUPPORTED : DIINN_OK;
+}
+static inline int check_grid(long long grid_y, long long grid_z) {     // HIP's limits of grid.y / grid.z
+    return (grid_y > 65535 || grid_z > 65535) ? DIINN_ERR_TOO_LARGE : DIINN_OK;
+}
+// pointers, LR map, HR band, extent, sine mode: the common order (a grid check, where there is one, follows)
+template <class... T>
+static inline int check_band_args(int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, const T*... ptrs) {
+    if (!all_set(ptrs...)) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_dims(B, H, W)) return st;
+    if (int st = check_band(Hu, Wu, y0, y1)) return st;
+    if (int st = check_extent(Hu, Wu)) return st;
+    return check_sin(sin_mode);
+}
+// workgroups of `extent` rows (columns) that cover [lo, hi)
+static inline int grid_blocks(int lo, int hi, int extent) { return (hi - lo + extent - 1) / extent; }
+constexpr int WG_W = TILE_W * WG_TILES_X, WG_H = TILE_H * WG_TILES_Y;   // the decode kernels' workgroup: 16 x 8 HR pixels
+
+// A run-time value as a template constant: launch(IC<V>{}) for the V of the list that equals v; false: none did.
+template <int... Vs, class F>
+static inline __attribute__((always_inline)) bool pick(int v, F&& launch) { return (... || (v == Vs && (launch(IC<Vs>{}), true))); }
+// The sine mode (of the listed ones; all three without a list) and, optionally, one more constant -- a flag of the kernel's
+// first template argument, a bool -- then the launch's status.  decltype(S)::value is the constant inside `launch`:
+//   launch_sin(sin_mode, [&](auto S) { hipLaunchKernelGGL(kernel<decltype(S)::value | FLAG>, grid, block, 0, stream, p); });
+// Only the listed combinations are instantiated.  The entry points have validated sin_mode; an unlisted value launches nothing.
+// (always_inline: a launch costs what the if / else chain it replaces did)
+template <int... SINS, class F>
+static inline __attribute__((always_inline)) int launch_sin_of(int sin_mode, F&& launch) {
+    if (!pick<SINS...>(sin_mode, launch)) return DIINN_ERR_UNSUPPORTED;
+    return hip_status(hipGetLastError());
+}
+template <class F>
+static inline __attribute__((always_inline)) int launch_sin(int sin_mode, F&& launch) {
+    return launch_sin_of<DIINN_SIN_HW, DIINN_SIN_HW_REDUCED, DIINN_SIN_ACCURATE>(sin_mode, launch);
+}
+template <int... Vs, class F>                                          // launch(IC<sine mode>, IC<v>), v one of Vs
+static inline __attribute__((always_inline)) int launch_sin(int sin_mode, int v, F&& launch) {
+    int st = DIINN_ERR_UNSUPPORTED;
+    pick<Vs...>(v, [&](auto V) { st = launch_sin(sin_mode, [&](auto S) { launch(S, V); }); });
+    return st;
+}
+
 // diinn_precompute.hip: the hoisted conv for mp_total M-tile pairs (16 = all 1024 channels), fp32 or bf16 operands
 struct RowWin { int row0, rows; };             // rows [row0, row0+rows) of a full-size tensor, stored on their own
 __attribute__((visibility("hidden")))
@@ -377,21 +430,17 @@ extern "C" __attribute__((visibility("hidden")))
 int diinn_conv1x1_x3_split(void* stream, float* xs_dev, long long xs_bs16, int Cin, const float* wx_dev, const float* bias_dev,
                            const float* res_dev, long long res_bs, float* o0_dev, long long o0_bs, float* o1_dev, long long o1_bs,
                            int B, int H, int W);
-// diinn_bf16.hip: the split-bf16 decode (DIINN_COMPUTE_BF16X3) of HR rows [p.y0, p.y1)
+// diinn_bf16x3.hip: the split-bf16 decode (DIINN_COMPUTE_BF16X3) of HR rows [p.y0, p.y1)
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
-// diinn_bf16x3.hip: the same arithmetic from the pixel planes of init_q (decode_bf16x3_kernel<SIN | X3_INITQ>)
+// diinn_bf16x3.hip: the other forms of decode_bf16x3_kernel<SIN | form>, the one-block kernel only:
+//   X3_INITQ  from the pixel planes of init_q (p.P = the planes of HR rows [p.y0, p.y1), p.Prow0 = p.y0)
+//   X3_SAVE   the training forward (`grid` = workgroups of four plane tiles; p.split = the split training image)
+//   X3_QONLY  decoder modes 1/2 (P holds the per-cell chain)
+//   X3_TAPS   mode 4's tap form (p.out = the tap buffer, p.head3 = the head image)
+constexpr int X3_INITQ = 4, X3_SAVE = 8, X3_QONLY = 16, X3_TAPS = 32;
 __attribute__((visibility("hidden")))
-int launch_decode_bf16x3_initq(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
-// diinn_bf16x3.hip: the training forward in that arithmetic (decode_bf16x3_kernel<SIN | X3_SAVE>; `blocks` workgroups of four plane tiles)
-__attribute__((visibility("hidden")))
-int launch_decode_bf16x3_save(void* stream, const DecodeParams& p, unsigned blocks, int sin_mode);
-// diinn_bf16x3.hip: decoder modes 1/2 in that arithmetic (decode_bf16x3_kernel<SIN | X3_QONLY>; P holds the per-cell chain) and
-// mode 4's tap form (decode_bf16x3_kernel<SIN | X3_TAPS>; p.out = the tap buffer, p.head3 = the head image)
-__attribute__((visibility("hidden")))
-int launch_decode_bf16x3_qonly(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
-__attribute__((visibility("hidden")))
-int launch_decode_bf16x3_taps(void* stream, const DecodeParams& p, int gx, int gy, int gz, int sin_mode);
+int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form);
 // diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1)
 __attribute__((visibility("hidden")))
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,

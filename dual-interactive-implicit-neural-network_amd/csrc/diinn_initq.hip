@@ -224,14 +224,9 @@ __global__ __launch_bounds__(256, 1) void initq_planes_kernel(const InitqParams 
 int launch_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                         float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool rad, bool rows512) {
     if (rad && rows512) return DIINN_ERR_UNSUPPORTED;
-    if (!feat_dev || !packed_dev || !initq_dev || !pix_dev) return DIINN_ERR_INVALID_ARG;
-    int st = check_dims(B, H, W);
-    if (st) return st;
-    if (Hu <= 0 || Wu <= 0 || y0 < 0 || y1 > Hu || y0 >= y1) return DIINN_ERR_INVALID_ARG;
-    if ((double)Hu * Wu >= 2.0e9) return DIINN_ERR_TOO_LARGE;
-    if (sin_mode < DIINN_SIN_ACCURATE || sin_mode > DIINN_SIN_HW_REDUCED) return DIINN_ERR_UNSUPPORTED;
-    const dim3 grid((Wu + IQ_TW - 1) / IQ_TW, (y1 - y0 + IQ_TH - 1) / IQ_TH, B);
-    if (grid.y > 65535 || B > 65535) return DIINN_ERR_TOO_LARGE;
+    if (int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, pix_dev)) return st;
+    const dim3 grid(grid_blocks(0, Wu, IQ_TW), grid_blocks(y0, y1, IQ_TH), B);
+    if (int st = check_grid(grid.y, B)) return st;
     InitqParams p;
     p.feat = feat_dev; p.Wt = packed_dev; p.iq = initq_dev; p.pix = pix_dev;
     p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu; p.y0 = y0; p.y1 = y1;
@@ -241,31 +236,9 @@ int launch_initq_planes(void* stream, const float* feat_dev, const float* packed
     p.aw = make_axis(W, Wu, small);
     // streaming stores once the planes no longer fit beside anything in the 256 MiB last-level cache (launch_P's rule)
     p.stream_stores = (double)B * (y1 - y0) * Wu * PIX_CH * 4.0 >= 128.0 * 1024 * 1024;
-    if (rad) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW_REDUCED | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE | INITQ_RAD>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (rows512) {
-        if (sin_mode == DIINN_SIN_HW)
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (sin_mode == DIINN_SIN_HW_REDUCED)
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW_REDUCED | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE | INITQ_ROWS512>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        return hip_status(hipGetLastError());
-    }
-    if (sin_mode == DIINN_SIN_HW)
-        hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (sin_mode == DIINN_SIN_HW_REDUCED)
-        hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_HW_REDUCED>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(initq_planes_kernel<DIINN_SIN_ACCURATE>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return hip_status(hipGetLastError());
+    return launch_sin<INITQ_RAD, INITQ_ROWS512, 0>(sin_mode, rad ? INITQ_RAD : rows512 ? INITQ_ROWS512 : 0, [&](auto S, auto F) {
+        hipLaunchKernelGGL(initq_planes_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int diinn_initq_planes(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
