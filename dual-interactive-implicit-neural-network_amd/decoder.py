@@ -27,7 +27,8 @@ import torch.nn as nn
 from . import _native
 # the formula sheets live in sheets.py; tests, tools and the documents cite them under this module's name
 from .sheets import (HIDDEN, INV_2PI_F32, P_CHANNELS, axis_tables, initq_forward_reference,  # noqa: F401
-                     initq_modes_forward_reference, initq_planes_reference, modes_x3_forward_reference)
+                     initq_modes_forward_reference, initq_planes_reference, liif_x3_forward_reference,
+                     modes_x3_forward_reference)
 
 IN_CHANNELS = 64
 
@@ -467,12 +468,28 @@ def liif_axis_tables(n_in: int, n_out: int, v: int) -> Tuple[np.ndarray, np.ndar
     return idx, rel, cell.value
 
 
+def pack_liif_split(packed_host: torch.Tensor) -> torch.Tensor:
+    """The split training image (``diinn_pack_split_train_host``) of a LIIF packed image on the host: pieces 1 / 3 of every
+    k-step of its forward half are hi / lo of ``imnet.layers.{2,4,6}.weight`` -- what ``liif_x3_kernel`` streams."""
+    from .split_training import pack_split_host
+    return torch.from_numpy(pack_split_host(packed_host.detach().cpu().numpy()))
+
+
 def _comparison_decode(name: str, workspace_bytes, feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
-                       out: Optional[torch.Tensor], workspace: Optional[torch.Tensor]) -> torch.Tensor:
-    """The LIIF / MetaSR decode of every HR pixel: the library's ``name`` (diinn_liif_decode's signature) with
-    ``workspace_bytes(B, H, W)`` bytes of workspace; a ``workspace`` that is too small is replaced."""
+                       out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
+                       split: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The LIIF / MetaSR decode of every HR pixel: the library's ``name`` (diinn_liif_decode's signature; with ``split``, a
+    second weight image behind ``packed``) with ``workspace_bytes(B, H, W)`` bytes of workspace; a ``workspace`` that is too
+    small is replaced."""
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
+    images = (packed,)
+    if split is not None:
+        _require_cuda(split, "split weights")
+        if split.dtype != torch.float32 or not split.is_contiguous() or split.numel() != _native.load().diinn_split_train_floats() \
+                or split.device != packed.device:
+            raise ValueError("split must be the contiguous fp32 split training image of packed (pack_liif_split) on its device")
+        images = (packed, split)
     feat, (b, h, w) = _checked_feat(feat)
     hu, wu = size
     hu, wu = int(hu), int(wu)
@@ -480,14 +497,23 @@ def _comparison_decode(name: str, workspace_bytes, feat: torch.Tensor, packed: t
     need = workspace_bytes(b, h, w)
     if workspace is None or workspace.numel() * 4 < need or workspace.device != feat.device:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
-    _launch(name, feat.device, feat, packed, workspace, out, b, h, w, hu, wu)
+    _launch(name, feat.device, feat, *images, workspace, out, b, h, w, hu, wu)
     return out
 
 
 def liif_decode_features(feat: torch.Tensor, packed: torch.Tensor, size: Sequence[int],
-                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """LIIF query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (liif.py:59-127,148-155)."""
-    return _comparison_decode("diinn_liif_decode", _native.load().diinn_workspace_bytes, feat, packed, size, out, workspace)
+                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                         split: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LIIF query of every HR pixel: encoder features [B,64,H,W] -> RGB [B,3,Hu,Wu] (liif.py:59-127,148-155).
+
+    ``split`` (opt-in, not in the reference): the split training image of ``packed`` (``pack_liif_split``) on its device.  The
+    three hidden 256 x 256 layers of every ensemble member then run in split-bf16 arithmetic (``diinn_liif_decode_x3``,
+    ``liif_x3_kernel``; sheet: ``liif_x3_forward_reference``) -- within the fp32 contract, 1e-4 x max(1, max|ref|), but not
+    ``liif_kernel``'s bits."""
+    if split is None:
+        return _comparison_decode("diinn_liif_decode", _native.load().diinn_workspace_bytes, feat, packed, size, out, workspace)
+    return _comparison_decode("diinn_liif_decode_x3", _native.load().diinn_workspace_bytes, feat, packed, size, out, workspace,
+                              split=split)
 
 
 # ---------------------------------------------------------------------------

@@ -280,7 +280,8 @@ class _GraphReplay:
                 getattr(dec, "sin_mode", None), getattr(dec, "compute", None), getattr(dec, "mode", None),
                 getattr(enc, "hip_trunk_max_pixels", None), getattr(enc, "hip_winograd", None),
                 getattr(enc, "hip_split_bf16", None), getattr(enc, "hip_winograd4", None),
-                getattr(dec, "hip_modes_split_bf16", None), getattr(self, "hip_hoisted", None))
+                getattr(dec, "hip_modes_split_bf16", None), getattr(self, "hip_hoisted", None),
+                getattr(self, "hip_split_bf16", None))
 
     def _forward_graphed(self, x, size, bsize):
         key = self._graph_key(x, size)
@@ -301,7 +302,7 @@ class _GraphReplay:
                 # private pool: workspaces, activations, the result) or kept alive by the entry below (packed
                 # weight images, which live in module caches that a later call may replace)
                 static_y = self._forward_eager(static_x, size, bsize)
-            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_packed_head", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2", "_hoisted_images")]
+            keep = [getattr(m, a, None) for m in self.modules() for a in ("_packed", "_packed_split", "_packed_head", "_hip_pack", "_hip_x3", "_hip_wu4", "_hip_wu2", "_hoisted_images")]
             entry = (graph, static_x, static_y, keep)
             self._graph_cache[key] = entry
         graph, static_x, static_y = entry[:3]
@@ -410,20 +411,31 @@ class LIIF(nn.Module, _GraphReplay):
     ``liif_training.LIIFFunction`` (the inference kernels saving the activations, the backward pass on the HIP kernels; ROCm GPU
     only), and with ``bsize`` given the decode runs under no_grad like the reference's ``batched_predict`` (liif.py:129-140): the
     output carries no graph.  With it unset a call under autograd raises NotImplementedError, as it always did.  ``bsize`` itself
-    is the reference's query-chunk size, a memory knob: accepted and ignored.  Graph replay is inference-only."""
+    is the reference's query-chunk size, a memory knob: accepted and ignored.  Graph replay is inference-only.
+
+    ``hip_split_bf16`` (a plain attribute, also a constructor keyword; default False; not in the reference; named after the
+    encoder's switch): the three hidden 256 x 256 layers of the decoder in split-bf16 arithmetic (``liif_x3_kernel`` through
+    ``liif_decode_features(..., split=...)``) -- within the reference tolerance, 1e-4 x max(1, max|ref|),
+    but not ``liif_kernel``'s bits, which the fixtures pin: hence a switch.  Inference only: the training forward
+    (``hip_autograd`` under autograd with ``bsize=None``) refuses while it is set; the no_grad decode of a call with ``bsize``
+    honours it.  ``set_split_bf16`` sets it together with the encoder's."""
 
     hip_autograd = False
+    hip_split_bf16 = False
 
-    def __init__(self, local_ensemble=True, feat_unfold=True, cell_decode=True, graphs: bool = False, hip_autograd: bool = False):
+    def __init__(self, local_ensemble=True, feat_unfold=True, cell_decode=True, graphs: bool = False, hip_autograd: bool = False,
+                 hip_split_bf16: bool = False):
         super().__init__()
         self._init_graphs(graphs)
         if not (local_ensemble and feat_unfold and cell_decode):
             raise NotImplementedError("the HIP path implements LIIF with local_ensemble, feat_unfold and cell_decode on")
         self.local_ensemble, self.feat_unfold, self.cell_decode = local_ensemble, feat_unfold, cell_decode
         self.hip_autograd = bool(hip_autograd)
+        self.hip_split_bf16 = bool(hip_split_bf16)
         self.encoder = make_rdn()
         self.imnet = MLP(self.encoder.out_dim * 9 + 4, 3, [256, 256, 256, 256])
         self._packed = None
+        self._packed_split = None                                # the split training image of _packed: built on first use, same key
         self._packed_key = None
 
     def gen_feat(self, inp):
@@ -434,12 +446,32 @@ class LIIF(nn.Module, _GraphReplay):
         key = (str(device),) + tuple((p.data_ptr(), p._version) for p in self.imnet.parameters())
         if self._packed is None or self._packed_key != key:
             self._packed = pack_liif_state_dict(self.imnet.state_dict(), prefix="").to(device)
+            self._packed_split = None
             self._packed_key = key
         return self._packed
+
+    def _split_weights(self, device):
+        """The split training image of ``_packed_weights(device)``, cached beside it under its key (the module holds on to it: a
+        graph entry keeps it alive)."""
+        from .decoder import pack_liif_split
+        packed = self._packed_weights(device)
+        if self._packed_split is None:
+            self._packed_split = pack_liif_split(packed).to(device)
+        return packed, self._packed_split
+
+    def set_split_bf16(self, enabled: bool = True) -> "LIIF":
+        """Switch both optional split-bf16 modes (not in the reference): the decoder's hidden layers (``hip_split_bf16``) and the
+        encoder's 3x3 layers (``encoder.hip_split_bf16``), as ``DIINN.set_split_bf16`` does."""
+        self.hip_split_bf16 = bool(enabled)
+        self.encoder.hip_split_bf16 = bool(enabled)
+        return self
 
     def _forward_eager(self, inp, size, bsize=None):
         from .decoder import liif_decode_features
         feat = self.gen_feat(inp)
+        if self.hip_split_bf16:
+            packed, split = self._split_weights(feat.device)
+            return liif_decode_features(feat, packed, size, split=split)
         return liif_decode_features(feat, self._packed_weights(feat.device), size)
 
     def _forward_train(self, inp, size):
@@ -452,6 +484,9 @@ class LIIF(nn.Module, _GraphReplay):
         if torch.is_grad_enabled() and self.hip_autograd:
             if inp.requires_grad or any(p.requires_grad for p in self.parameters()):
                 if bsize is None:
+                    if self.hip_split_bf16:
+                        raise NotImplementedError("diinn_amd: LIIF trains in fp32 only: unset LIIF.hip_split_bf16 (the split-bf16 "
+                                                  "decoder is inference-only), or call under torch.no_grad()")
                     return self._forward_train(inp, size)
                 with torch.no_grad():                            # batched_predict is no_grad in the reference: no graph
                     return self._forward_eager(inp, size, bsize)

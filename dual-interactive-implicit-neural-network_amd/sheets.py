@@ -339,3 +339,47 @@ def modes_x3_forward_reference(sd, feat, size, mode: int, prefix: str = "") -> t
             k = kc[i][:, :, cell]
         q = k * sin_rev(s)
     return head3x3(get, q, g) if mode == 4 else head1x1(get, q, g)
+
+
+def liif_x3_forward_reference(sd, feat, size, prefix: str = "imnet.") -> torch.Tensor:
+    """The EMULATION sheet of the split-bf16 arithmetic of the LIIF comparison decoder (``liif_decode_features(..., split=...)``,
+    ``liif_x3_kernel``), in fp32 torch algebra on any device: the reference's form (liif.py:59-127) with the three hidden
+    256 x 256 layers ``imnet.layers.{2,4,6}`` as ``split_matmul(W, x^T) + b`` -- every operand carried as hi = bf16(v),
+    lo = bf16(v - hi), the product ``(w_lo.x_hi + w_hi.x_lo) + w_hi.x_hi`` in fp32 (torch matmuls, not the MFMA's summation order).
+
+    What stays fp32: the index and coordinate tables (``decoder.liif_axis_tables``), layer 0 on [unfolded features of the shifted
+    nearest cell ; rel_h ; rel_w ; cell_h ; cell_w] as the reference forms it (one ``linear``; the kernel hoists its 576 feature
+    columns into a conv per LR cell), the biases, the head on the unsplit activation, the areas and the blend."""
+    from .decoder import liif_axis_tables
+    f32 = torch.float32
+    feat = feat if isinstance(feat, torch.Tensor) else torch.from_numpy(np.asarray(feat))
+    dev = feat.device
+    get = tensor_getter(sd, prefix, dev, f32)
+    x = feat.to(f32)
+    b, c, h, w = x.shape
+    hu, wu = int(size[0]), int(size[1])
+    unf = torch.nn.functional.unfold(x, 3, padding=1).view(b, c * 9, h, w)
+    w0, b0 = get("layers.0.weight", (HIDDEN, c * 9 + 4)), get("layers.0.bias", (HIDDEN,))
+    preds, areas = [], []
+    for vh in (-1, 1):                                            # member order: vx outer, vy inner (liif.py:88-89)
+        ih, rh, cell_h = liif_axis_tables(h, hu, vh)
+        for vw in (-1, 1):
+            iw, rw, cell_w = liif_axis_tables(w, wu, vw)
+            q = unf[:, :, torch.from_numpy(ih.astype(np.int64)).to(dev)][:, :, :, torch.from_numpy(iw.astype(np.int64)).to(dev)]
+            rel = torch.empty((b, hu, wu, 4), dtype=f32, device=dev)
+            rel[..., 0] = torch.from_numpy(rh).to(dev)[None, :, None]
+            rel[..., 1] = torch.from_numpy(rw).to(dev)[None, None, :]
+            rel[..., 2] = cell_h
+            rel[..., 3] = cell_w
+            z = torch.cat([q.permute(0, 2, 3, 1), rel], dim=-1).reshape(-1, c * 9 + 4)
+            z = torch.relu(torch.nn.functional.linear(z, w0, b0)).t()                    # [256, b * n]
+            for i in (2, 4, 6):
+                z = torch.relu(split_matmul(get(f"layers.{i}.weight", (HIDDEN, HIDDEN)), z) + get(f"layers.{i}.bias", (HIDDEN, 1)))
+            z = torch.nn.functional.linear(z.t(), get("layers.8.weight", (3, HIDDEN)), get("layers.8.bias", (3,)))
+            preds.append(z.view(b, hu, wu, 3))
+            areas.append((rel[..., 0] * rel[..., 1]).abs() + 1e-9)
+    tot = torch.stack(areas).sum(dim=0)
+    out = 0
+    for pred, area in zip(preds, (areas[3], areas[2], areas[1], areas[0])):              # diagonal swap, liif.py:121-123
+        out = out + pred * (area / tot).unsqueeze(-1)
+    return out.permute(0, 3, 1, 2).contiguous()

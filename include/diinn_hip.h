@@ -669,6 +669,17 @@ int diinn_conv_wgrad(void* stream, const float* g_dev, long long g_batch_stride,
 int diinn_liif_decode(void* stream, const float* feat_dev, const float* packed_dev, float* workspace_dev,
                       float* out_dev, int B, int H, int W, int Hu, int Wu);
 int diinn_liif_make_axis_tables(int n_in, int n_out, int v, int32_t* idx, float* rel, float* rel_cell);
+/* LIIF in split-bf16 arithmetic (added under ABI 11, backward compatible; opt-in, not in the reference).  diinn_liif_decode with the
+ * three hidden 256 x 256 layers (imnet.layers.{2,4,6}) of every ensemble member on the bf16 matrix cores: every operand carried as
+ * hi = bf16(v), lo = bf16(v - hi), a product formed as w_lo.h_hi + w_hi.h_lo + w_hi.h_hi with fp32 accumulation (liif_x3_kernel).  The
+ * hoisted conv, the first layer, the biases, the head, the areas and the blend are diinn_liif_decode's fp32 expressions.  The result is
+ * within the fp32 contract, 1e-4 x max(1, max|reference|), but not diinn_liif_decode's bits.
+ * split_dev: the split training image of packed_dev, diinn_split_train_floats() floats (diinn_pack_split_train_host on the host image,
+ *   or diinn_pack_split_train on the device; 16-byte aligned); its forward half is read.  packed_dev must carry the validity word:
+ *   without it every output is NaN.  Otherwise diinn_liif_decode's arguments, checks (split_dev counts among the pointers),
+ *   status codes, workspace size (diinn_workspace_bytes) and launch count: 2 kernels; no allocation, no sync. */
+int diinn_liif_decode_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* split_dev,
+                         float* workspace_dev, float* out_dev, int B, int H, int W, int Hu, int Wu);
 /* LIIF under autograd (added under ABI 11, backward compatible).  Replaces what autograd records and runs backward for
  * LIIF.query_rgb (liif.py:59-127) when forward(inp, size, None) runs under grad (sr_module.py:127-129).  Per HR pixel p and
  * ensemble member v = 2 vh + vw (vx outer, vy inner: liif.py:88-89) -- the VIRTUAL pixel vp = v * N + p, N = B*Hu*Wu; 4 N is what

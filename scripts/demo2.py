@@ -67,7 +67,14 @@ def demo2(args):
     if args.compute != "f32" and args.model_name != "bicubic":
         # (not in the reference's command line) arithmetic of the implicit decoder's per-pixel layers: "bf16x3" = split
         # bf16, held to the fp32 tolerance at ~2.9x the decode speed; "bf16" / "bf16_full" = reduced precision
-        model.net.decoder.compute = args.compute
+        if hasattr(model.net, "decoder"):
+            model.net.decoder.compute = args.compute
+        elif args.compute == "bf16x3" and hasattr(model.net, "hip_split_bf16"):
+            model.net.hip_split_bf16 = True          # LIIF: the decoder's three hidden layers in split bf16
+        else:
+            raise ValueError(f"--compute {args.compute}: a {type(model.net).__name__} checkpoint decodes in 'f32'"
+                             + (" or 'bf16x3'" if hasattr(model.net, "hip_split_bf16") else "")
+                             + "; 'bf16' and 'bf16_full' are the DIINN decoder's arithmetics")
     if args.encoder_split_bf16 and args.model_name != "bicubic" and hasattr(model.net, "encoder"):
         model.net.encoder.hip_split_bf16 = True      # the RDN trunk's 3x3 layers in split bf16 (maps of >= ~180x180 pixels)
     if rank == 0:
