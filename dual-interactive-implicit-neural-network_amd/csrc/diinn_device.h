@@ -20,7 +20,8 @@
 //   diinn_baselines.hip        LIIF and MetaSR comparison decoders
 //   diinn_metasr_training.hip  metasr_bwd_cells_kernel (MetaSR under autograd: the per-cell backward pass)
 //   diinn_liif_training.hip    liif_bwd_layer_kernel, liif_cell_sum_kernel (LIIF under autograd; the forward is liif_kernel<SAVE> in diinn_baselines.hip)
-//   diinn_liif_x3.hip          liif_x3_kernel (LIIF's hidden layers in split-bf16 arithmetic, opt-in; inference)
+//   diinn_liif_x3.hip          liif_x3_kernel (LIIF's hidden layers in split-bf16 arithmetic, opt-in; inference), liif_x3_save_kernel (its training forward)
+//   diinn_liif_split_training.hip  liif_bwd_layer_x3_kernel (LIIF under autograd in split-bf16 arithmetic: the backward chain)
 //   diinn_initq_training.hip   initq_bwd_kernel (init_q under autograd: the transposed per-pixel GEMMs), cell_sum_rows_kernel, fold3x3_kernel
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))

@@ -17,6 +17,7 @@
 //     barrier); in the last layer the three head FMAs on the unsplit activation instead, in liif_kernel's (m, g, e) order;
 //   * the blend, the stores: liif_kernel's.  The Q0 rows, the head rows and bL sit in an LDS table, filled once per workgroup.
 // The image's validity word is folded into bL like decode_bf16x3_kernel's: an image without it decodes to NaN.
+// The body is a template on SAVE (the training forward, liif_x3_save_kernel: see the two kernels below it).
 // ---------------------------------------------------------------------------------
 struct LiifX3Params {
     const float* P;        // [B,H,W,1024], channels 0..255 = first-layer pre-activation of the cell (fp32 hoisted conv)
@@ -25,6 +26,10 @@ struct LiifX3Params {
     float* out;            // [B,3,Hu,Wu]
     int B, H, W, Hu, Wu;
     LiifAxis ah, aw;
+};
+struct LiifX3SaveParams : LiifX3Params {    // the training forward's (a struct of its own: the inference kernel keeps its arguments)
+    float* acts;           // h_1..h_4, tiled planes over the virtual pixels [4][vtiles][256][32]
+    long long npix;        // N = B*Hu*Wu
 };
 
 constexpr int LIIF_X3_PREFETCH = 4;             // ring depth in k-steps (2 pieces, 3 MFMAs each)
@@ -47,7 +52,8 @@ __device__ __forceinline__ void liif_split_bf16(float v, __bf16& hi, __bf16& lo)
     lo = (__bf16)(v - (float)hi);               // exact difference: v and hi share sign and exponent range
 }
 
-__global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
+template <bool SAVE, class Params>
+__device__ __forceinline__ void liif_x3_body(const Params& p) {
     __shared__ __attribute__((aligned(16))) bf16x8 park[4][2][16][64];     // [wave][hi, lo][fragment][lane] = 128 KiB
     __shared__ __attribute__((aligned(16))) float tab[LIIF_X3_TAB];
     const int lane = threadIdx.x & 63;
@@ -63,12 +69,24 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
             *(f32x4*)(tab + 5 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 1 * HID + 4 * lane);
         } else {
             *(f32x4*)(tab + 6 * HID + 4 * lane) = *(const f32x4*)(Wt + OFF_L + 2 * HID + 4 * lane);
-            if (lane == 0) *(f32x4*)(tab + 7 * HID) = or_bits(*(const f32x4*)(Wt + OFF_BL), derived_nan_mask(Wt));
+            if (lane == 0) *(f32x4*)(tab + 7 * HID) = or_bits(*(const f32x4*)(Wt + OFF_BL), SAVE ? 0u : derived_nan_mask(Wt));   // (a gathered training image carries no validity word)
         }
     }
-    const int x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
-    const int y = blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
-    const int b = blockIdx.z;
+    int x, y, b;
+    [[maybe_unused]] const long long ptile = (long long)blockIdx.x * 4 + wave;   // SAVE: this wave's 32 consecutive flattened pixels
+    if constexpr (SAVE) {                                       // liif_kernel<SAVE>'s ownership
+        const long long pix = ptile * PLANE_TILE + j;
+        const long long pc = pix < p.npix ? pix : p.npix - 1;    // lanes past the end compute on the last pixel
+        const int hw = p.Hu * p.Wu;
+        b = (int)(pc / hw);
+        const int rem = (int)(pc - (long long)b * hw);
+        y = rem / p.Wu;
+        x = pix < p.npix ? rem - y * p.Wu : p.Wu;                // ... and are marked invalid below
+    } else {
+        x = blockIdx.x * (TILE_W * WG_TILES_X) + (wave & 1) * TILE_W + (j & (TILE_W - 1));
+        y = blockIdx.y * (TILE_H * WG_TILES_Y) + (wave >> 1) * TILE_H + (j / TILE_W);
+        b = blockIdx.z;
+    }
     const bool valid = (x < p.Wu) && (y < p.Hu);
     __syncthreads();
     if (__builtin_amdgcn_readfirstlane((int)(__ballot(valid) == 0ull))) return;
@@ -108,6 +126,25 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
         const int vh = v >> 1, vw = v & 1;
         const float relh = rh[vh], relw = rw[vw];
         const float* __restrict__ Pc = p.P + (((size_t)b * p.H + iy[vh]) * p.W + ix[vw]) * PCH + 4 * h;
+        // SAVE: the two plane tiles that hold this wave's pixels of member v and the lane's place in them, as liif_kernel<SAVE>
+        // derives them per member (lanes past the end carry an offset outside the descriptor's range: the store is dropped)
+        [[maybe_unused]] const float* act0 = nullptr;
+        [[maybe_unused]] size_t act_group = 0;
+        [[maybe_unused]] int act_bytes = 0;
+        [[maybe_unused]] unsigned act_voff = 0xFFFFFFF0u;
+        if constexpr (SAVE) {
+            const long long vtiles = (4 * p.npix + PLANE_TILE - 1) / PLANE_TILE;
+            const long long vp0 = (long long)v * p.npix + ptile * PLANE_TILE;
+            const long long t0 = vp0 >> 5;
+            const unsigned qpos = (unsigned)(vp0 & 31) + (unsigned)j;
+            act_group = (size_t)vtiles * HID * PLANE_TILE;
+            act0 = p.acts + (size_t)t0 * HID * PLANE_TILE;
+            act_bytes = (int)((vtiles - t0 < 2 ? vtiles - t0 : 2) * HID * (long long)PLANE_ROW_BYTES);
+            if (valid) act_voff = (qpos >> 5) * (unsigned)(HID * PLANE_ROW_BYTES) + 4u * (qpos & 31) + 4u * h * PLANE_ROW_BYTES;
+        }
+        [[maybe_unused]] auto act_rsrc = [&](int layer) {
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(act0 + (size_t)layer * act_group), 0, act_bytes, 0x00020000);
+        };
         f32x4 rqh[PF], rql[PF];
 #pragma unroll
         for (int d = 0; d < PF; ++d) ld_kstep_q(rqh[d], rql[d], d * KS_BYTES);
@@ -132,8 +169,10 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
                         a = __builtin_fmaf(ww[e], relw, a);
                         a = __builtin_fmaf(wch[e], p.ah.rel_cell, a);
                         a = __builtin_fmaf(wcw[e], p.aw.rel_cell, a);
+                        a = relu0(a);
+                        if constexpr (SAVE) st_act(act_rsrc(0), act_voff, (unsigned)(c0 + e) * PLANE_ROW_BYTES, a);   // h_1, unsplit
                         __bf16 sh, sl;
-                        liif_split_bf16(relu0(a), sh, sl);
+                        liif_split_bf16(a, sh, sl);
                         qh[2 * m + (g >> 1)][4 * (g & 1) + e] = sh;
                         ql[2 * m + (g >> 1)][4 * (g & 1) + e] = sl;
                     }
@@ -158,6 +197,7 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
             f32x16 ps;
             bf16x8 fh, fl;
             f32x4 l0[4], l1[4], l2[4];
+            [[maybe_unused]] const __amdgpu_buffer_rsrc_t arl = act_rsrc(SAVE ? layer + 1 : 0);   // SAVE: plane h_{layer + 2}
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 f32x16 as;
@@ -189,6 +229,8 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
                     if (m > 0) {                                  // one epilogue element of tile m-1 per k-step
                         float a = relu0(ps[ks]);
                         asm volatile("" : "+v"(a));               // the element stays behind its k-step (see decode_bf16x3_kernel)
+                        // register r of tile m-1 = channel 32(m-1) + (r&3) + 8(r>>2) + 4h: the unsplit value, as liif_kernel<SAVE> stores it
+                        if constexpr (SAVE) st_act(arl, act_voff, (unsigned)(32 * (m - 1) + (ks & 3) + 8 * (ks >> 2)) * PLANE_ROW_BYTES, a);
                         if (LAST) {
                             m0 = __builtin_fmaf(l0[ks >> 2][ks & 3], a, m0);
                             m1 = __builtin_fmaf(l1[ks >> 2][ks & 3], a, m1);
@@ -219,6 +261,7 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float a = relu0(ps[r]);
+                if constexpr (SAVE) st_act(arl, act_voff, (unsigned)(32 * 7 + (r & 3) + 8 * (r >> 2)) * PLANE_ROW_BYTES, a);
                 if (LAST) {
                     m0 = __builtin_fmaf(l0[r >> 2][r & 3], a, m0);
                     m1 = __builtin_fmaf(l1[r >> 2][r & 3], a, m1);
@@ -268,6 +311,22 @@ __global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
     }
 }
 
+// The two instantiations.  SAVE = true is the training forward of LIIF.hip_autograd_split_bf16 (diinn_liif_train_fwd_x3): the same
+// network on liif_kernel<SAVE>'s pixel ownership -- a wave owns 32 consecutive pixels of the flattened (b, y, x) index, the grid is
+// ceil(N / 128) workgroups -- that also writes the unsplit fp32 relu0(a) of every hidden layer and member, h_1..h_4, to p.acts
+// [4 layers][ceil(4 N / 32)][256][32] over the virtual pixels vp = v * N + pix, in liif_kernel<SAVE>'s layout and its
+// two-neighbouring-tiles addressing: the planes diinn_liif_backward_data[_x3] read.  A pixel's arithmetic does not depend on the
+// lane that owns it, so the output is liif_x3_kernel's bit for bit.  Every SAVE branch of the body is `if constexpr` around code
+// the inference instantiation keeps whole.  (Two kernel names over one body, not one templated name: the inference kernel keeps
+// its symbol.)
+__global__ __launch_bounds__(256, 1) void liif_x3_kernel(const LiifX3Params p) {
+    liif_x3_body<false, LiifX3Params>(p);
+}
+
+__global__ __launch_bounds__(256, 1) void liif_x3_save_kernel(const LiifX3SaveParams p) {
+    liif_x3_body<true, LiifX3SaveParams>(p);
+}
+
 extern "C" {
 
 // diinn_liif_decode's checks in its order, with split_dev among the pointers
@@ -287,6 +346,29 @@ int diinn_liif_decode_x3(void* stream, const float* feat_dev, const float* packe
     p.ah = make_liif_axis(H, Hu);
     p.aw = make_liif_axis(W, Wu);
     hipLaunchKernelGGL(liif_x3_kernel, dim3(gx, gy, gz), dim3(blk), 0, (hipStream_t)stream, p);
+    return hip_status(hipGetLastError());
+}
+
+// diinn_liif_decode_x3's checks in its order, with acts_dev among the pointers and diinn_liif_train_fwd's limits (the virtual
+// pixels, the 1-D grid) in the place of the inference grid's
+int diinn_liif_train_fwd_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* split_dev,
+                            float* workspace_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu) {
+    if (!all_set(feat_dev, packed_dev, split_dev, out_dev, workspace_dev, acts_dev)) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_dims(B, H, W)) return st;
+    if (Hu <= 0 || Wu <= 0) return DIINN_ERR_INVALID_ARG;
+    if (int st = check_extent(Hu, Wu)) return st;
+    const long long npix = (long long)B * Hu * Wu;
+    if (int st = check_npix(4 * npix)) return st;                // the limit applies to the virtual pixels
+    const long long blocks = ((npix + PLANE_TILE - 1) / PLANE_TILE + 3) / 4;
+    if (blocks > 2147483000LL) return DIINN_ERR_TOO_LARGE;       // every argument is judged before the first launch
+    if (int st = launch_P(stream, feat_dev, packed_dev, workspace_dev, B, H, W, 0, H, 4)) return st;   // diinn_liif_decode's P
+    LiifX3SaveParams p;
+    p.P = workspace_dev; p.Wt = packed_dev; p.split = split_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.Hu = Hu; p.Wu = Wu;
+    p.ah = make_liif_axis(H, Hu);
+    p.aw = make_liif_axis(W, Wu);
+    p.acts = acts_dev; p.npix = npix;
+    hipLaunchKernelGGL(liif_x3_save_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     return hip_status(hipGetLastError());
 }
 

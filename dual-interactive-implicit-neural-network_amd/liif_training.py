@@ -264,11 +264,13 @@ def cell_sum(g1: torch.Tensor, b: int, h: int, w: int, hu: int, wu: int,
 
 
 def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, image: torch.Tensor, w0: torch.Tensor, wkey, wpins,
-                   size: Sequence[int], need_feat_grad: bool = True, need_w0_grad: bool = True
+                   size: Sequence[int], need_feat_grad: bool = True, need_w0_grad: bool = True, split: Optional[torch.Tensor] = None
                    ) -> Tuple[Optional[torch.Tensor], List[Optional[torch.Tensor]]]:
     """The same gradients as ``liif_backward_reference``, on the HIP kernels throughout (module docstring).  ``acts``: the tiled
     buffer of ``train_forward``; ``w0``: imnet.layers.0.weight; ``wkey`` / ``wpins`` identify its values for the cache of the
-    transposed conv weight.  ``need_w0_grad`` false skips the conv's weight GEMM (d layers.0.weight is then None)."""
+    transposed conv weight.  ``need_w0_grad`` false skips the conv's weight GEMM (d layers.0.weight is then None).
+    ``split`` (the split training image of ``image``, ``liif_split_training.split_on_device``): the chain runs on
+    ``diinn_liif_backward_data_x3`` -- the three transposed products in split-bf16 arithmetic -- and nothing else differs."""
     b, _, h, w = feat.shape
     hu, wu = int(size[0]), int(size[1])
     n = b * hu * wu
@@ -290,7 +292,10 @@ def backward_fused(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, i
     part1 = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
     partl = torch.empty((rsplit, HIDDEN, 4), dtype=torch.float32, device=dev)
     with _native.launcher(dev) as run:
-        run("diinn_liif_backward_data", gp, acts, image, g, b, h, w, hu, wu)
+        if split is None:
+            run("diinn_liif_backward_data", gp, acts, image, g, b, h, w, hu, wu)
+        else:
+            run("diinn_liif_backward_data_x3", gp, acts, image, split, g, b, h, w, hu, wu)
         for li in (3, 2, 1):                                      # [dW_l | db_l] = g_a,l . h_{l-1}^T, l = li + 1
             run("diinn_plane_gemm_nt", g[li], HIDDEN, 0, acts[li - 1], HIDDEN, 0, part[li - 1], HIDDEN, HIDDEN, vn, ksplit, 1)
         run("diinn_plane_rowdot", acts[3], HIDDEN, wg_t, partl, HIDDEN, vn, rsplit)

@@ -416,15 +416,24 @@ class LIIF(nn.Module, _GraphReplay):
     ``hip_split_bf16`` (a plain attribute, also a constructor keyword; default False; not in the reference; named after the
     encoder's switch): the three hidden 256 x 256 layers of the decoder in split-bf16 arithmetic (``liif_x3_kernel`` through
     ``liif_decode_features(..., split=...)``) -- within the reference tolerance, 1e-4 x max(1, max|ref|),
-    but not ``liif_kernel``'s bits, which the fixtures pin: hence a switch.  Inference only: the training forward
-    (``hip_autograd`` under autograd with ``bsize=None``) refuses while it is set; the no_grad decode of a call with ``bsize``
-    honours it.  ``set_split_bf16`` sets it together with the encoder's."""
+    but not ``liif_kernel``'s bits, which the fixtures pin: hence a switch.  On its own it is inference only: the training forward
+    (``hip_autograd`` under autograd with ``bsize=None``) refuses while it is set, unless ``hip_autograd_split_bf16`` is set too; the
+    no_grad decode of a call with ``bsize`` honours it.  ``set_split_bf16`` sets it together with the encoder's.
+
+    ``hip_autograd_split_bf16`` (a plain attribute, also a constructor keyword; default False; not in the state dict; not in the
+    reference; named after ``ImplicitDecoder``'s switch): acts only together with ``hip_autograd`` AND ``hip_split_bf16``.  With all
+    three set, a call under autograd with ``bsize=None`` trains with the three hidden layers in split-bf16 arithmetic both ways:
+    ``liif_split_training.LIIFSplitFunction`` -- the forward is ``liif_x3_kernel``'s arithmetic saving the activations (the output
+    under grad is the no_grad split output bit for bit), the backward chain runs on ``liif_bwd_layer_x3_kernel``, everything behind
+    it stays fp32.  With ``hip_split_bf16`` unset it changes nothing: fp32 training.  ``set_split_bf16`` does
+    not touch it."""
 
     hip_autograd = False
     hip_split_bf16 = False
+    hip_autograd_split_bf16 = False
 
     def __init__(self, local_ensemble=True, feat_unfold=True, cell_decode=True, graphs: bool = False, hip_autograd: bool = False,
-                 hip_split_bf16: bool = False):
+                 hip_split_bf16: bool = False, hip_autograd_split_bf16: bool = False):
         super().__init__()
         self._init_graphs(graphs)
         if not (local_ensemble and feat_unfold and cell_decode):
@@ -432,6 +441,7 @@ class LIIF(nn.Module, _GraphReplay):
         self.local_ensemble, self.feat_unfold, self.cell_decode = local_ensemble, feat_unfold, cell_decode
         self.hip_autograd = bool(hip_autograd)
         self.hip_split_bf16 = bool(hip_split_bf16)
+        self.hip_autograd_split_bf16 = bool(hip_autograd_split_bf16)
         self.encoder = make_rdn()
         self.imnet = MLP(self.encoder.out_dim * 9 + 4, 3, [256, 256, 256, 256])
         self._packed = None
@@ -474,8 +484,11 @@ class LIIF(nn.Module, _GraphReplay):
             return liif_decode_features(feat, packed, size, split=split)
         return liif_decode_features(feat, self._packed_weights(feat.device), size)
 
-    def _forward_train(self, inp, size):
-        from .liif_training import decode_with_grad
+    def _forward_train(self, inp, size, split: bool = False):
+        if split:
+            from .liif_split_training import decode_with_grad
+        else:
+            from .liif_training import decode_with_grad
         if not inp.is_cuda:
             raise RuntimeError("diinn_amd: the training forward runs on a ROCm GPU only (no CPU implementation)")
         return decode_with_grad(self.imnet, self.gen_feat(inp), size)
@@ -484,6 +497,8 @@ class LIIF(nn.Module, _GraphReplay):
         if torch.is_grad_enabled() and self.hip_autograd:
             if inp.requires_grad or any(p.requires_grad for p in self.parameters()):
                 if bsize is None:
+                    if self.hip_split_bf16 and self.hip_autograd_split_bf16:
+                        return self._forward_train(inp, size, split=True)
                     if self.hip_split_bf16:
                         raise NotImplementedError("diinn_amd: LIIF trains in fp32 only: unset LIIF.hip_split_bf16 (the split-bf16 "
                                                   "decoder is inference-only), or call under torch.no_grad()")

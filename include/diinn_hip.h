@@ -708,6 +708,31 @@ int diinn_liif_backward_data(void* stream, const float* gout_planes_dev, const f
                              float* G_dev, int B, int H, int W, int Hu, int Wu);
 int diinn_liif_cell_sum(void* stream, const float* G1_dev, const int32_t* seg_h_dev, const int32_t* seg_w_dev,
                         float* dP_dev, float* dP_tiled_dev, int B, int H, int W, int Hu, int Wu);
+/* LIIF under autograd in split-bf16 arithmetic (added under ABI 11, backward compatible; opt-in, not in the reference): the two
+ * kernels of the step that are bound by the fp32 matrix rate, with the three hidden 256 x 256 products of every virtual pixel on the
+ * bf16 matrix cores, both ways -- every operand carried as hi = bf16(v), lo = bf16(v - hi), a product formed as
+ * w_lo.x_hi + w_hi.x_lo + w_hi.x_hi on one fp32 accumulator.  The planes keep diinn_liif_train_fwd's fp32 contract (layout, values
+ * unsplit, padding of a ragged last tile neither written nor read as data), so either forward may be followed by either backward,
+ * and diinn_plane_gemm_nt, diinn_plane_rowdot and diinn_liif_cell_sum run on them unchanged.
+ * split_dev (both): the split training image of packed_dev, diinn_split_train_floats() floats (diinn_pack_split_train on the
+ *   gathered device image, or diinn_pack_split_train_host; 16-byte aligned).  The forward reads pieces 1 / 3 of its forward half
+ *   (imnet.layers.{2,4,6} from section WL), the backward pieces 1 / 3 of its backward half (their transposes from section WLT).
+ * diinn_liif_train_fwd_x3: diinn_liif_decode_x3 (same kernels' arithmetic on the same images: out_dev is diinn_liif_decode_x3's
+ *   output bit for bit) that additionally writes acts_dev [4][ceil(4 N / 32)][256][32] = h_1..h_4, each the unsplit fp32 relu(a_l)
+ *   that the next layer splits (h_4: the value the head consumes); h_1 is diinn_liif_train_fwd's bit for bit (layer 1 is fp32 in
+ *   both).  diinn_liif_decode_x3's argument checks in its order with acts_dev among the pointers, then diinn_liif_train_fwd's
+ *   limits (4 N <= DIINN_TRAIN_MAX_PIXELS).  The image may be a gathered one (no validity word is asked for: only permutation
+ *   sections are read).  workspace_dev: diinn_workspace_bytes.  2 kernels.
+ * diinn_liif_backward_data_x3: diinn_liif_backward_data with the three products W_l^T g_a,l (l = 4, 3, 2) in the split arithmetic;
+ *   g_a,4 = (L^T (w_v g)) [h_4 > 0] stays fp32 and is diinn_liif_backward_data's slot 3 bit for bit on the same acts_dev; every gate
+ *   is taken from the saved plane (a zero or a NaN closes it); G_dev holds unsplit fp32 values.  diinn_liif_backward_data's argument
+ *   checks in its order with split_dev among the pointers and under packed_dev's alignment rule.  Reads section 6 (L) of packed_dev.
+ *   3 kernels.
+ * Both validate every argument before the first launch, allocate nothing, do not synchronise, and are deterministic. */
+int diinn_liif_train_fwd_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* split_dev,
+                            float* workspace_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu);
+int diinn_liif_backward_data_x3(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
+                                const float* split_dev, float* G_dev, int B, int H, int W, int Hu, int Wu);
 
 /* ---- MetaSR comparison decoder ----------------------
  * Replaces: MetaSR.query_rgb + batched_predict + reshape_pred (metasr.py:70-104,106-123): per HR pixel the
