@@ -29,7 +29,8 @@ HEAD3X3_MAGIC = 0x44494833             # validity word of the mode-4 head image 
 INITQ_MAGIC = 0x44494951               # validity word of the init_q image (diinn_pack_initq)
 INITQ_X3_MAGIC = 0x44495833            # validity word of the init_q split image (diinn_pack_initq_x3)
 INITQ_TRAIN_MAGIC = 0x44495154         # validity word of the init_q training image (diinn_pack_initq_train)
-PACKED_MAGIC_WPU = 0x44495750          # a training image: permutation sections + section 13 (WPU) filled on the device
+INITQ_SPLIT_TRAIN_MAGIC = 0x44495153   # validity word of the init_q split training image (diinn_pack_initq_split_train)
+PACKED_MAGIC_WPU = 0x44495750         # a training image: permutation sections + section 13 (WPU) filled on the device
 P_ALGO_DIRECT, P_ALGO_WINOGRAD, P_ALGO_DIRECT_BF16, P_ALGO_DIRECT_BF16X3 = 0, 1, 2, 3
 RDN_ALGO_AUTO, RDN_ALGO_DIRECT, RDN_ALGO_WINO, RDN_ALGO_WINO4, RDN_ALGO_X3 = 0, 1, 2, 3, 4
 COMPUTE_F32 = 0
@@ -231,6 +232,13 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_backward_data_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_longlong]),
+    "diinn_initq_split_train_floats": (C.c_size_t, []),
+    "diinn_pack_initq_split_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diinn_pack_initq_split_train_host": (C.c_int, [_f, _f, _f]),
+    "diinn_decode_initq_train_fwd_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "diinn_initq_backward_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "diinn_head3x3_from_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int]),
     "diinn_backward_data_head3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

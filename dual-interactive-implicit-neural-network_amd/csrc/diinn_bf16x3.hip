@@ -77,6 +77,12 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 // training image p.split (diinn_layout.h: section WLX's piece layout without the division by 2 pi).  Layer 0, P, the seeds, the
 // sine and the head stay fp32 as in inference.  The one-block form only.
 //
+// INITQ | SAVE (init_q=True, mode 3, under autograd, behind ImplicitDecoder.hip_autograd_initq_split_bf16; diinn_decode_initq_train_fwd_x3):
+// the two together, an instantiation of its own.  INITQ's record addressing -- the seeds and layer 0's argument come from the
+// pixel's record, no Q0 table is loaded or read -- under SAVE's contract: `p.P` holds the planes of the WHOLE image as
+// initq_planes_x3_kernel<SIN | INITQ_X3_RAD> wrote them, channels 1024..1279 in RADIANS; k_i / s_i leave as tiled fp32 planes, the
+// biases come from section BQ and the weight stream from the forward half of the split training image of the body image.
+//
 // QONLY (decoder modes 1/2, init_q=False, inference, behind ImplicitDecoder.hip_modes_split_bf16; SIN_X = sine mode | X3_QONLY):
 // decode_kernel<SIN, KPART = false>'s contract on this kernel's arithmetic.  cell_chain_kernel (fp32) has left the rectified
 // modulation k_i of the pixel's LR cell in slot i of P; it seeds the modulation accumulator, which no MFMA touches, and the
@@ -101,7 +107,6 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     constexpr bool QONLY = (SIN_X & X3_QONLY) != 0;
     constexpr bool TAPF = (SIN_X & X3_TAPS) != 0;
     static_assert(SIN_X >= 0 && SIN_X < 2 * X3_TAPS && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ | X3_SAVE | X3_QONLY | X3_TAPS");
-    static_assert(!(INITQ && SAVE), "the SAVE form covers init_q=False only");
     static_assert(!((QONLY || TAPF) && (INITQ || SAVE)) && !(QONLY && TAPF), "the Q-only and the tap form: init_q=False, inference, one at a time");
     constexpr size_t S_Q0 = SAVE ? OFF_Q0 : OFF_Q0R, S_BQ = SAVE ? OFF_BQ : OFF_BQR;
     auto sine = [](float v) {
@@ -826,7 +831,7 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
 
 // the forms the flags of SIN_X select (diinn_device.h lists what each reads from p); the one-block kernel only
 int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form) {
-    return launch_sin<X3_INITQ, X3_SAVE, X3_QONLY, X3_TAPS>(sin_mode, form, [&](auto S, auto F) {
+    return launch_sin<X3_INITQ, X3_SAVE, X3_QONLY, X3_TAPS, X3_INITQ | X3_SAVE>(sin_mode, form, [&](auto S, auto F) {
         hipLaunchKernelGGL(decode_bf16x3_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
     });
 }

@@ -1024,7 +1024,8 @@ static int check_train_args(int B, int H, int W, int Hu, int Wu, int sin_mode, l
 
 // The training forward's per-pixel layers over the whole image, one workgroup per four plane tiles: P_dev holds rows `pw` -- the
 // hoisted conv (or, kpart = false, the per-cell chain) of all H LR rows, or (initq) the pixel planes of all Hu HR rows, in
-// radians.  split_dev (mode 3 from P only): the split training image -- decode_bf16x3_kernel<SIN | X3_SAVE> runs the layers.
+// radians.  split_dev (mode 3, from P or from init_q's planes): the split training image -- decode_bf16x3_kernel<SIN | X3_SAVE>, or
+// with initq <SIN | X3_INITQ | X3_SAVE>, runs the layers.
 static int train_fwd_launch(void* stream, const float* P_dev, const float* packed_dev, float* out_dev, float* acts_dev,
                             int B, int H, int W, int Hu, int Wu, long long npix, int sin_mode, RowWin pw, bool initq, bool kpart,
                             const float* split_dev = nullptr) {
@@ -1033,7 +1034,7 @@ static int train_fwd_launch(void* stream, const float* P_dev, const float* packe
     p.acts = acts_dev; p.npix = npix;
     if (split_dev) {
         p.split = split_dev;
-        return launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_SAVE);
+        return launch_decode_bf16x3_form(stream, p, grid, sin_mode, initq ? (X3_INITQ | X3_SAVE) : X3_SAVE);
     }
     int st = DIINN_ERR_UNSUPPORTED;
     pick<0, DECODE_INITQ>(initq ? DECODE_INITQ : 0, [&](auto Q) {
@@ -1079,6 +1080,25 @@ static int initq_train_fwd_impl(void* stream, const float* feat_dev, const float
     }
     return train_fwd_launch(stream, pix_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, npix, sin_mode, RowWin{0, Hu}, true,
                             chain == 0);
+}
+
+// The same in split-bf16 arithmetic (mode 3): initq_planes_x3_kernel<SIN | INITQ_X3_RAD> on the init_q training image and the init_q
+// split training image, then decode_bf16x3_kernel<SIN | X3_INITQ | X3_SAVE> on the split training image of the body image.
+static int initq_train_fwd_x3_impl(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                   const float* split_dev, const float* initq_split_dev, float* pix_dev, float* out_dev,
+                                   float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    if (!all_set(feat_dev, packed_dev, train_image_dev, split_dev, initq_split_dev, pix_dev, out_dev, acts_dev)) return DIINN_ERR_INVALID_ARG;
+    long long npix;
+    int st = check_train_args(B, H, W, Hu, Wu, sin_mode, &npix);
+    if (st) return st;
+    if ((((size_t)packed_dev) | ((size_t)train_image_dev) | ((size_t)split_dev) | ((size_t)initq_split_dev) | ((size_t)pix_dev)) & 15)
+        return DIINN_ERR_INVALID_ARG;                               // 16-byte pieces and seeds
+    st = check_grid(grid_blocks(0, Hu, WG_H), B);
+    if (st) return st;
+    st = launch_initq_planes_x3(stream, feat_dev, packed_dev, train_image_dev, initq_split_dev, pix_dev, B, H, W, Hu, Wu, 0, Hu, sin_mode, true);
+    if (st) return st;
+    return train_fwd_launch(stream, pix_dev, packed_dev, out_dev, acts_dev, B, H, W, Hu, Wu, npix, sin_mode, RowWin{0, Hu}, true, true,
+                            split_dev);
 }
 
 extern "C" {
@@ -1296,6 +1316,13 @@ int diinn_decode_train_fwd_x3(void* stream, const float* P_dev, const float* pac
 int diinn_decode_initq_train_fwd(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
                                  float* pix_dev, float* out_dev, float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
     return initq_train_fwd_impl(stream, feat_dev, packed_dev, train_image_dev, pix_dev, out_dev, acts_dev, B, H, W, Hu, Wu, sin_mode, 0);
+}
+
+int diinn_decode_initq_train_fwd_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                    const float* split_dev, const float* initq_split_dev, float* pix_dev, float* out_dev,
+                                    float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode) {
+    return initq_train_fwd_x3_impl(stream, feat_dev, packed_dev, train_image_dev, split_dev, initq_split_dev, pix_dev, out_dev, acts_dev,
+                                   B, H, W, Hu, Wu, sin_mode);
 }
 
 // init_q with modes 1/2 under autograd: the radians planes of the whole image, pixel_chain_kernel over all Hu rows, then

@@ -23,6 +23,7 @@
 //   diinn_liif_x3.hip          liif_x3_kernel (LIIF's hidden layers in split-bf16 arithmetic, opt-in; inference), liif_x3_save_kernel (its training forward)
 //   diinn_liif_split_training.hip  liif_bwd_layer_x3_kernel (LIIF under autograd in split-bf16 arithmetic: the backward chain)
 //   diinn_initq_training.hip   initq_bwd_kernel (init_q under autograd: the transposed per-pixel GEMMs), cell_sum_rows_kernel, fold3x3_kernel
+//   diinn_initq_split_training.hip  initq_split_train_pack_kernel, initq_bwd_x3_kernel (init_q under autograd in split-bf16 arithmetic)
 //   diinn_encoder.hip          RDN trunk: conv_ksplit kernels (small maps), conv1x1_stream_kernel, sfe1_conv_kernel
 //   diinn_winograd.hip         RDN trunk: conv_wino_kernel / conv_wino_half_kernel (3x3 layers, Winograd F(2x2,3x3))
 //   diinn_conv_x3.hip          RDN trunk, optional split-bf16 arithmetic: conv3x3_x3m_kernel / conv3x3_x3_kernel (3x3 layers), conv1x1_x3_kernel (fusion)
@@ -438,13 +439,15 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
 // diinn_bf16x3.hip: the other forms of decode_bf16x3_kernel<SIN | form>, the one-block kernel only:
 //   X3_INITQ  from the pixel planes of init_q (p.P = the planes of HR rows [p.y0, p.y1), p.Prow0 = p.y0)
 //   X3_SAVE   the training forward (`grid` = workgroups of four plane tiles; p.split = the split training image)
+//   X3_INITQ | X3_SAVE   init_q's training forward: X3_SAVE with p.P = the radians pixel planes of the whole image
 //   X3_QONLY  decoder modes 1/2 (P holds the per-cell chain)
 //   X3_TAPS   mode 4's tap form (p.out = the tap buffer, p.head3 = the head image)
 constexpr int X3_INITQ = 4, X3_SAVE = 8, X3_QONLY = 16, X3_TAPS = 32;
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form);
-// diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1)
+// diinn_initq_x3.hip: initq_planes_x3_kernel for HR rows [y0,y1); rad: the radians form (the split training forward), initq_dev the
+// init_q training image and initq_x3_dev the init_q split training image
 __attribute__((visibility("hidden")))
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                            const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                           int sin_mode);
+                           int sin_mode, bool rad = false);

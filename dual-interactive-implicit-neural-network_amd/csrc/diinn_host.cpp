@@ -592,6 +592,32 @@ int diinn_pack_initq_train(const float* Fw, const float* Fb, const float* Q0w, c
     return DIINN_OK;
 }
 
+// ---- init_q under autograd in split-bf16 arithmetic: the init_q split training image (diinn_layout.h) -----------
+// The host twin of diinn_pack_initq_split_train (diinn_initq_split_training.hip): the same pairs from HOST images, by the same
+// iqs_source().
+size_t diinn_initq_split_train_floats(void) { return IQS_FLOATS; }
+
+int diinn_pack_initq_split_train_host(const float* packed, const float* train_image, float* initq_split) {
+    if (!packed || !train_image || !initq_split) return DIINN_ERR_INVALID_ARG;
+    for (int pair = 0; pair < IQS_PAIRS; ++pair) {
+        uint16_t* xhi = reinterpret_cast<uint16_t*>(initq_split + iqs_pair_offset(pair));
+        uint16_t* xlo = xhi + 64 * 8;
+        for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 8; ++j) {
+                int img;
+                const size_t at = iqs_source(pair, lane, j, img);
+                const float v = img < 0 ? 0.0f : (img ? train_image : packed)[at];
+                const uint16_t hi = f32_to_bf16(v);
+                xhi[lane * 8 + j] = hi;
+                xlo[lane * 8 + j] = f32_to_bf16(v - bf16_to_f32(hi));   // exact difference, then one rounding
+            }
+    }
+    const uint32_t magic = DIINN_INITQ_SPLIT_TRAIN_MAGIC;
+    std::memcpy(initq_split + IQS_OFF_WORD, &magic, 4);
+    for (int i = 1; i < 4; ++i) initq_split[IQS_OFF_WORD + i] = 0.0f;
+    return DIINN_OK;
+}
+
 size_t diinn_initq_pix_bytes(int B, int Wu, int rows) {
     if (B <= 0 || Wu <= 0 || rows <= 0) return 0;
     return (size_t)B * (size_t)rows * (size_t)Wu * PIX_CH * sizeof(float);

@@ -33,8 +33,8 @@
 struct InitqX3Params {
     const float* feat;   // [B,64,H,W]
     const float* Wt;     // body image (sections WPX, BK)
-    const float* iq;     // init_q image (F)
-    const float* iqx;    // init_q split image (diinn_pack_initq_x3)
+    const float* iq;     // init_q image (F); INITQ_X3_RAD: the init_q training image (F, BQ0 in radians)
+    const float* iqx;    // init_q split image (diinn_pack_initq_x3); INITQ_X3_RAD: the init_q split training image (WX, Q0X)
     float* pix;          // [B][y1 - y0][Wu][PIX_CH]
     int B, H, W, Hu, Wu, y0, y1;
     float ratio;         // fp32(H*W / (Hu*Wu))   (diinn.py:166)
@@ -50,9 +50,19 @@ constexpr int IX_STEP_BYTES = 4 * PIECE_BYTES;            // the four weight pie
 constexpr int IX_PAIR_BYTES = IX_KS * IX_STEP_BYTES;      // an M-tile pair's weights: 144 KiB
 constexpr int IX_PF = 4;                                  // weight ring depth in k-steps
 
-template <int SIN_MODE>
+// INITQ_X3_RAD (the split training forward, diinn_decode_initq_train_fwd_x3): the radians form, as INITQ_RAD is initq_planes_kernel's.
+// `iq` is the init_q TRAINING image (F and BQ0 in radians, DIINN_INITQ_TRAIN_MAGIC), `iqx` the init_q SPLIT TRAINING image
+// (diinn_layout.h: WX in section WPX's order, Q0X in the init_q split image's, nothing divided by 2 pi, its own validity word), so
+// E = dsin<SIN_MODE>(a) takes a in radians, BOTH GEMMs stream from `iqx` -- the training body image has no section WPX -- and
+// channels 1024..1279 leave as Q0 . E + bQ0 in radians, as decode_bf16x3_kernel<SIN | X3_INITQ | X3_SAVE> saves them.  Launched over
+// the whole image.  The flag rides in the template argument, SIN_X = sine mode | INITQ_X3_RAD: the inference instantiations keep
+// their symbols and their instructions.
+constexpr int INITQ_X3_RAD = 4;
+template <int SIN_X>
 __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const InitqX3Params p) {
-    static_assert(SIN_MODE >= DIINN_SIN_ACCURATE && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode");
+    constexpr int SIN_MODE = SIN_X & (INITQ_X3_RAD - 1);
+    constexpr bool RAD = (SIN_X & INITQ_X3_RAD) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * INITQ_X3_RAD && SIN_MODE >= DIINN_SIN_ACCURATE && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | INITQ_X3_RAD");
     __shared__ __attribute__((aligned(16))) bf16x8 buf[IX_KS][2][2][64];   // [k-step][hi, lo][N-tile][lane] = 144 KiB
     __shared__ __attribute__((aligned(16))) float tr[IX_WAVES][16 * IX_TR_PITCH];   // 10 KiB
     const int lane = threadIdx.x & 63;
@@ -90,7 +100,8 @@ __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const In
                 float a = __builtin_fmaf(F[2 * UNF + n], p.ratio, F[3 * UNF + n]);
                 a = __builtin_fmaf(F[1 * UNF + n], relw, a);
                 a = __builtin_fmaf(F[0 * UNF + n], relh, a);
-                const float e = dsin_rev<SIN_MODE>(a);
+                float e;
+                if constexpr (RAD) e = dsin<SIN_MODE>(a); else e = dsin_rev<SIN_MODE>(a);
                 const __bf16 hi = (__bf16)e;
                 eh[jj] = hi;
                 el[jj] = (__bf16)(e - (float)hi);
@@ -196,7 +207,16 @@ __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const In
     };
 
     __syncthreads();                                             // hi/lo(E) is in LDS
-    {
+    if constexpr (RAD) {
+        const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)p.iqx, 0, (int)(IQS_FLOATS * sizeof(float)), 0x00020000);
+        // a training image or a split training image without its validity word answers NaN in every sine argument
+        const bool ok = __builtin_bit_cast(unsigned, p.iqx[IQS_OFF_WORD]) == DIINN_INITQ_SPLIT_TRAIN_MAGIC &&
+                        __builtin_bit_cast(unsigned, p.iq[IQ_OFF_BQ0 + HID]) == DIINN_INITQ_TRAIN_MAGIC;
+        const unsigned nanm = ok ? 0u : 0x7fc00000u;
+        gemm(IC<1>{}, qrs, (int)(IQS_OFF_Q0X * sizeof(float)) + (wave >> 1) * IX_PAIR_BYTES + (wave & 1) * 2 * PIECE_BYTES,
+             p.iq + IQ_OFF_BQ0 + 32 * wave, nanm, PCH + 32 * wave);
+    } else {
         const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)p.iqx, 0, (int)(IQX_FLOATS * sizeof(float)), 0x00020000);   // reads past the end return 0
         // an init_q image or a split image without its validity word answers NaN in every sine argument
@@ -252,7 +272,13 @@ __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const In
         }
     }
     __syncthreads();                                             // hi/lo(E * X) is in LDS
-    {
+    if constexpr (RAD) {                                         // Wx from the split training image; bK from the body image (a permutation section)
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)p.iqx, 0, (int)(IQS_FLOATS * sizeof(float)), 0x00020000);
+#pragma unroll 1
+        for (int mp = 2 * wave; mp < 2 * wave + 2; ++mp)
+            gemm(IC<2>{}, wrs, (int)(IQS_OFF_WX * sizeof(float)) + mp * IX_PAIR_BYTES, p.Wt + OFF_BK + 64 * mp, 0u, 64 * mp);
+    } else {
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
         const unsigned nanm = derived_nan_mask(p.Wt);            // a body image without its derived sections (WPX) answers NaN
@@ -264,7 +290,7 @@ __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const In
 
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                            const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                           int sin_mode) {
+                           int sin_mode, bool rad) {
     if (int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev)) return st;
     const dim3 grid(grid_blocks(0, Wu, IX_TW), grid_blocks(y0, y1, IX_TH), B);
     if (int st = check_grid(grid.y, B)) return st;
@@ -277,13 +303,13 @@ int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* pac
     p.aw = make_axis(W, Wu, small);
     // streaming stores once the planes no longer fit beside anything in the 256 MiB last-level cache (launch_P's rule)
     p.stream_stores = (double)B * (y1 - y0) * Wu * PIX_CH * 4.0 >= 128.0 * 1024 * 1024;
-    return launch_sin(sin_mode, [&](auto S) {
-        hipLaunchKernelGGL(initq_planes_x3_kernel<decltype(S)::value>, grid, dim3(64 * IX_WAVES), 0, (hipStream_t)stream, p);
+    return launch_sin<0, INITQ_X3_RAD>(sin_mode, rad ? INITQ_X3_RAD : 0, [&](auto S, auto F) {
+        hipLaunchKernelGGL(initq_planes_x3_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(64 * IX_WAVES), 0, (hipStream_t)stream, p);
     });
 }
 
 extern "C" int diinn_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                                      const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0,
                                      int y1, int sin_mode) {
-    return launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+    return launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
 }

@@ -191,6 +191,72 @@ constexpr size_t ST_OFF_FWD   = 0;
 constexpr size_t ST_OFF_BWD   = SZ_WLX;
 constexpr size_t ST_FLOATS    = 2 * SZ_WLX;                     // 786,432 floats = 3 MiB
 
+// ---- decoder init_q=True, mode 3, under autograd in split-bf16 arithmetic: the init_q SPLIT TRAINING image
+// (diinn_pack_initq_split_train; host twin diinn_pack_initq_split_train_host) ----
+// A fourth image of a training step, beside the body image, its split training image (above: the layers and the chain) and the init_q
+// training image.  Filled on the device once per weight version from section WP of the body image and from the Q0W part of the init_q
+// training image -- both in RADIANS, nothing is divided by 2 pi.  Everything in it is a PAIR of 1 KiB pieces [lane 64][j 8] bf16, the hi
+// piece then the lo piece, hi = bf16(v), lo = bf16(v - hi), round to nearest even; pair p of the image starts at float
+// iqs_pair_offset(p).  A operands of v_mfma_f32_32x32x16_bf16: lane & 31 is the output row of the M-tile, 8 (lane >> 5) + j the k index.
+//   WX  [og 16][group 4][tap 9][M-tile 2]   section WPX's order (the training body image carries permutation sections only: WPX does not
+//       exist there): output channel o = 64 og + 32 mt + (lane & 31) of the 1024 (o = 256 i + ch: Wx_0 = K.0.weight, Wx_i =
+//       K.i.weight[:, 256:]), unfolded input n = c * 9 + tap with c = 16 group + 8 (lane >> 5) + j.
+//   Q0X [og 4][group 4][tap 9][M-tile 2]    the init_q split image's order: Q.0.weight[o = 64 og + 32 mt + (lane & 31)][n], in radians.
+//   the image's own validity word DIINN_INITQ_SPLIT_TRAIN_MAGIC and three zero floats (IQS_OFF_WORD); without it the kernels that
+//       read the image answer NaN.
+//   WXT [wave 4][chunk 4][ks 16][M-tile 5]  Wx^T as [640 x 1024], initq_bwd_x3_kernel's stream order: a wave owns 5 of the 20 M-tiles,
+//       output row n = 32 (5 wave + mt) + (lane & 31) (n >= 576: zero), k-step ks of chunk i covers rows ch = 16 ks + 8 (lane >> 5) + j
+//       of the 256-row gate-gradient group g_a,i; value = Wx_i[ch][n].
+//   Q0T [wave 4][ks 16][M-tile 5]           Q0^T as [640 x 256], the same order for the one chunk g_s,0; value = Q.0.weight[ch][n].
+constexpr int    IQS_PAIRS_WX  = 16 * 4 * 9 * 2;                 // 1,152
+constexpr int    IQS_PAIRS_Q0X = 4 * 4 * 9 * 2;                  // 288
+constexpr int    IQS_PAIRS_WXT = 4 * 4 * 16 * IQT_MT;            // 1,280
+constexpr int    IQS_PAIRS_Q0T = 4 * 16 * IQT_MT;                // 320
+constexpr int    IQS_PAIRS_FWD = IQS_PAIRS_WX + IQS_PAIRS_Q0X;
+constexpr int    IQS_PAIRS     = IQS_PAIRS_FWD + IQS_PAIRS_WXT + IQS_PAIRS_Q0T;   // 3,040
+constexpr size_t IQS_PAIR      = 2 * WLB_PIECE;                  // floats per pair: 512
+constexpr size_t IQS_OFF_WX    = 0;
+constexpr size_t IQS_OFF_Q0X   = IQS_OFF_WX + IQS_PAIRS_WX * IQS_PAIR;     // 589,824 (= SZ_WPX)
+constexpr size_t IQS_OFF_WORD  = IQS_OFF_Q0X + IQS_PAIRS_Q0X * IQS_PAIR;   // 737,280
+constexpr size_t IQS_OFF_WXT   = IQS_OFF_WORD + 4;                         // 737,284 (16-byte aligned)
+constexpr size_t IQS_OFF_Q0T   = IQS_OFF_WXT + IQS_PAIRS_WXT * IQS_PAIR;   // 1,392,644
+constexpr size_t IQS_FLOATS    = IQS_OFF_Q0T + IQS_PAIRS_Q0T * IQS_PAIR;   // 1,556,484
+constexpr size_t IQS_KSTEP     = IQT_MT * IQS_PAIR;              // floats of a wave's k-step in WXT / Q0T: 5 pairs = 10 KiB
+
+// float index of W[o][n = c * 9 + tap] inside a section in WP's order [mp][kg 72][t 2][lane 64][e 4] (WP itself, Q0W)
+DIINN_HD size_t wp_index(int o, int c, int tap) {
+    const int mo = o >> 5, kk = 32 * tap + (c >> 1), lane = 32 * (c & 1) + (o & 31);
+    return ((((size_t)(mo >> 1) * WP_KG + (kk >> 2)) * 2 + (mo & 1)) * 64 + lane) * 4 + (kk & 3);
+}
+DIINN_HD size_t iqs_pair_offset(int pair) {
+    return pair < IQS_PAIRS_FWD ? (size_t)pair * IQS_PAIR : IQS_OFF_WXT + (size_t)(pair - IQS_PAIRS_FWD) * IQS_PAIR;
+}
+// where element (lane, j) of pair `pair` comes from: img = 0, a float index of the body image (section WP); img = 1, of the init_q
+// training image (Q0W); img = -1: a padding row, zero.  The one statement of the layout the device packer and its host twin share.
+DIINN_HD size_t iqs_source(int pair, int lane, int j, int& img) {
+    const int h = lane >> 5, r = lane & 31;
+    int o, n;
+    bool q0;
+    if (pair < IQS_PAIRS_FWD) {
+        q0 = pair >= IQS_PAIRS_WX;
+        const int p = q0 ? pair - IQS_PAIRS_WX : pair;
+        const int mt = p & 1, tap = (p >> 1) % 9, group = ((p >> 1) / 9) & 3, og = (p >> 1) / 36;
+        o = 64 * og + 32 * mt + r;
+        n = (16 * group + 8 * h + j) * 9 + tap;
+    } else {
+        int p = pair - IQS_PAIRS_FWD;
+        q0 = p >= IQS_PAIRS_WXT;
+        if (q0) p -= IQS_PAIRS_WXT;
+        const int mt = p % IQT_MT, ks = (p / IQT_MT) & 15, rest = p / (IQT_MT * 16);
+        const int chunk = q0 ? 0 : (rest & 3), wave = q0 ? rest : (rest >> 2);
+        n = 32 * (IQT_MT * wave + mt) + r;
+        o = HID * chunk + 16 * ks + 8 * h + j;
+        if (n >= UNF) { img = -1; return 0; }
+    }
+    img = q0 ? 1 : 0;
+    return (q0 ? IQ_OFF_Q0W : OFF_WP) + wp_index(o, n / 9, n % 9);
+}
+
 // channel held by activation register (m, r) of lane-half h
 DIINN_HD int chan_of(int kk /* = 16*m + r */, int h) {
     const int m = kk >> 4, r = kk & 15;

@@ -589,36 +589,40 @@ class ImplicitDecoder(nn.Module):
     for mode 3, inference, fp32; with modes 1, 2, 4 (unless ``hip_initq_modes`` is set, below) or under autograd ``forward`` raises
     ``NotImplementedError``.
 
-    Seven opt-ins, each a plain attribute and a constructor keyword, default False.  Each opens exactly one more combination of
+    Eight opt-ins, each a plain attribute and a constructor keyword, default False.  Each opens exactly one more combination of
     (mode, ``init_q``, ``compute``, inference or autograd) and changes nothing for any other; "autograd" is ``forward(x, size,
     None)`` with grad enabled and something requiring it (``bsize`` given, or ``no_grad``, is the inference path, like the
     reference's ``batched_step``).  ``_route`` is the rule -- one table, every supported combination, the flag that opens it and
-    the refusal everything else gets -- and ``tests/test_decoder_routes.py`` pins it for every setting of the seven.
+    the refusal everything else gets -- and ``tests/test_decoder_routes.py`` pins it for every setting of the first seven (the eighth:
+    ``tests/test_initq_split_training.py``).
 
-    ============================  ==========================================  ===========================  =============================
-    flag                          opens                                       needs beside it              what keeps refusing with it
-    ============================  ==========================================  ===========================  =============================
-    ``hip_autograd``              autograd, ``init_q``, mode 3, fp32          --                           init_q modes 1/2/4, mode 4,
-                                  (``initq_training``)                                                     every bf16 arithmetic
-    ``hip_autograd_mode4``        autograd, mode 4, ``init_q=False``, fp32    output >= 2 x 2              mode 4 with ``init_q`` or a
-                                  (``mode4_training``)                                                     bf16 arithmetic
-    ``hip_initq_modes``           inference, ``init_q``, modes 1/2/4, fp32    --                           autograd, bf16 arithmetics,
-                                  (``decode_features_initq``)                                 ``graphs=True``, sharded
-    ``hip_initq_split_bf16``      inference, ``init_q``, mode 3, "bf16x3"     ``compute="bf16x3"``         "bf16", "bf16_full", autograd,
-                                                                                           init_q modes 1/2/4, graphs,
-                                                                                                           sharded
-    ``hip_autograd_initq_modes``  autograd, ``init_q``, modes 1/2/4, fp32     ``hip_initq_modes``          bf16 arithmetics, graphs,
-                                  (``initq_modes_training``)     (alone it does nothing)      sharded
-    ``hip_autograd_split_bf16``   autograd, mode 3, ``init_q=False``,         ``compute="bf16x3"``         modes 1/2/4 and ``init_q``
-                                  "bf16x3" both ways (``split_training``;                                  in "bf16x3" under autograd,
-                                  DESIGN.md 3.7f)                                                          "bf16", "bf16_full", graphs,
-                                                                                                           sharded
-    ``hip_modes_split_bf16``      inference, modes 1/2/4, ``init_q=False``,   ``compute="bf16x3"``         autograd in "bf16x3", init_q
-                                  "bf16x3" (``decode_features(modes_x3=       (``graphs=True`` replays     modes 1/2/4 in any bf16,
-                                  True)``)                    it)                          "bf16", "bf16_full", sharded
-    ============================  ==========================================  ===========================  =============================
+    ==================================  ==========================================  ===========================  =============================
+    flag                                opens                                       needs beside it              what keeps refusing with it
+    ==================================  ==========================================  ===========================  =============================
+    ``hip_autograd``                    autograd, ``init_q``, mode 3, fp32          --                           init_q modes 1/2/4, mode 4,
+                                        (``initq_training``)                                                     every bf16 arithmetic
+    ``hip_autograd_mode4``              autograd, mode 4, ``init_q=False``, fp32    output >= 2 x 2              mode 4 with ``init_q`` or a
+                                        (``mode4_training``)                                                     bf16 arithmetic
+    ``hip_initq_modes``                 inference, ``init_q``, modes 1/2/4, fp32    --                           autograd, bf16 arithmetics,
+                                        (``decode_features_initq``)                                 ``graphs=True``, sharded
+    ``hip_initq_split_bf16``            inference, ``init_q``, mode 3, "bf16x3"     ``compute="bf16x3"``         "bf16", "bf16_full", autograd,
+                                                                                                 init_q modes 1/2/4, graphs,
+                                                                                                                 sharded
+    ``hip_autograd_initq_modes``        autograd, ``init_q``, modes 1/2/4, fp32     ``hip_initq_modes``          bf16 arithmetics, graphs,
+                                        (``initq_modes_training``)     (alone it does nothing)      sharded
+    ``hip_autograd_split_bf16``         autograd, mode 3, ``init_q=False``,         ``compute="bf16x3"``         modes 1/2/4 and ``init_q``
+                                        "bf16x3" both ways (``split_training``;                                  in "bf16x3" under autograd,
+                                        DESIGN.md 3.7f)                                                          "bf16", "bf16_full", graphs,
+                                                                                                                 sharded
+    ``hip_modes_split_bf16``            inference, modes 1/2/4, ``init_q=False``,   ``compute="bf16x3"``         autograd in "bf16x3", init_q
+                                        "bf16x3" (``decode_features(modes_x3=       (``graphs=True`` replays     modes 1/2/4 in any bf16,
+                                        True)``)                    it)                          "bf16", "bf16_full", sharded
+    ``hip_autograd_initq_split_bf16``   autograd, ``init_q``, mode 3, "bf16x3"      ``compute="bf16x3"`` and     init_q modes 1/2/4 in any
+                                        both ways (``initq_split_training``;        ``hip_initq_split_bf16``     bf16, "bf16", "bf16_full",
+                                        DESIGN.md 3.7g)                             (alone it does nothing)      graphs, sharded
+    ==================================  ==========================================  ===========================  =============================
 
-    ``compute="f32"`` gives the fp32 bits whatever is set.  ``DIINN.set_split_bf16()`` sets none of the three split flags: a user who
+    ``compute="f32"`` gives the fp32 bits whatever is set.  ``DIINN.set_split_bf16()`` sets none of the four split flags: a user who
     wants the split arithmetic on such a model sets both."""
 
     hip_autograd = False
@@ -628,12 +632,13 @@ class ImplicitDecoder(nn.Module):
     hip_autograd_initq_modes = False
     hip_autograd_split_bf16 = False
     hip_modes_split_bf16 = False
+    hip_autograd_initq_split_bf16 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
                  hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False,
                  hip_autograd_initq_modes: bool = False, hip_autograd_split_bf16: bool = False,
-                 hip_modes_split_bf16: bool = False):
+                 hip_modes_split_bf16: bool = False, hip_autograd_initq_split_bf16: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
@@ -644,6 +649,7 @@ class ImplicitDecoder(nn.Module):
         self.hip_autograd_initq_modes = bool(hip_autograd_initq_modes)
         self.hip_autograd_split_bf16 = bool(hip_autograd_split_bf16)
         self.hip_modes_split_bf16 = bool(hip_modes_split_bf16)
+        self.hip_autograd_initq_split_bf16 = bool(hip_autograd_initq_split_bf16)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -751,12 +757,14 @@ class ImplicitDecoder(nn.Module):
         ("grad_mode4",       (4,),         False, ("f32",),    ("hip_autograd_mode4",)),
         ("grad_initq",       (3,),         True,  ("f32",),    ("hip_autograd",)),
         ("grad_initq_modes", (1, 2, 4),    True,  ("f32",),    ("hip_initq_modes", "hip_autograd_initq_modes")),
+        ("grad_initq_split", (3,),         True,  ("bf16x3",), ("hip_initq_split_bf16", "hip_autograd_initq_split_bf16")),
         (_INFERENCE_ONLY,    (1, 2, 4),    True,  None,        ()),
         (_NO_AUTOGRAD,       (1, 2, 3, 4), None,  None,        ()),
     )
     # the module whose decode_with_grad runs an autograd route
     _GRAD_MODULES = {"grad": "training", "grad_split": "split_training", "grad_mode4": "mode4_training",
-                     "grad_initq": "initq_training", "grad_initq_modes": "initq_modes_training"}
+                     "grad_initq": "initq_training", "grad_initq_modes": "initq_modes_training",
+                     "grad_initq_split": "initq_split_training"}
 
     def _route(self, wants_grad: bool) -> str:
         """The path of this (mode, init_q, compute) with the flags as they are set, under autograd or not: a route name, or the

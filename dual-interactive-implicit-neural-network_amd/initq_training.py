@@ -143,9 +143,11 @@ def embedding_planes(feat: torch.Tensor, p: Dict[str, torch.Tensor], size: Seque
 
 
 def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, params: Sequence[torch.Tensor],
-                              size: Sequence[int], need_feat_grad: bool = True
+                              size: Sequence[int], need_feat_grad: bool = True, product=None
                               ) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """Gradients of the ``init_q=True``, mode-3 decoder given d(loss)/d(out): the formula sheet (any device, the dtype of ``acts``).
+    ``product(w_t, g)``: how the four transposed per-pixel products -- the chain's Wq_i^T g_a,i and Qw_i^T g_s,i, dx' 's Wx_i^T g_a,i
+    and t = Q0^T g_s,0 -- are formed; None: a plain matmul (``initq_split_training`` passes the split-bf16 product).
 
     gout [B,3,Hu,Wu]; feat [B,64,H,W]; acts [4,2,256,N] plain planes k_i, s_i (radians); params in INITQ_PARAM_NAMES order.
     Returns (d feat or None, [d param ...] in INITQ_PARAM_NAMES order).  With the gates of mode 3,
@@ -155,6 +157,8 @@ def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torc
         dWx_i = g_a,i x'^T     dbK_i = rowsum g_a,i     dQ0 = g_s,0 E^T     dbQ0 = rowsum g_s,0     dFw = da syn^T     dbF = rowsum da
         dfeat = fold3x3(per-cell sums of U)   (the adjoint of unfold3x3; the features get no other gradient)."""
     dt = acts.dtype
+    if product is None:
+        product = torch.matmul
     p = {name: t.to(dt) for name, t in zip(INITQ_PARAM_NAMES, params)}
     feat = feat.to(dt)
     b, _, h, w = feat.shape
@@ -181,7 +185,7 @@ def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torc
         g_s = g_q * k * torch.cos(s)
         wfull = p[f"K.{i}.0.weight"].reshape(HIDDEN, -1)
         wx = wfull[:, HIDDEN:] if i else wfull
-        dxp += wx.t() @ g_a
+        dxp += product(wx.t(), g_a)
         d_wx = g_a @ xp.t()
         grads[f"K.{i}.0.bias"] = g_a.sum(1)
         grads[f"Q.{i}.0.bias"] = g_s.sum(1)
@@ -189,11 +193,11 @@ def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torc
             q_prev = acts[i - 1, 0] * torch.sin(acts[i - 1, 1])
             grads[f"K.{i}.0.weight"] = torch.cat([g_a @ q_prev.t(), d_wx], 1).reshape(HIDDEN, HIDDEN + UNFOLD, 1, 1)
             grads[f"Q.{i}.0.weight"] = (g_s @ q_prev.t()).reshape(HIDDEN, HIDDEN, 1, 1)
-            g_q = wfull[:, :HIDDEN].t() @ g_a + p[f"Q.{i}.0.weight"].reshape(HIDDEN, HIDDEN).t() @ g_s
+            g_q = product(wfull[:, :HIDDEN].t(), g_a) + product(p[f"Q.{i}.0.weight"].reshape(HIDDEN, HIDDEN).t(), g_s)
         else:
             grads["K.0.0.weight"] = d_wx.reshape(HIDDEN, UNFOLD, 1, 1)
             grads["Q.0.0.weight"] = (g_s @ e.t()).reshape(HIDDEN, UNFOLD, 1, 1)
-            d_e = dxp * xc + p["Q.0.0.weight"].reshape(HIDDEN, UNFOLD).t() @ g_s
+            d_e = dxp * xc + product(p["Q.0.0.weight"].reshape(HIDDEN, UNFOLD).t(), g_s)
     d_a = d_e * cos_a
     grads["first_layer.0.weight"] = (d_a @ syn_n.t()).reshape(UNFOLD, 3, 1, 1)
     grads["first_layer.0.bias"] = d_a.sum(1)
@@ -209,7 +213,8 @@ def backward_from_saved_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torc
 # ---------------------------------------------------------------------------
 def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Tensor, packed: torch.Tensor, image: torch.Tensor,
                          size: Sequence[int], need_feat_grad: bool = True, qonly: bool = False,
-                         head: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+                         head: Optional[torch.Tensor] = None, split: Optional[torch.Tensor] = None,
+                         initq_split: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
     """The same gradients as ``backward_from_saved_initq``, on the HIP kernels throughout:
       diinn_backward_data     3 x bwd_layer_kernel: the per-pixel chain of mode 3, unchanged; leaves G_i = (g_a,i ; g_s,i) and q_i
       diinn_plane_gemm_nt     [dWq_i ; dQw_i | bias sums] = G_i . q_{i-1}^T (i = 1..3), as in mode 3
@@ -225,8 +230,12 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
                 rows 0..255 of G_i; [dKk_i | dbK_i] = g_a,i . k_{i-1}^T (rows 0..255 of ``acts[i-1]``) and [dQw_i | dbQ_i] = g_s,i . q_{i-1}^T
                 are two 256-row plane GEMMs per layer in place of the stacked 512-row one;
       ``head``  (mode 4: the 3x3 head image; ``packed`` is the body image with a zero 1x1 head)  diinn_backward_data_head3x3, and
-                d last_layer.weight [3,256,3,3] from q_3 against the seven 4-row groups of dT, as in ``training.backward_fused``."""
-    c = ChainStage(gout, feat, acts, packed, size, head=head, qonly=qonly)
+                d last_layer.weight [3,256,3,3] from q_3 against the seven 4-row groups of dT, as in ``training.backward_fused``.
+    Mode 3 in split-bf16 arithmetic (initq_split_training.py) exchanges two kernels, each by a keyword of its own, so that the fp32 and
+    the split forms mix:
+      ``split``        the split training image of ``packed``: the chain on diinn_backward_data_x3 (bwd_layer_x3_kernel);
+      ``initq_split``  the init_q split training image: diinn_initq_backward_x3 (initq_bwd_x3_kernel) in place of diinn_initq_backward."""
+    c = ChainStage(gout, feat, acts, packed, size, head=head, qonly=qonly, split=split)
     b, h, w, hu, wu, n, t, g = c.b, c.h, c.w, c.hu, c.wu, c.n, c.t, c.g
     syn_t = c.geo["syn_t"]
     f32 = dict(dtype=torch.float32, device=c.dev)
@@ -242,7 +251,10 @@ def backward_fused_initq(gout: torch.Tensor, feat: torch.Tensor, acts: torch.Ten
     d_feat = None
     with _native.launcher(c.dev) as run:
         c.launch(run)
-        run("diinn_initq_backward", feat, g, image, u_t, da_t, xp_t, e_t, b, h, w, hu, wu)
+        if initq_split is None:
+            run("diinn_initq_backward", feat, g, image, u_t, da_t, xp_t, e_t, b, h, w, hu, wu)
+        else:
+            run("diinn_initq_backward_x3", feat, g, image, initq_split, u_t, da_t, xp_t, e_t, b, h, w, hu, wu)
         for i in range(4):                                       # dWx_i^T [640 x 256] = x' . g_a,i^T
             run("diinn_plane_gemm_nt", xp_t, PAD_ROWS, 0, g[i], 2 * HIDDEN, 0, partx[i], PAD_ROWS, HIDDEN, n, xsplit, 0)
         run("diinn_plane_gemm_nt", e_t, PAD_ROWS, 0, g[0], 2 * HIDDEN, HIDDEN, partx[4], PAD_ROWS, HIDDEN, n, xsplit, 0)

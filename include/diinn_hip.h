@@ -556,6 +556,39 @@ int diinn_decode_train_fwd_x3(void* stream, const float* P_dev, const float* pac
 int diinn_backward_data_x3(void* stream, const float* gout_planes_dev, const float* acts_dev, const float* packed_dev,
                            const float* split_dev, float* G_dev, float* Q_dev, long long npix);
 
+/* ---- Training, init_q=True, mode 3, in split-bf16 arithmetic (opt-in: ImplicitDecoder.hip_autograd_initq_split_bf16 beside
+ * hip_initq_split_bf16 and compute="bf16x3") ---------------------------------------------------------------------------------------
+ * diinn_decode_initq_train_fwd / diinn_initq_backward with their fp32-MFMA products on v_mfma_f32_32x32x16_bf16 under the rule above
+ * (hi = bf16(v), lo = bf16(v - hi); lo.hi + hi.lo + hi.hi, fp32 accumulation): the two plane GEMMs Wx . x' and Q0 . E, the three
+ * per-pixel layers, and the transposed per-pixel GEMMs dx' = sum_i Wx_i^T g_a,i, t = Q0^T g_s,0.  The sines, x' = E * X, the gates, the
+ * epilogue of the backward kernel, every plane and every parameter-gradient kernel are fp32 and unchanged; the planes keep the fp32
+ * entries' contract, so fp32 and split forwards and backwards mix.  Beside the body image (packed_dev), the init_q training image
+ * (train_image_dev) and the split training image of the body image (split_dev: diinn_pack_split_train), the
+ * INIT_Q SPLIT TRAINING IMAGE: diinn_initq_split_train_floats() = 1,556,484 floats.  Pairs of 1 KiB pieces [lane 64][j 8] bf16, hi then
+ * lo, A operands of the bf16 MFMA (row lane & 31 of the M-tile, k index 8 (lane >> 5) + j), all values in RADIANS:
+ *     WX   [og 16][group 4][tap 9][mt 2]   Wx[o = 64 og + 32 mt + (lane & 31)][n = c * 9 + tap], c = 16 group + 8 (lane >> 5) + j
+ *                                          (section 15's order; o = 256 i + ch, Wx_0 = K.0.weight, Wx_i = K.i.weight[:, 256:])     float 0
+ *     Q0X  [og 4][group 4][tap 9][mt 2]    Q.0.weight[o][n], the init_q split image's order, not divided by 2 pi            float 589,824
+ *     the validity word DIINN_INITQ_SPLIT_TRAIN_MAGIC, three zero floats (without it every output is NaN)                    float 737,280
+ *     WXT  [wave 4][chunk 4][ks 16][mt 5]  Wx_chunk[ch = 16 ks + 8 (lane >> 5) + j][n = 32 (5 wave + mt) + (lane & 31)]     float 737,284
+ *     Q0T  [wave 4][ks 16][mt 5]           Q.0.weight[ch][n]; rows n = 576..639 of both are zero                           float 1,392,644
+ * diinn_pack_initq_split_train fills it on the device from the body image (section 1) and the init_q training image (one kernel, the
+ * three pointers 16-byte aligned); diinn_pack_initq_split_train_host is its host twin, bit-identical.
+ * diinn_decode_initq_train_fwd_x3: diinn_decode_initq_train_fwd in that arithmetic: same outputs, layouts and status codes.  2 kernels.
+ * diinn_initq_backward_x3: diinn_initq_backward in that arithmetic: same inputs (G_dev may come from either chain), outputs and status
+ *   codes; dA_dev doubles as the kernel's parking space for t between its two reductions.  1 kernel, no atomics.
+ * All validate every argument before the first launch; none allocates or synchronises. */
+#define DIINN_INITQ_SPLIT_TRAIN_MAGIC 0x44495153u   /* "DIQS" */
+size_t diinn_initq_split_train_floats(void);
+int    diinn_pack_initq_split_train(void* stream, const float* packed_dev, const float* train_image_dev, float* initq_split_dev);
+int    diinn_pack_initq_split_train_host(const float* packed, const float* train_image, float* initq_split);
+int    diinn_decode_initq_train_fwd_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* train_image_dev,
+                                       const float* split_dev, const float* initq_split_dev, float* pix_dev, float* out_dev,
+                                       float* acts_dev, int B, int H, int W, int Hu, int Wu, int sin_mode);
+int    diinn_initq_backward_x3(void* stream, const float* feat_dev, const float* G_dev, const float* train_image_dev,
+                               const float* initq_split_dev, float* U_dev, float* dA_dev, float* XP_dev, float* E_dev,
+                               int B, int H, int W, int Hu, int Wu);
+
 /* The same for decoder modes 1 and 2 (autograd's backward through diinn.py:116-131, the per-pixel part): the modulation branch
  * does not see q there, so g_q,i-1 = Qw_i^T g_s,i alone (half the MFMAs and half the weight stream of diinn_backward_data).
  * Same buffers and layouts; acts_dev from diinn_decode_train_fwd_qonly.  Rows 0..255 of G_i hold g_q,i sin(s_i) [k_i > 0], the
