@@ -55,11 +55,6 @@
         __builtin_amdgcn_sched_barrier(0);                                            \
     } while (0)
 
-__device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);               // exact difference: v and hi share sign and exponent range
-}
-
 // INITQ (decoder init_q=True, mode 3, behind ImplicitDecoder.hip_initq_split_bf16): `p.P` holds the PIXEL PLANES of
 // initq_planes_x3_kernel (diinn_initq_x3.hip) -- per HR pixel a record of PIX_CH floats, channels 0..1023 what P holds per cell,
 // channels 1024..1279 layer 0's sine argument in revolutions -- so Pc points at the pixel's own record, layer 0 reads its argument
@@ -97,6 +92,13 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 // [B][p.Orows rows from p.Orow0][Wu][TAP_STRIDE].  The head table (27 x 256 floats from p.head3) sits behind the Q0 rows of
 // `tab`; mode 4's bias and both validity words belong to head3x3_reflect_kernel, which follows unchanged.
 // Both flags ride in SIN_X like X3_INITQ and X3_SAVE; both are one-block forms only.
+//
+// INITQ | QONLY (init_q=True, modes 1/2, inference, behind ImplicitDecoder.hip_initq_modes_split_bf16; diinn_decode_initq_mode{1,2}_x3):
+// INITQ's record addressing and layer-0 argument (channels 1024.. of the pixel's record, in revolutions) under the Q-only k-step;
+// the multiplier k_i is read from slot i of the record, where pixel_chain_x3_kernel (diinn_pixel_chain_x3.hip) wrote it.
+// INITQ | TAPS (init_q=True, mode 4, inference, the same switch; diinn_decode_initq_mode4_x3): INITQ's layers -- mode 3's, bit for bit --
+// from the planes of the tap rows, then the 27 fp32 tap sums on the unsplit q_3 into the tap buffer; the Q0 rows of `tab` stay unused.
+// Instantiations of their own (SIN_X = 20..22, 36..38): nothing that existed before changes its symbol, LDS size or instructions.
 // (X3_INITQ = 4, X3_SAVE = 8, X3_QONLY = 16, X3_TAPS = 32: diinn_device.h, beside launch_decode_bf16x3_form)
 typedef f32x4 __attribute__((may_alias)) f32x4_lds;
 template <int SIN_X>
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(256, 1) void decode_bf16x3_kernel(const DecodeParam
     constexpr bool QONLY = (SIN_X & X3_QONLY) != 0;
     constexpr bool TAPF = (SIN_X & X3_TAPS) != 0;
     static_assert(SIN_X >= 0 && SIN_X < 2 * X3_TAPS && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | X3_INITQ | X3_SAVE | X3_QONLY | X3_TAPS");
-    static_assert(!((QONLY || TAPF) && (INITQ || SAVE)) && !(QONLY && TAPF), "the Q-only and the tap form: init_q=False, inference, one at a time");
+    static_assert(!((QONLY || TAPF) && SAVE) && !(QONLY && TAPF), "the Q-only and the tap form: inference, one at a time");
     constexpr size_t S_Q0 = SAVE ? OFF_Q0 : OFF_Q0R, S_BQ = SAVE ? OFF_BQ : OFF_BQR;
     auto sine = [](float v) {
         if constexpr (SAVE) return dsin<SIN_MODE>(v); else return dsin_rev<SIN_MODE>(v);
@@ -831,7 +833,7 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
 
 // the forms the flags of SIN_X select (diinn_device.h lists what each reads from p); the one-block kernel only
 int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form) {
-    return launch_sin<X3_INITQ, X3_SAVE, X3_QONLY, X3_TAPS, X3_INITQ | X3_SAVE>(sin_mode, form, [&](auto S, auto F) {
+    return launch_sin<X3_INITQ, X3_SAVE, X3_QONLY, X3_TAPS, X3_INITQ | X3_SAVE, X3_INITQ | X3_QONLY, X3_INITQ | X3_TAPS>(sin_mode, form, [&](auto S, auto F) {
         hipLaunchKernelGGL(decode_bf16x3_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, p);
     });
 }

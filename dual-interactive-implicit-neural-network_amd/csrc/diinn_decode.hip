@@ -939,8 +939,8 @@ static int decode_mode4_band_impl(void* stream, const float* P_dev, const float*
                                    OutView{taprows.row0, taprows.rows, 0, 0, 0, 0});
     p.head3 = head_dev;
     int st;
-    if (x3)
-        st = launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_TAPS);
+    if (x3)                                                     // (from init_q's planes: <SIN | X3_INITQ | X3_TAPS>)
+        st = launch_decode_bf16x3_form(stream, p, grid, sin_mode, pw ? X3_TAPS : (X3_INITQ | X3_TAPS));
     else if (pw)
         st = launch_sin(sin_mode, [&](auto S) {
             hipLaunchKernelGGL((decode_kernel<decltype(S)::value, true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -976,7 +976,8 @@ int launch_head3x3_whole(void* stream, const float* taps_dev, const float* head_
 
 // init_q (mode 3): HR rows [y0,y1) from the pixel planes of exactly those rows (diinn_initq_planes) into a contiguous [B,3,Hu,Wu].
 // The throughput kernel only (no 16-pixel latency twin).  kpart = false: modes 1/2, the planes hold the per-pixel chain
-// (diinn_pixel_chain).  x3: split bf16, decode_bf16x3_kernel<SIN | X3_INITQ>.
+// (diinn_pixel_chain).  x3: split bf16, decode_bf16x3_kernel<SIN | X3_INITQ> (kpart = false: <SIN | X3_INITQ | X3_QONLY>, the chain
+// diinn_pixel_chain_x3's).
 static int decode_initq_band_impl(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,
                                   int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode, bool kpart = true,
                                   bool x3 = false) {
@@ -985,7 +986,7 @@ static int decode_initq_band_impl(void* stream, const float* pix_dev, const floa
     if (int st = check_grid(grid.y, B)) return st;
     const DecodeParams p = decode_params(pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, 0, Wu,
                                          RowWin{y0, y1 - y0}, contig(RowWin{0, Hu}, Wu));      // P = the pixel planes: HR rows
-    if (x3) return launch_decode_bf16x3_form(stream, p, grid, sin_mode, X3_INITQ);
+    if (x3) return launch_decode_bf16x3_form(stream, p, grid, sin_mode, kpart ? X3_INITQ : (X3_INITQ | X3_QONLY));
     return launch_sin<0, 1>(sin_mode, kpart, [&](auto S, auto K) {
         hipLaunchKernelGGL((decode_kernel<decltype(S)::value | DECODE_INITQ, decltype(K)::value>), grid, dim3(256), 0, (hipStream_t)stream, p);
     });
@@ -1010,6 +1011,21 @@ static int decode_initq_mode12(void* stream, const float* feat_dev, const float*
     st = pixel_chain_impl(stream, pix_dev, packed_dev, B, Wu, y1 - y0, rows512);
     if (st) return st;
     return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+// The same in split-bf16 arithmetic: initq_planes_x3_kernel (rows512: its 512-row form), pixel_chain_x3_kernel, then
+// decode_bf16x3_kernel<SIN | X3_INITQ | X3_QONLY>.  Every check before the first launch.
+static int decode_initq_mode12_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                  const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                                  int y0, int y1, int sin_mode, bool rows512) {
+    int st = initq_args_ok(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, out_dev);
+    if (st) return st;
+    if ((((size_t)pix_dev) | ((size_t)packed_dev) | ((size_t)initq_dev) | ((size_t)initq_x3_dev)) & 15) return DIINN_ERR_INVALID_ARG;
+    st = launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, rows512);
+    if (st) return st;
+    st = launch_pixel_chain_x3(stream, pix_dev, packed_dev, B, Wu, y1 - y0, rows512);
+    if (st) return st;
+    return decode_initq_band_impl(stream, pix_dev, packed_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, true);
 }
 
 // The training forward's checks after the pointers (its own order: the sine mode before the extent); npix = B Hu Wu
@@ -1144,6 +1160,40 @@ int diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float* p
     st = diinn_initq_planes(stream, feat_dev, packed_dev, initq_dev, pix_dev, B, H, W, Hu, Wu, ty0, ty1, sin_mode);
     if (st) return st;
     return diinn_decode_initq_mode4_band(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode);
+}
+
+// init_q with modes 1, 2 and 4 in split-bf16 arithmetic (behind ImplicitDecoder.hip_initq_modes_split_bf16): the arguments of the fp32
+// twins plus the init_q split image
+int diinn_decode_initq_mode1_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                                int y0, int y1, int sin_mode) {
+    return decode_initq_mode12_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, true);
+}
+
+int diinn_decode_initq_mode2_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu, int Wu,
+                                int y0, int y1, int sin_mode) {
+    return decode_initq_mode12_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+// planes of the tap rows (initq_planes_x3_kernel), decode_bf16x3_kernel<SIN | X3_INITQ | X3_TAPS>, head3x3_reflect_kernel unchanged
+int diinn_decode_initq_mode4_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                const float* initq_x3_dev, const float* head_dev, float* pix_dev, float* taps_dev, float* out_dev,
+                                int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode) {
+    if (!all_set(head_dev, taps_dev)) return DIINN_ERR_INVALID_ARG;
+    int st = initq_args_ok(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, out_dev);
+    if (st) return st;
+    if ((((size_t)pix_dev) | ((size_t)packed_dev) | ((size_t)initq_dev) | ((size_t)initq_x3_dev) | ((size_t)head_dev)) & 15)
+        return DIINN_ERR_INVALID_ARG;
+    int ty0, ty1, r0, r1;
+    st = diinn_mode4_rows(H, Hu, Wu, y0, y1, &ty0, &ty1, &r0, &r1);
+    if (st) return st;
+    st = check_grid(grid_blocks(ty0, ty1, WG_H), B);
+    if (st) return st;
+    st = launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, ty0, ty1, sin_mode);
+    if (st) return st;
+    return decode_mode4_band_impl(stream, pix_dev, packed_dev, head_dev, taps_dev, out_dev, B, H, W, Hu, Wu, y0, y1, sin_mode,
+                                  nullptr, RowWin{0, Hu}, true);
 }
 
 int diinn_decode_initq_band(void* stream, const float* pix_dev, const float* packed_dev, float* out_dev,

@@ -294,6 +294,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const float* group, 
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+// the two parts of a split-bf16 operand: hi = bf16(v), lo = bf16(v - hi)
+__device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)v;
+    lo = (__bf16)(v - (float)hi);               // exact difference: v and hi share sign and exponent range
+}
 
 // ---------------------------------------------------------------------------------
 // host side of the launch functions
@@ -442,6 +447,8 @@ int launch_decode_bf16x3(void* stream, const DecodeParams& p, int gx, int gy, in
 //   X3_INITQ | X3_SAVE   init_q's training forward: X3_SAVE with p.P = the radians pixel planes of the whole image
 //   X3_QONLY  decoder modes 1/2 (P holds the per-cell chain)
 //   X3_TAPS   mode 4's tap form (p.out = the tap buffer, p.head3 = the head image)
+//   X3_INITQ | X3_QONLY  init_q with modes 1/2 (the planes hold the per-pixel chain of pixel_chain_x3_kernel)
+//   X3_INITQ | X3_TAPS   init_q with mode 4 (the planes of the tap rows)
 constexpr int X3_INITQ = 4, X3_SAVE = 8, X3_QONLY = 16, X3_TAPS = 32;
 __attribute__((visibility("hidden")))
 int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, int sin_mode, int form);
@@ -450,4 +457,7 @@ int launch_decode_bf16x3_form(void* stream, const DecodeParams& p, dim3 grid, in
 __attribute__((visibility("hidden")))
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                            const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                           int sin_mode, bool rad = false);
+                           int sin_mode, bool rad = false, bool rows512 = false);
+// diinn_pixel_chain_x3.hip: pixel_chain_x3_kernel over the pixel planes of `rows` HR rows (diinn_pixel_chain's contract and checks)
+__attribute__((visibility("hidden")))
+int launch_pixel_chain_x3(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, bool bk_seeds);

@@ -58,11 +58,20 @@ constexpr int IX_PF = 4;                                  // weight ring depth i
 // the whole image.  The flag rides in the template argument, SIN_X = sine mode | INITQ_X3_RAD: the inference instantiations keep
 // their symbols and their instructions.
 constexpr int INITQ_X3_RAD = 4;
+// INITQ_X3_ROWS512 (decoder mode 1 with init_q, as INITQ_ROWS512 is initq_planes_kernel's: K.1..3 are [256 x 256], the feature halves
+// of Wx_1..3 do not exist): pass 1 is unchanged; pass 2 computes Wx_0 alone -- its four M-tile pairs as eight M-tiles, ONE per wave
+// (channels 32 wave .. 32 wave + 31, the hi / lo pieces of M-tile wave & 1 of pair wave >> 1) -- and channels 256..1023 of the record
+// are NOT written: pixel_chain_x3_kernel<BK_SEEDS = true> seeds layers 1..3 from bK_i and writes k_i there.  Channels 0..255 and
+// 1024..1279 hold the bits of the 1280-row form: an output channel's terms and their order do not depend on how many M-tiles share
+// the B fragments.  Rides in SIN_X as well, not combinable with INITQ_X3_RAD; inference only.
+constexpr int INITQ_X3_ROWS512 = 8;
 template <int SIN_X>
 __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const InitqX3Params p) {
     constexpr int SIN_MODE = SIN_X & (INITQ_X3_RAD - 1);
     constexpr bool RAD = (SIN_X & INITQ_X3_RAD) != 0;
-    static_assert(SIN_X >= 0 && SIN_X < 2 * INITQ_X3_RAD && SIN_MODE >= DIINN_SIN_ACCURATE && SIN_MODE <= DIINN_SIN_HW_REDUCED, "sine mode | INITQ_X3_RAD");
+    constexpr bool ROWS512 = (SIN_X & INITQ_X3_ROWS512) != 0;
+    static_assert(SIN_X >= 0 && SIN_X < 2 * INITQ_X3_ROWS512 && !(RAD && ROWS512) && SIN_MODE >= DIINN_SIN_ACCURATE && SIN_MODE <= DIINN_SIN_HW_REDUCED,
+                  "sine mode | INITQ_X3_RAD or sine mode | INITQ_X3_ROWS512");
     __shared__ __attribute__((aligned(16))) bf16x8 buf[IX_KS][2][2][64];   // [k-step][hi, lo][N-tile][lane] = 144 KiB
     __shared__ __attribute__((aligned(16))) float tr[IX_WAVES][16 * IX_TR_PITCH];   // 10 KiB
     const int lane = threadIdx.x & 63;
@@ -282,15 +291,21 @@ __global__ __launch_bounds__(64 * IX_WAVES) void initq_planes_x3_kernel(const In
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)p.Wt, 0, (int)(PACKED_FLOATS * sizeof(float)), 0x00020000);
         const unsigned nanm = derived_nan_mask(p.Wt);            // a body image without its derived sections (WPX) answers NaN
+        if constexpr (ROWS512) {                                 // M-tile `wave` of Wx_0's eight: pair wave >> 1, its pieces (wave & 1) hi, lo
+            gemm(IC<1>{}, wrs, (int)(OFF_WPX * sizeof(float)) + (wave >> 1) * IX_PAIR_BYTES + (wave & 1) * 2 * PIECE_BYTES,
+                 p.Wt + OFF_BK + 32 * wave, nanm, 32 * wave);
+        } else {
 #pragma unroll 1
-        for (int mp = 2 * wave; mp < 2 * wave + 2; ++mp)
-            gemm(IC<2>{}, wrs, (int)(OFF_WPX * sizeof(float)) + mp * IX_PAIR_BYTES, p.Wt + OFF_BK + 64 * mp, nanm, 64 * mp);
+            for (int mp = 2 * wave; mp < 2 * wave + 2; ++mp)
+                gemm(IC<2>{}, wrs, (int)(OFF_WPX * sizeof(float)) + mp * IX_PAIR_BYTES, p.Wt + OFF_BK + 64 * mp, nanm, 64 * mp);
+        }
     }
 }
 
 int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
                            const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1,
-                           int sin_mode, bool rad) {
+                           int sin_mode, bool rad, bool rows512) {
+    if (rad && rows512) return DIINN_ERR_UNSUPPORTED;
     if (int st = check_band_args(B, H, W, Hu, Wu, y0, y1, sin_mode, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev)) return st;
     const dim3 grid(grid_blocks(0, Wu, IX_TW), grid_blocks(y0, y1, IX_TH), B);
     if (int st = check_grid(grid.y, B)) return st;
@@ -303,7 +318,7 @@ int launch_initq_planes_x3(void* stream, const float* feat_dev, const float* pac
     p.aw = make_axis(W, Wu, small);
     // streaming stores once the planes no longer fit beside anything in the 256 MiB last-level cache (launch_P's rule)
     p.stream_stores = (double)B * (y1 - y0) * Wu * PIX_CH * 4.0 >= 128.0 * 1024 * 1024;
-    return launch_sin<0, INITQ_X3_RAD>(sin_mode, rad ? INITQ_X3_RAD : 0, [&](auto S, auto F) {
+    return launch_sin<0, INITQ_X3_RAD, INITQ_X3_ROWS512>(sin_mode, rad ? INITQ_X3_RAD : rows512 ? INITQ_X3_ROWS512 : 0, [&](auto S, auto F) {
         hipLaunchKernelGGL(initq_planes_x3_kernel<decltype(S)::value | decltype(F)::value>, grid, dim3(64 * IX_WAVES), 0, (hipStream_t)stream, p);
     });
 }
@@ -312,4 +327,11 @@ extern "C" int diinn_initq_planes_x3(void* stream, const float* feat_dev, const 
                                      const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0,
                                      int y1, int sin_mode) {
     return launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false);
+}
+
+// decoder mode 1 with init_q: channels 0..255 and 1024..1279 only (INITQ_X3_ROWS512)
+extern "C" int diinn_initq_planes_m1_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                        const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0,
+                                        int y1, int sin_mode) {
+    return launch_initq_planes_x3(stream, feat_dev, packed_dev, initq_dev, initq_x3_dev, pix_dev, B, H, W, Hu, Wu, y0, y1, sin_mode, false, true);
 }

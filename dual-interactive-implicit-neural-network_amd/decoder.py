@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _native
 # the formula sheets live in sheets.py; tests, tools and the documents cite them under this module's name
 from .sheets import (HIDDEN, INV_2PI_F32, P_CHANNELS, axis_tables, initq_forward_reference,  # noqa: F401
-                     initq_modes_forward_reference, initq_planes_reference, liif_x3_forward_reference,
+                     initq_modes_forward_reference, initq_modes_x3_forward_reference, initq_planes_reference, liif_x3_forward_reference,
                      modes_x3_forward_reference)
 
 IN_CHANNELS = 64
@@ -316,8 +316,9 @@ def decode_features_initq(feat: torch.Tensor, packed: torch.Tensor, initq: torch
                           head: Optional[torch.Tensor] = None, taps: Optional[torch.Tensor] = None,
                           pix: Optional[torch.Tensor] = None, rows: Optional[Tuple[int, int]] = None,
                           out: Optional[torch.Tensor] = None, sin_mode: int = _native.SIN_DEFAULT,
-                          planes_rows: Optional[int] = None) -> torch.Tensor:
-    """``init_q=True`` with decoder modes 1, 2 and 4 (fp32, inference): encoder features ``feat`` [B,64,H,W] -> RGB [B,3,Hu,Wu].
+                          planes_rows: Optional[int] = None, compute: str = "f32",
+                          initq_x3: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``init_q=True`` with decoder modes 1, 2 and 4 (inference): encoder features ``feat`` [B,64,H,W] -> RGB [B,3,Hu,Wu].
     (Mode 3 is ``decode_features(..., initq=...)``, which keeps refusing these modes.)
 
     ``packed`` = ``pack_state_dict(initq_body_state_dict(sd), mode=mode)``, ``initq`` = ``pack_initq(sd)``, ``head`` (mode 4) =
@@ -326,15 +327,26 @@ def decode_features_initq(feat: torch.Tensor, packed: torch.Tensor, initq: torch
     rows decoded -- for mode 4 of the tap rows [max(0, y0-1), min(Hu, y1+1)) (``diinn_initq_mode4_pix_bytes``), as is ``taps``
     (``diinn_mode4_taps_bytes``); both allocated if None.  ``planes_rows`` (mode 1): 512 (default; the planes kernel computes the 512
     GEMM rows mode 1 has, the chain takes its seeds from the biases) or 1280 (mode 2's form on the zero-widened image: the
-    same bits).  Enqueues three kernels on the current stream; never synchronises."""
+    same bits).  ``compute`` = "f32" (default) or "bf16x3": the split-bf16 arithmetic (``initq_planes_x3_kernel``,
+    ``pixel_chain_x3_kernel``, ``decode_bf16x3_kernel<SIN | X3_INITQ | X3_QONLY>`` or ``<.. | X3_TAPS>``), which needs
+    ``initq_x3 = pack_initq_x3(sd)`` on feat's device; the same workspaces, bands bit-identical to the whole image.  Any other
+    ``compute`` raises ``ValueError``.  Enqueues three kernels on the current stream; never synchronises."""
     lib = _native.load()
     if mode not in (1, 2, 4):
         raise NotImplementedError(f"decode_features_initq covers modes 1, 2 and 4 (mode 3: decode_features(..., initq=...)), got mode {mode}")
+    if compute not in ("f32", "bf16x3"):
+        raise ValueError(f"init_q=True with modes 1, 2 and 4 runs in 'f32' or 'bf16x3', got compute={compute!r}")
+    if compute == "bf16x3" and initq_x3 is None:
+        raise ValueError("compute='bf16x3' needs initq_x3, the init_q split image (pack_initq_x3)")
+    if compute == "f32" and initq_x3 is not None:
+        raise ValueError("initq_x3 is the image of compute='bf16x3'")
     if planes_rows not in ((None, 512, 1280) if mode == 1 else (None, 1280)):
         raise ValueError(f"planes_rows={planes_rows}: mode 1 takes 512 or 1280, modes 2 and 4 the 1280-row planes only")
     _require_cuda(feat, "feat")
     _require_cuda(packed, "packed weights")
     _require_cuda(initq, "init_q image")
+    if initq_x3 is not None:
+        _require_cuda(initq_x3, "init_q split image")
     feat, (b, h, w) = _checked_feat(feat)
     hu, wu = size
     hu, wu = int(hu), int(wu)
@@ -351,10 +363,16 @@ def decode_features_initq(feat: torch.Tensor, packed: torch.Tensor, initq: torch
     geometry = (b, h, w, hu, wu, y0, y1, int(sin_mode))
     if mode == 4:
         taps = _checked_buffer(taps, lib.diinn_mode4_taps_bytes(b, hu, wu, y0, y1), dev, "taps", False)
-        _launch("diinn_decode_initq_mode4", dev, feat, packed, initq, head, pix, taps, out, *geometry)
+        if initq_x3 is not None:
+            _launch("diinn_decode_initq_mode4_x3", dev, feat, packed, initq, initq_x3, head, pix, taps, out, *geometry)
+        else:
+            _launch("diinn_decode_initq_mode4", dev, feat, packed, initq, head, pix, taps, out, *geometry)
     else:
-        _launch("diinn_decode_initq_mode1" if mode == 1 and planes_rows != 1280 else "diinn_decode_initq_mode2", dev,
-                feat, packed, initq, pix, out, *geometry)
+        entry = "diinn_decode_initq_mode1" if mode == 1 and planes_rows != 1280 else "diinn_decode_initq_mode2"
+        if initq_x3 is not None:
+            _launch(entry + "_x3", dev, feat, packed, initq, initq_x3, pix, out, *geometry)
+        else:
+            _launch(entry, dev, feat, packed, initq, pix, out, *geometry)
     return out
 
 
@@ -589,12 +607,12 @@ class ImplicitDecoder(nn.Module):
     for mode 3, inference, fp32; with modes 1, 2, 4 (unless ``hip_initq_modes`` is set, below) or under autograd ``forward`` raises
     ``NotImplementedError``.
 
-    Eight opt-ins, each a plain attribute and a constructor keyword, default False.  Each opens exactly one more combination of
+    Nine opt-ins, each a plain attribute and a constructor keyword, default False.  Each opens exactly one more combination of
     (mode, ``init_q``, ``compute``, inference or autograd) and changes nothing for any other; "autograd" is ``forward(x, size,
     None)`` with grad enabled and something requiring it (``bsize`` given, or ``no_grad``, is the inference path, like the
     reference's ``batched_step``).  ``_route`` is the rule -- one table, every supported combination, the flag that opens it and
     the refusal everything else gets -- and ``tests/test_decoder_routes.py`` pins it for every setting of the first seven (the eighth:
-    ``tests/test_initq_split_training.py``).
+    ``tests/test_initq_split_training.py``; the ninth: ``tests/test_decoder_initq_modes_x3.py``).
 
     ==================================  ==========================================  ===========================  =============================
     flag                                opens                                       needs beside it              what keeps refusing with it
@@ -620,9 +638,12 @@ class ImplicitDecoder(nn.Module):
     ``hip_autograd_initq_split_bf16``   autograd, ``init_q``, mode 3, "bf16x3"      ``compute="bf16x3"`` and     init_q modes 1/2/4 in any
                                         both ways (``initq_split_training``;        ``hip_initq_split_bf16``     bf16, "bf16", "bf16_full",
                                         DESIGN.md 3.7g)                             (alone it does nothing)      graphs, sharded
+    ``hip_initq_modes_split_bf16``      inference, ``init_q``, modes 1/2/4,         ``compute="bf16x3"`` and     autograd in "bf16x3", "bf16",
+                                        "bf16x3" (``decode_features_initq(          ``hip_initq_modes``          "bf16_full", graphs, sharded
+                                        compute="bf16x3")``)        (alone it does nothing)
     ==================================  ==========================================  ===========================  =============================
 
-    ``compute="f32"`` gives the fp32 bits whatever is set.  ``DIINN.set_split_bf16()`` sets none of the four split flags: a user who
+    ``compute="f32"`` gives the fp32 bits whatever is set.  ``DIINN.set_split_bf16()`` sets none of the five split flags: a user who
     wants the split arithmetic on such a model sets both."""
 
     hip_autograd = False
@@ -633,12 +654,14 @@ class ImplicitDecoder(nn.Module):
     hip_autograd_split_bf16 = False
     hip_modes_split_bf16 = False
     hip_autograd_initq_split_bf16 = False
+    hip_initq_modes_split_bf16 = False
 
     def __init__(self, in_channels: int = 64, hidden_dims=(256, 256, 256, 256), mode: int = 1,
                  init_q: bool = False, sin_mode: int = _native.SIN_DEFAULT, compute: str = "f32", hip_autograd: bool = False,
                  hip_autograd_mode4: bool = False, hip_initq_modes: bool = False, hip_initq_split_bf16: bool = False,
                  hip_autograd_initq_modes: bool = False, hip_autograd_split_bf16: bool = False,
-                 hip_modes_split_bf16: bool = False, hip_autograd_initq_split_bf16: bool = False):
+                 hip_modes_split_bf16: bool = False, hip_autograd_initq_split_bf16: bool = False,
+                 hip_initq_modes_split_bf16: bool = False):
         super().__init__()
         self.mode = mode
         self.init_q = init_q
@@ -650,6 +673,7 @@ class ImplicitDecoder(nn.Module):
         self.hip_autograd_split_bf16 = bool(hip_autograd_split_bf16)
         self.hip_modes_split_bf16 = bool(hip_modes_split_bf16)
         self.hip_autograd_initq_split_bf16 = bool(hip_autograd_initq_split_bf16)
+        self.hip_initq_modes_split_bf16 = bool(hip_initq_modes_split_bf16)
         self.in_channels = in_channels
         self.hidden_dims = list(hidden_dims)
         self.sin_mode = sin_mode
@@ -749,6 +773,7 @@ class ImplicitDecoder(nn.Module):
         ("initq",           (3,),         True,  ("f32",),    ()),
         ("initq",           (3,),         True,  ("bf16x3",), ("hip_initq_split_bf16",)),
         ("initq_modes",     (1, 2, 4),    True,  ("f32",),    ("hip_initq_modes",)),
+        ("initq_modes",     (1, 2, 4),    True,  ("bf16x3",), ("hip_initq_modes", "hip_initq_modes_split_bf16")),
         (_INITQ_FP32_ONLY,  (1, 2, 3, 4), True,  None,        ()),
     )
     _AUTOGRAD_ROUTES = (
@@ -807,7 +832,8 @@ class ImplicitDecoder(nn.Module):
         Under autograd with ``bsize=None`` it raises unless ``hip_autograd`` is set (then: ``initq_training.DecodeInitqFunction``,
         the whole image at once).
 
-        ``init_q=True`` with modes 1, 2, 4 (``hip_initq_modes`` set; fp32, inference only): the same chunks of HR rows; mode 4
+        ``init_q=True`` with modes 1, 2, 4 (``hip_initq_modes`` set; fp32, or ``"bf16x3"`` with ``hip_initq_modes_split_bf16`` set as
+        well; inference only): the same chunks of HR rows in either arithmetic; mode 4
         computes the planes and the taps of a chunk's rows plus one row each way, clipped to the image, and it is those
         ``initq_chunk_rows`` rows that stay within the cap (a chunk is two output rows shorter).  Chunks change no bit,
         ``bsize`` is ignored, and mode 4 reproduces ``bsize=None`` as it does without ``init_q``.  Under autograd with ``bsize=None``
@@ -850,9 +876,10 @@ class ImplicitDecoder(nn.Module):
         # does without init_q -- so a chunk is two output rows shorter (16 + 2 tap rows would start a third block row of both
         # kernels: B = 16 of 48 x 48 x4 measured 22.8 ms that way against the eager sequence's 21.4)
         halo = 2 if self.mode == 4 else 0
+        # (fp32: the call as it always was; the split arithmetic adds its two keywords)
         return self._decode_chunks(x, size, chunk - halo, halo, lambda packed, out, rows, pix, taps: decode_features_initq(
             x, packed, self._packed_initq, out.shape[2:], self.mode, head=self._packed_head, taps=taps, pix=pix, rows=rows, out=out,
-            sin_mode=self.sin_mode))
+            sin_mode=self.sin_mode, **({"compute": "bf16x3", "initq_x3": self._packed_initq_x3} if x3 else {})))
 
     def _workspace(self, cache, numel: int, device) -> torch.Tensor:
         """An fp32 buffer of at least ``numel`` from ``cache``, one per (device, stream) that called forward."""

@@ -341,6 +341,41 @@ def modes_x3_forward_reference(sd, feat, size, mode: int, prefix: str = "") -> t
     return head3x3(get, q, g) if mode == 4 else head1x1(get, q, g)
 
 
+def initq_modes_x3_forward_reference(sd, feat, size, mode: int, prefix: str = "") -> torch.Tensor:
+    """The EMULATION sheet of the split-bf16 arithmetic of ``init_q=True`` with decoder modes 1, 2 and 4
+    (``decode_features_initq(..., compute="bf16x3")``), in fp32 torch algebra on any device; beside
+    ``initq_forward_reference(..., split_bf16=True)`` (mode 3) and ``modes_x3_forward_reference`` (``init_q=False``).
+
+    What is split (``split_matmul``: every operand as hi = bf16(v), lo = bf16(v - hi), the product ``(w_lo.x_hi + w_hi.x_lo) +
+    w_hi.x_hi`` in fp32 torch matmuls, not the MFMA's summation order): both planes GEMMs on ``E`` and ``x'`` as
+    ``initq_planes_reference`` forms them (mode 1: ``K_0`` and ``Q_0`` only, the seeds of layers 1..3 are ``bK_i``); the
+    per-pixel chain of modes 1/2, ``k_i = relu(split_matmul(K_i[:, :256], k_{i-1}) + seed_i)`` (``pixel_chain_x3_kernel``); mode
+    4's ``K_i[:, :256] . q_{i-1}``; and the synthesis products on ``Q_i * fp32(1/(2 pi))``.  The synthesis branch runs in
+    REVOLUTIONS and every sine is taken of revolutions in float64 (``sin_rev``).
+
+    What stays fp32: ``E``'s fma sequence, ``x' = E * X``, seeds, biases, ReLU, and the head on the unsplit ``q_3`` -- ``L . q_3 +
+    bL`` (modes 1/2) or the 27 tap values per pixel and the reflect-padded 9-point gather (mode 4)."""
+    if mode not in (1, 2, 4):
+        raise ValueError(f"initq_modes_x3_forward_reference states modes 1, 2 and 4 (mode 3: initq_forward_reference(split_bf16=True)), got {mode}")
+    f32 = torch.float32
+    get = tensor_getter(sd, prefix, feat.device, f32)
+    inv = torch.tensor(INV_2PI_F32, dtype=f32, device=feat.device)
+    x = feat.to(f32)
+    g = geometry(x.shape[2], x.shape[3], size, feat.device)
+    e = sin_rev(coordinate_fma(g, get("first_layer.0.weight", (UNFOLD, 3)) * inv, get("first_layer.0.bias", (UNFOLD, 1)) * inv))
+    xp = e[None] * gather_unfold(x, g)                                                  # [b, 576, n], fp32
+    kw, bk = _k_layers(get, mode)
+    k = torch.relu(split_matmul(get("K.0.0.weight", (HIDDEN, UNFOLD)), xp) + bk[0])     # PIX[0:256]
+    a0 = split_matmul(get("Q.0.0.weight", (HIDDEN, UNFOLD)) * inv, e) + get("Q.0.0.bias", (HIDDEN, 1)) * inv   # PIX[1024:1280]
+    q = k * sin_rev(a0)[None]
+    for i in (1, 2, 3):
+        seed = bk[i] if mode == 1 else split_matmul(kw[i - 1][:, HIDDEN:], xp) + bk[i]  # PIX[256 i : 256 i + 256]
+        k = torch.relu(split_matmul(kw[i - 1][:, :HIDDEN], q if mode == 4 else k) + seed)
+        s = split_matmul(get(f"Q.{i}.0.weight", (HIDDEN, HIDDEN)) * inv, q) + get(f"Q.{i}.0.bias", (HIDDEN, 1)) * inv
+        q = k * sin_rev(s)
+    return head3x3(get, q, g) if mode == 4 else head1x1(get, q, g)
+
+
 def liif_x3_forward_reference(sd, feat, size, prefix: str = "imnet.") -> torch.Tensor:
     """The EMULATION sheet of the split-bf16 arithmetic of the LIIF comparison decoder (``liif_decode_features(..., split=...)``,
     ``liif_x3_kernel``), in fp32 torch algebra on any device: the reference's form (liif.py:59-127) with the three hidden

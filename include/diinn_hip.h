@@ -431,6 +431,33 @@ int    diinn_decode_initq_mode4(void* stream, const float* feat_dev, const float
                                 const float* head_dev, float* pix_dev, float* taps_dev, float* out_dev,
                                 int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
 
+/* ---- decoder init_q=True with modes 1, 2 and 4 in split-bf16 arithmetic (inference, every sine_mode) -------------------
+ * The entry points above with the two planes GEMMs, the per-pixel chain of modes 1/2 and the 256 x 256 products of layers 1..3
+ * in the arithmetic of DIINN_COMPUTE_BF16X3 (w_lo.x_hi + w_hi.x_lo + w_hi.x_hi on the bf16 MFMA, fp32 accumulation); E, x',
+ * seeds, biases, sines and the head (1x1, or the 27 taps on the unsplit q_3 and the gather) stay fp32.  The same images plus
+ * the init_q split image (diinn_pack_initq_x3), the same PIXEL PLANES record, the same workspaces and sizes.
+ * diinn_initq_planes_m1_x3: diinn_initq_planes_x3 for mode 1 -- channels 0..255 and 1024..1279 only (the bits of the same
+ *   channels of diinn_initq_planes_x3), channels 256..1023 UNWRITTEN.
+ * diinn_pixel_chain_x3: diinn_pixel_chain's contract, arguments and checks; K_i[:, :256] from section WLX of the body image
+ *   (a body image without its derived sections gives NaN), k_{i-1} split from the fp32 value the record holds.
+ * diinn_decode_initq_mode1_x3 / _mode2_x3: planes (_m1 form for mode 1), chain, band decode, in order.
+ * diinn_decode_initq_mode4_x3: planes of the tap rows [ty0,ty1), the tap form, the gather (unchanged).
+ * Every image and pix_dev must be 16-byte aligned; every argument is validated before the first launch.  A band is
+ * BIT-IDENTICAL to the same rows of a whole-image decode. */
+int    diinn_initq_planes_m1_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                const float* initq_x3_dev, float* pix_dev, int B, int H, int W, int Hu, int Wu, int y0,
+                                int y1, int sin_mode);
+int    diinn_pixel_chain_x3(void* stream, float* pix_dev, const float* packed_dev, int B, int Wu, int rows, int bk_seeds);
+int    diinn_decode_initq_mode1_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                   const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu,
+                                   int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq_mode2_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                   const float* initq_x3_dev, float* pix_dev, float* out_dev, int B, int H, int W, int Hu,
+                                   int Wu, int y0, int y1, int sin_mode);
+int    diinn_decode_initq_mode4_x3(void* stream, const float* feat_dev, const float* packed_dev, const float* initq_dev,
+                                   const float* initq_x3_dev, const float* head_dev, float* pix_dev, float* taps_dev,
+                                   float* out_dev, int B, int H, int W, int Hu, int Wu, int y0, int y1, int sin_mode);
+
 /* ---- decoder init_q=True, mode 3, under autograd (diinn.py:48-51,113-115,132-139 recorded by autograd; caller
  * SRLitModule.training_step, sr_module.py:127-129).  Tiled planes: see "training" below. ---------------------------
  * TRAINING IMAGE.  diinn_pack_initq_train(Fw [576][3], Fb [576], Q0w [256][576], Q0b [256], K0w [256][576],
