@@ -95,6 +95,91 @@ def pack_conv_x3(weight: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# the split-bf16 trunk's emulation sheets (test infrastructure: plain torch on CPU tensors, no kernel is touched)
+# ---------------------------------------------------------------------------
+# The faults a sheet can carry (``fault=``): what a wrong split-format kernel would do, applied to the emulation so that a test
+# can show that it would notice (tests/test_encoder_trunk_x3.py).  Never set outside tests.
+X3_FAULTS = ("lo_vector",       # the lo half of ONE 8-channel vector (group 3, the middle pixel) of the last dense layer's output zeroed
+             "lo_last_pixel",   # the lo halves of the map's last pixel zeroed in every dense layer's output
+             "wlo_tail",        # w_lo . x_hi dropped for the last 16 input channels of the Cin = 512 layer
+             "lo_layer",        # every lo half of the last dense layer's output zeroed
+             "trunc")           # lo formed by truncation instead of round-to-nearest-even
+
+
+def _bf16_rne(v: torch.Tensor) -> torch.Tensor:
+    return v.to(torch.bfloat16).to(torch.float32)
+
+
+def split_pair(v: torch.Tensor, fault: Optional[str] = None):
+    """fp32 -> the split pair the kernels store: hi = bf16_rne(v), lo = bf16_rne(v - hi), both as float32."""
+    hi = _bf16_rne(v)
+    r = v - hi
+    lo = (r.contiguous().view(torch.int32) & -65536).view(torch.float32) if fault == "trunc" else _bf16_rne(r)
+    return hi, lo
+
+
+def unpack_conv_x3(image: torch.Tensor, cin: int, k: int):
+    """The inverse of ``pack_conv_x3``: its image of a [64, cin, k, k] weight -> (hi, lo) as float32 [64, cin, k, k]."""
+    parts = image.contiguous().view(torch.int16).reshape(cin // 16, k * k, 2, 2, 2, 32, 8)    # [g, tap, mt, part, h, m, j]
+    parts = parts.permute(3, 2, 5, 0, 4, 6, 1).contiguous().view(torch.bfloat16)              # [part, mt, m, g, h, j, tap]
+    hi, lo = parts.reshape(2, 64, cin, k, k).to(torch.float32)
+    return hi, lo
+
+
+def split_planes_decode(xs: torch.Tensor):
+    """The trunk's split activation buffer viewed as int16 [B, 72, 2, H*W, 8] ([b][group of 8 channels][hi, lo][pixel][j],
+    channel = 8 group + j: csrc/diinn_conv_x3.hip) -> (hi, lo) as float32 [B, 576, H*W]."""
+    b, groups, _, hw, _ = xs.shape
+    v = xs.contiguous().view(torch.bfloat16).permute(2, 0, 1, 4, 3).reshape(2, b, 8 * groups, hw).to(torch.float32)
+    return v[0], v[1]
+
+
+def conv_x3_reference(x_hi, x_lo, weight, bias, padding, relu=True, residual=None, fault: Optional[str] = None):
+    """The emulation sheet of one split-bf16 layer: the operands as bf16-exact float32 hi / lo parts, the three products
+    w_lo.x_hi + w_hi.x_lo + w_hi.x_hi as float32 convolutions added in that order, then bias, ReLU and the residual in fp32
+    (``conv3x3_x3_kernel`` / ``conv1x1_x3_kernel``; what it does not model is the order of the fp32 sums inside a product).
+    Returns (v, hi, lo): the output as fp32 and as the split pair the kernel stores.  ``fault``: one of X3_FAULTS, tests only."""
+    import torch.nn.functional as F
+    w = weight.detach().to(torch.float32)
+    w_hi, w_lo = split_pair(w)
+    if fault == "wlo_tail" and w.shape[1] == 512:
+        w_lo = w_lo.clone()
+        w_lo[:, -16:] = 0
+    v = F.conv2d(x_hi, w_lo, None, padding=padding) + F.conv2d(x_lo, w_hi, None, padding=padding)
+    v = v + F.conv2d(x_hi, w_hi, None, padding=padding)
+    v = v + bias.detach().to(torch.float32).view(1, -1, 1, 1)
+    if relu:
+        v = v.relu()
+    if residual is not None:
+        v = v + residual
+    hi, lo = split_pair(v, fault)
+    return v, hi, lo
+
+
+def rdb_x3_reference(block, x, fault: Optional[str] = None):
+    """The sheet of one residual dense block (modules.RDB) inside the split-bf16 trunk, from its fp32 input ``x`` [B,64,H,W]: the
+    input split, eight dense layers that read and write split pairs only, the 1x1 fusion layer over all 576 channels plus ``x``.
+    Returns (out, out_hi, out_lo, dense_hi, dense_lo): the block's fp32 output, its split pair, and the split pairs of the eight
+    dense outputs as [B,512,H,W] -- what the trunk leaves in its fusion input, in groups 0..7 and in groups 8..71 of its split
+    buffer.  ``fault``: one of X3_FAULTS, tests only."""
+    hi, lo = split_pair(x, fault if fault == "trunc" else None)
+    last = len(block.convs) - 1
+    for c, layer in enumerate(block.convs):
+        conv = layer.conv[0]
+        _, h, l = conv_x3_reference(hi, lo, conv.weight, conv.bias, 1, fault=fault if fault in ("wlo_tail", "trunc") else None)
+        if fault == "lo_last_pixel":
+            l[:, :, -1, -1] = 0
+        if c == last and fault == "lo_layer":
+            l.zero_()
+        if c == last and fault == "lo_vector":
+            l[0, 24:32, l.shape[2] // 2, l.shape[3] // 2] = 0
+        hi, lo = torch.cat([hi, h], 1), torch.cat([lo, l], 1)
+    out, out_hi, out_lo = conv_x3_reference(hi, lo, block.LFF.weight, block.LFF.bias, 0, relu=False, residual=x,
+                                            fault="trunc" if fault == "trunc" else None)
+    return out, out_hi, out_lo, hi[:, 64:], lo[:, 64:]
+
+
+# ---------------------------------------------------------------------------
 # which kernel family runs a 3x3 layer, its image, its launch
 # ---------------------------------------------------------------------------
 def conv_form(b: int, h: int, w: int) -> str:
